@@ -14,6 +14,9 @@ Extra objects: `roofline` (dominant kernel family, HIP-event timed in an instrum
 the launch stream; algorithmic bytes = input read once + output written once per conv)
 and `cpu_baseline` (the CPU oracle = port of the reference path, timed on the host cores on a
 bounded sample; rank 0, N=1 only).
+`--dump-outputs DIR` (rank 0): after the timed steps, what the last one returned to its caller, as DIR/<name>.npy
+(float32 / float64, at most 64 MB).  Inputs, weights and random draws are seeded, and the last timed step of a training
+workload starts from the initial state, so the same arguments dump the same step.
 """
 import argparse
 import json
@@ -44,6 +47,45 @@ def load_traffic(entry_point):
     return None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 tensors as float64 and every other
+    dtype as float32, at most `budget` bytes in all.  Smaller arrays are written whole in their own shape; an array
+    larger than its share of what is left becomes a 1-D sample at fixed, seeded positions (sorted flat indices), so
+    two builds given the same arguments write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].numel(), k))
+    left = budget
+    for i, name in enumerate(names):
+        t = arrays[name].detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        cap = left // (len(names) - i) // esz
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return names
+
+
+def step_outputs(workload, res):
+    """name -> tensor: what a caller of the timed path holds after its last step."""
+    import torch
+    if workload == "infer":                      # (sem_out, sem_argmax)
+        return {"sem_out": res[0], "sem_argmax": res[1]}
+    if isinstance(res, dict):                    # Trainer: [ce, dice] and [ins_cost (finite part), criterion, ins_ce, ins_dice]
+        out = {"sem_losses": res["sem"], "head_losses": res["head"]}
+    else:                                        # ReSeg.forward(True, ...) (--no-graph train_fwd)
+        out = {"sem_out": res[0], "sem_argmax": res[1], "head_losses": torch.stack([s.reshape(()) for s in res[2:]])}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -55,7 +97,12 @@ def main():
     ap.add_argument("--workload", default="auto", choices=["auto", "train_step", "train_fwd", "infer"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy, "
+                         "at most 64 MB; rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     def log(msg):
         print("[bench] " + msg, file=sys.stderr, flush=True)
@@ -76,6 +123,9 @@ def main():
     if rehearsal:
         local_rank = local_rank % torch.cuda.device_count()
     torch.cuda.set_device(local_rank)
+    # the step's own random draws (Dropout2d masks, the sampled glimpse points) come from torch's generators: seeded, so
+    # that the same arguments give the same inputs from run to run
+    torch.manual_seed(1000 + rank)
     if world > 1:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         if rehearsal:
@@ -107,30 +157,44 @@ def main():
         trainer = Trainer(model, world_size=world)
 
         def eager_step():
-            trainer.train_step(x, sem, ins, n, selected_idx=sel)
+            return trainer.train_step(x, sem, ins, n, selected_idx=sel)
 
         def step():
             if args.no_graph:
-                eager_step()
-            else:               # hipGraph replay of the same launches (trainer.py: train_step_graphed)
-                trainer.train_step_graphed(x, sem, ins, n, selected_idx=sel)
+                return eager_step()
+            # hipGraph replay of the same launches (trainer.py: train_step_graphed)
+            return trainer.train_step_graphed(x, sem, ins, n, selected_idx=sel)
     elif workload == "train_fwd":
         model.train()
         trainer = Trainer(model, world_size=world)
 
         def step():
             if args.no_graph:
-                model(True, x, sem, ins, n, selected_idx=sel)
-            else:               # the training-mode forward alone (batch statistics, sampling, Dropout2d, losses), graph-replayed
-                trainer.train_step_graphed(x, sem, ins, n, selected_idx=sel, forward_only=True)
+                return model(True, x, sem, ins, n, selected_idx=sel)
+            # the training-mode forward alone (batch statistics, sampling, Dropout2d, losses), graph-replayed
+            return trainer.train_step_graphed(x, sem, ins, n, selected_idx=sel, forward_only=True)
     else:
         model.eval()
 
         def step():
             if args.no_graph:
-                model(False, x)
-            else:
-                model.infer_graphed(x)      # hipGraph replay of the same launches (reseg.py)
+                return model(False, x)
+            return model.infer_graphed(x)       # hipGraph replay of the same launches (reseg.py)
+
+    # The state a training step carries into the next: the flat store (parameters, BatchNorm running statistics), the
+    # optimizer's running averages and the REINFORCE baseline (zeros when the first step creates it).  Float-atomic
+    # summation order and bf16 rounding make that state drift apart between two runs of the same command within a few
+    # steps, so the last timed step starts again from the initial state: its inputs then repeat from run to run, and
+    # --dump-outputs can compare two builds.  The restore is three device copies issued before that step, in every run.
+    initial = [(t, t.clone()) for t in (model.store.flat, trainer.sq, trainer.acc)] if trainer is not None else []
+
+    def restart():
+        for t, t0 in initial:
+            t.copy_(t0)
+        if model.head.baseline is not None:
+            model.head.baseline.zero_()
+        # (no repack request needed: a training step has marked the weights dirty already, a forward-only step
+        # leaves them as they were)
 
     def sync_all():
         torch.cuda.synchronize()
@@ -159,10 +223,15 @@ def main():
     sync_all()
     log("timing %d steps" % args.steps)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if initial and i == args.steps - 1:
+            restart()
+        res = step()
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # before the instrumented step below overwrites the step's buffers
+        names = dump_outputs(args.dump_outputs, step_outputs(workload, res))
+        log("wrote %s under %s" % (", ".join(n + ".npy" for n in names), args.dump_outputs))
     if world > 1:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
