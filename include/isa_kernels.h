@@ -259,7 +259,13 @@ typedef struct isa_bn_upd {
 } isa_bn_upd;
 int isa_bn_running_update(const isa_bn_upd* upd, int32_t n, float momentum, void* stream);
 /* backward of t = act(scale*y+shift): reduce pass  red[2C] += (sum dz, sum dz*yhat),
- * then apply pass  dy = gamma*invstd*(dz - red0/count - yhat*red1/count)  (in place over dt ok) */
+ * then apply pass  dy = gamma*invstd*(dz - red0/count - yhat*red1/count)  (in place over dt ok).
+ * dz = dt * act'(z) (* bscale[b][c]), yhat = (y - mean) * invstd.
+ * red != NULL (either mode): dbeta += red0 and dgamma += red1 (each may be NULL), once per group and channel.
+ * train != 0: red is required and the apply subtracts the batch-statistics terms above.
+ * train == 0 (eval-mode BatchNorm2d, constants from the running statistics): dy = scale * dz; pass the sums of a
+ * reduce pass over the same dt as `red` to get torch's dbeta = sum dz, dgamma = sum dz * yhat, or NULL for none.
+ * Activation only (NULL constants, NULL red, count 1, train 0): dy = dt * act'(y). */
 int isa_bn_bwd_reduce(const isa_tensor* dt, const isa_tensor* y, const float* scale,
                       const float* shift, const float* mean, const float* invstd, int32_t act,
                       const float* bscale, float* red, void* stream);
@@ -293,7 +299,8 @@ int isa_avgpool3(const isa_tensor* x, const isa_tensor* mask, const isa_tensor* 
                  void* stream);
 
 /* ---- squeeze-excite gate + heads (utils.py:402-420, reseg.py:72-75,116-120) ------------------ */
-/* mean over h*w of pro(x), ADDED to out[n,c] (float atomics from several workgroups per image): zero it first */
+/* mean over h*w of pro(x), ADDED to out[n,c] (float atomics from several workgroups per image): zero it first.
+ * The whole prologue is honoured: per-group scale/shift [G][c] for a grouped x, then the activation, then bscale[n][c]. */
 int isa_chan_mean(const isa_tensor* x, const isa_pro* pro, float* out, void* stream);
 /* gate[n,c] = sigmoid(W2 relu(W1 m + b1) + b2); hidden/intermediates kept for backward */
 int isa_se_fc(const float* mean, const float* w1, const float* b1, const float* w2,

@@ -95,7 +95,7 @@ struct BnBwdParams {
     View dt, y, dy;
     const float *scale, *shift, *mean, *invstd, *bscale, *gamma, *red;
     float* out_red; float* dgamma; float* dbeta;
-    float inv_count; int act, train;
+    float inv_count; int act, train;      // train: red feeds k0 / k1; red (either mode): dgamma / dbeta
     long pixels; int cg;
     int groups;                  // statistic groups (blockIdx.z): pixels / wk.pixels are per group
 };
@@ -134,9 +134,10 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p, Walk wk) {
     if (!APPLY) {
         for (int i = threadIdx.x; i < 2 * C; i += 256) red[i] = 0.f;
         __syncthreads();
-    } else if (p.train) {
+    } else if (p.red) {
         // fold the ISA_STAT_R replicas of the reduce pass once per workgroup, for the channels this workgroup
-        // owns (blockIdx.y = channel chunk on wide tensors)
+        // owns (blockIdx.y = channel chunk on wide tensors).  They are dbeta / dgamma in both modes; only train
+        // mode also uses them below (the batch statistics' share of the gradient)
         const int cw = 8 << wk.sh;                                // channels per chunk
         for (int cb = blockIdx.y * cw; cb < C; cb += gridDim.y * cw) {
             for (int i = threadIdx.x; i < 2 * cw; i += 256) {
@@ -450,12 +451,18 @@ __global__ __launch_bounds__(256) void avgpool3_vec_kernel(Pool3Params p) {
     }
 }
 
-// per-(image,channel) mean of pro(x): grid = (blocks, n)
-struct MeanParams { View x; ProDev pro; float* out; float inv_hw; };
+// per-(image,channel) mean of pro(x): grid = (blocks, n).  groups > 1: image b takes the constants of its statistic
+// group b / (n / groups); bscale [n][c] multiplies after the activation, as in every other prologue
+struct MeanParams { View x; ProDev pro; float* out; float inv_hw; int groups; };
 template <typename T>
 __global__ __launch_bounds__(256) void chan_mean_kernel(MeanParams p) {
     extern __shared__ float red[];            // [C]
     const int C = p.x.c, cg = C / 8, b = blockIdx.y;
+    if (p.groups > 1) {
+        const long g = b / (p.x.n / p.groups);
+        p.pro.scale = goff(p.pro.scale, g * C); p.pro.shift = goff(p.pro.shift, g * C);
+    }
+    const float* bs = goff(p.pro.bscale, (long)b * C);
     for (int i = threadIdx.x; i < C; i += 256) red[i] = 0.f;
     __syncthreads();
     const long hw = (long)p.x.h * p.x.w, items = hw * cg;
@@ -475,7 +482,9 @@ __global__ __launch_bounds__(256) void chan_mean_kernel(MeanParams p) {
             float z = v[j];
             if (p.pro.scale) z *= p.pro.scale[c0 + j];
             if (p.pro.shift) z += p.pro.shift[c0 + j];
-            s[j] += act_apply(z, p.pro.act);
+            z = act_apply(z, p.pro.act);
+            if (bs) z *= bs[c0 + j];
+            s[j] += z;
         }
     }
     if (last_c0 >= 0) {
@@ -824,9 +833,9 @@ extern "C" int isa_avgpool3(const isa_tensor* x, const isa_tensor* mask, const i
 }
 
 extern "C" int isa_chan_mean(const isa_tensor* x, const isa_pro* pro, float* out, void* stream) {
+    if (!tensor_ok(x, 8) || x->c % 8 || !out || x->n % tensor_groups(x)) return ISA_EINVAL;
     if (pro && pro->fin) { if (int rc = fin_standalone(pro, x->c, tensor_groups(x), as_stream(stream))) return rc; }   // no in-kernel form here
-    if (!tensor_ok(x, 8) || x->c % 8 || !out) return ISA_EINVAL;
-    MeanParams p{mkview(x), make_pro(pro), out, 1.f / ((float)x->h * x->w)};
+    MeanParams p{mkview(x), make_pro(pro), out, 1.f / ((float)x->h * x->w), tensor_groups(x)};
     const long items = (long)x->h * x->w * (x->c / 8);
     dim3 grid(grid_cap(cdiv(items, 256), 128), x->n);
     DISPATCH_T(x->dtype,

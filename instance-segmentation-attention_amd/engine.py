@@ -1082,12 +1082,14 @@ class Engine:
 
     def _bn_backward(self, lazy: Act, dt: Act, dy: Act, bscale, do_apply=True):
         """reduce (sum g', sum g'*xhat) then apply; `red_done` on the layer means a fused producer
-        already wrote the sums; do_apply=False leaves the apply to a fused consumer and returns them."""
+        already wrote the sums; do_apply=False leaves the apply to a fused consumer and returns them.
+        Eval mode needs the sums too: they are dbeta / dgamma (torch's eval BatchNorm2d backward, xhat from the running
+        statistics), though the apply does not subtract them from the data gradient."""
         b = lazy.bn
         P = self.params
         red = b.pop("red_done", None)
         nb = lazy.n * lazy.h * lazy.w * lazy.c * lazy.buf.element_size()
-        if b["train"] and red is None:
+        if red is None:
             red = self.scratch(2 * lazy.c * STAT_R * lazy.groups)
             if self.profile:
                 self.next_bytes = 2 * nb
