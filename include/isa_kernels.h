@@ -64,9 +64,10 @@ typedef struct isa_tensor {
  * updates.  The arithmetic is isa_bn_finalize's (the same device function).  It removes a ~5 us launch from the dependency
  * chain of every BatchNorm (nn.BatchNorm2d forward in train mode, torch/nn/modules/batchnorm.py; the reference's
  * MobileNetDenseASPP.py:68-123 blocks have three each).  Entry points that take an isa_pro but have no in-kernel form
- * (isa_chan_mean, the non-tiled depthwise fallback, the weight-gradient and fused backward entry points, the eval-epilogue
- * GEMM) run isa_bn_finalize on the same stream first, so
- * a non-NULL fin is always honoured.  c <= ISA_FIN_MAX_C in-kernel, wider layers take the launch. */
+ * (isa_chan_mean, the weight-gradient and fused backward entry points, the eval-epilogue GEMM) run isa_bn_finalize on
+ * the same stream ahead of their own kernels, so a non-NULL fin is always honoured.  They launch it after every argument
+ * and workspace check: a call that returns ISA_EINVAL, ISA_EALIGN or ISA_ENOMEM has changed nothing.  c <= ISA_FIN_MAX_C
+ * in-kernel, wider layers take the launch. */
 #define ISA_FIN_MAX_C 1024
 typedef struct isa_bn_fin {
     const float* stats;        /* [G][ISA_STAT_REPLICAS][2c] sums of the batch, complete on this stream */
@@ -163,8 +164,6 @@ int isa_conv_wgrad(const isa_tensor* x, const isa_pro* pro, const isa_tensor* dy
                    float* dw, float* dbias, int32_t in_mode, int32_t out_mode,
                    const int32_t* kmap, int32_t ksrc, float* ws, int64_t ws_floats, isa_slab_arena* defer,
                    void* stream);
-/* out[c] += sum over all pixels of x[.,c]  (bias gradients) */
-int isa_colsum(const isa_tensor* x, float* out, void* stream);
 
 /* ---- depthwise 3x3, pad 1 (MobileNetDenseASPP.py:77,109; reseg.py:79,93) ---------------------
  * y = dw3x3(pro(x)) (+bias); w packed [9][C] (kind 4); stats as above.                         */
@@ -291,8 +290,6 @@ int isa_axpy(const isa_tensor* src, const isa_tensor* dst, float alpha, int32_t 
 /* 2x2 mean, stride 2 == F.interpolate(scale=0.5,bilinear) on even sizes (unet_parts.py:58) */
 int isa_avgpool2(const isa_tensor* x, const isa_tensor* y, void* stream);
 int isa_avgpool2_bwd(const isa_tensor* dy, const isa_tensor* dx, int32_t accumulate, void* stream);
-/* f x f max / mean pooling with stride f of small-channel maps (utils.py:841-846) */
-int isa_pool_f(const isa_tensor* x, const isa_tensor* y, int32_t f, int32_t is_max, void* stream);
 /* 3x3 mean, stride 1, pad 1, count_include_pad (utils.py:634,645); optional per-pixel mask mul;
  * y (+)= ...: the operator is self-adjoint, so the same call with accumulate is its backward */
 int isa_avgpool3(const isa_tensor* x, const isa_tensor* mask, const isa_tensor* y, int32_t accumulate,

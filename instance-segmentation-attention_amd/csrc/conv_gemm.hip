@@ -19,7 +19,6 @@
 //   * bf16 storage: v_mfma_f32_32x32x16_bf16, fp32 accumulate.  f32 storage: v_mfma_f32_32x32x2_f32
 //     (exact fp32 FMA chain) — used for the 1e-3 parity mode.
 #include "common.hpp"
-#include <cstdlib>
 
 int conv3x3_tiled_launch(const isa_tensor* x, const void* w, const float* bias, const isa_tensor* y, int accumulate,
                          hipStream_t s);          // conv3x3_tiled.hip: narrow dense 3x3 convs from an LDS halo tile
@@ -117,13 +116,14 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(GemmParams p) {
     // A pending finalize of the input's BatchNorm (isa_pro.fin, train mode) runs in this kernel: this group's scale / shift
     // go straight into the table.  One dword of the cache line of this lane's first fragment is requested ahead of it, so
     // the round trip to the input overlaps the one to the statistics instead of following it (running the finalize inside
-    // the tile loop, behind the real fragment load, costs these kernels an occupancy step).
+    // the tile loop, behind the real fragment load, costs these kernels an occupancy step).  The probe stays within the
+    // pixel's first rup(cin, 8) elements: the upper half-wave's offset 16 only when cin > 16.
     bool fin_live = false;
     if constexpr (HAS_PRO && !EP) {
         if (p.fin.stats != nullptr) {
             long m = (long)gs.bx * 128 + wave * 32 + r;
             if (m > p.M - 1) m = p.M - 1;
-            const T* touch = reinterpret_cast<const T*>(p.x) + (IN_MODE == ISA_IN_GATHER2 ? 0 : m * p.ldx + 16 * hh);
+            const T* touch = reinterpret_cast<const T*>(p.x) + (IN_MODE == ISA_IN_GATHER2 ? 0 : m * p.ldx + (p.cin > 16 ? 16 * hh : 0));
             const unsigned probe = *reinterpret_cast<const unsigned*>(touch);
             asm volatile("" ::: "memory");                        // keep the request ahead of the finalize
             bn_fin_inline<256>(p.fin, p.cin, p.G, gs.g, pro_tab, p.kp, tid);
@@ -738,16 +738,27 @@ int launch_tiled(const GemmParams& p, bool has_pro, hipStream_t s) {
     return p.ep_scale ? launch_tiled_ep<WN, true>(p, has_pro, s) : launch_tiled_ep<WN, false>(p, has_pro, s);
 }
 
+// Kernel selection thresholds, fixed so that the choice is a function of the arguments alone (A/B by loading another build).
+// GEMM_FAST: plain 1x1 launches with at least GEMM_FAST_MIN_GROUPS K/32 groups take the straight-line K loop (unconditional
+// fragment loads, next tile's first fragment requested before the epilogue).  Measured: on HBM-cold single launches
+// (KBENCH_ROTATE) K = 128 gains (58.7 -> 51.9 us at 128x128), K = 64 is neutral and K = 32 loses a little (31.0 vs 29.5 us);
+// inside the training step taking it for every eligible launch is the best setting (same-session A/B, images/s: off 590.8,
+// >= 4 groups 590.2, >= 2 groups 591.1, all 593.0).
+constexpr bool GEMM_FAST = true;
+constexpr int GEMM_FAST_MIN_GROUPS = 1;
+// bf16 1x1 convolutions with K >= TILED_MIN_K over at most TILED_MAX_M pixels take the LDS-tiled small-GEMM kernel, with
+// 128-wide column tiles from TILED_WIDE_MIN workgroups on (after the batch doubled: 25.3-25.5 ms per step, flat)
+constexpr long TILED_MAX_M = 65536;
+constexpr int TILED_MIN_K = 128;
+constexpr long TILED_WIDE_MIN = 512;
+// resident workgroups per CU of the streaming kernel (measured: 2 -> 36.5 ms, 3 -> 36.3, 4 -> 36.9)
+constexpr int WG_PER_CU = 3;
+
 template <typename T, int NT, int IN_MODE, int OUT_MODE>
 int launch2(const GemmParams& p, bool has_pro, dim3 grid, size_t lds, hipStream_t s) {
     if constexpr (IN_MODE == ISA_IN_1X1 && OUT_MODE == ISA_OUT_PLAIN) {
-        static const bool fast_ok = !(getenv("ISA_GEMM_FAST") && atoi(getenv("ISA_GEMM_FAST")) == 0);
-        // Measured: on HBM-cold single launches (KBENCH_ROTATE) K = 128 gains (58.7 -> 51.9 us at 128x128), K = 64 is neutral and
-        // K = 32 loses a little (31.0 vs 29.5 us); inside the training step taking it for every eligible launch is the best
-        // setting (same-session A/B, images/s: off 590.8, >= 4 groups 590.2, >= 2 groups 591.1, all 593.0).  With a prologue
-        // the wider tiles would cross an occupancy step, so those stay on the general path.
-        static const int fast_min_groups = getenv("ISA_GEMM_FAST_MIN_GROUPS") ? atoi(getenv("ISA_GEMM_FAST_MIN_GROUPS")) : 1;
-        if (fast_ok && p.cin == p.kp && p.total_groups >= fast_min_groups && !p.ep_scale && (!has_pro || NT == 1)) {
+        // with a prologue the wider tiles would cross an occupancy step, so those stay on the general path
+        if (GEMM_FAST && p.cin == p.kp && p.total_groups >= GEMM_FAST_MIN_GROUPS && !p.ep_scale && (!has_pro || NT == 1)) {
             if (has_pro && p.pro.act == ISA_ACT_RELU6) hipLaunchKernelGGL((conv_gemm_kernel<T, NT, IN_MODE, OUT_MODE, 1, false, true>), grid, dim3(256), lds, s, p);
             else if (has_pro) hipLaunchKernelGGL((conv_gemm_kernel<T, NT, IN_MODE, OUT_MODE, 2, false, true>), grid, dim3(256), lds, s, p);
             else hipLaunchKernelGGL((conv_gemm_kernel<T, NT, IN_MODE, OUT_MODE, 0, false, true>), grid, dim3(256), lds, s, p);
@@ -787,15 +798,12 @@ template <typename T>
 int launch0(GemmParams& p, bool has_pro, int in_mode, int out_mode, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
         // low-resolution 1x1 layers: small GEMMs, both operands through LDS (conv_gemm_tiled_kernel)
-        static const long tiled_max_m = getenv("ISA_GEMM_TILED_MAX_M") ? atol(getenv("ISA_GEMM_TILED_MAX_M")) : 65536;
-        static const int tiled_min_k = getenv("ISA_GEMM_TILED_MIN_K") ? atoi(getenv("ISA_GEMM_TILED_MIN_K")) : 128;
-        if (in_mode == ISA_IN_1X1 && out_mode == ISA_OUT_PLAIN && p.cin == p.kp && p.kp >= tiled_min_k && p.kp % 64 == 0 && p.kp <= 2048 &&
-            p.N >= 64 && p.N % 16 == 0 && p.M <= tiled_max_m)
+        if (in_mode == ISA_IN_1X1 && out_mode == ISA_OUT_PLAIN && p.cin == p.kp && p.kp >= TILED_MIN_K && p.kp % 64 == 0 && p.kp <= 2048 &&
+            p.N >= 64 && p.N % 16 == 0 && p.M <= TILED_MAX_M)
         {
-            static const long wide_min_wgs = getenv("ISA_GEMM_TILED_WIDE_MIN") ? atol(getenv("ISA_GEMM_TILED_WIDE_MIN")) : 512;
             // 128-wide column tiles only when they still give >= 2 workgroups per CU: the second resident workgroup is
             // what keeps the MFMA pipe busy while the first one writes its next tile to LDS and waits at the barrier
-            return (p.N >= 128 && ((p.M + 127) / 128) * ((p.N + 127) / 128) * p.G >= wide_min_wgs) ? launch_tiled<2>(p, has_pro, s)
+            return (p.N >= 128 && ((p.M + 127) / 128) * ((p.N + 127) / 128) * p.G >= TILED_WIDE_MIN) ? launch_tiled<2>(p, has_pro, s)
                                                                                                : launch_tiled<1>(p, has_pro, s);
         }
     }
@@ -817,8 +825,7 @@ int launch0(GemmParams& p, bool has_pro, int in_mode, int out_mode, hipStream_t 
     p.ntiles = (int)((p.M + 127) / 128);
     const int gy = (p.N + n_blk - 1) / n_blk;
     int gx = p.ntiles * p.G;
-    static const int wg_per_cu = getenv("ISA_GEMM_WG_PER_CU") ? atoi(getenv("ISA_GEMM_WG_PER_CU")) : 3;
-    const int cap = max(1, (256 * wg_per_cu) / gy);  // three resident workgroups per CU (measured: 2 -> 36.5 ms, 3 -> 36.3, 4 -> 36.9)
+    const int cap = max(1, (256 * WG_PER_CU) / gy);
     if (gx > cap) gx = cap;
     gx = (int)group_grid(gx, p.G);
     dim3 grid(gx, gy);
@@ -836,6 +843,7 @@ static int conv_gemm_impl(const isa_tensor* x, const isa_pro* pro, const void* w
                           int32_t out_mode, float* stats, int32_t accumulate, const isa_conv_ep* ep, void* stream) {
     if (!tensor_ok(x, 8) || !tensor_ok(y, 1) || !w || x->dtype != y->dtype) return ISA_EINVAL;
     if (kp <= 0 || kp % 32 || kp < x->c) return ISA_EINVAL;
+    if (in_mode != ISA_IN_1X1 && in_mode != ISA_IN_3X3 && in_mode != ISA_IN_GATHER2) return ISA_EINVAL;
     if (y->ld % 8) return ISA_EALIGN;
     GemmParams p{};
     p.x = x->data; p.xh = x->h; p.xw = x->w; p.cin = x->c; p.ldx = x->ld;

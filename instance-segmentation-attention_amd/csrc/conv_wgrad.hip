@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgReduce q) {
     fold_fragments(q, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z);
 }
 
-// depthwise tile slabs [gx][ncb][10*cb] (dwconv_tiled.hip): dw[c][t] += sum_b slab[b][cblk][t*cb+cc]; dbias from row 9
+// depthwise tile slabs [gx][ncb][10*cb] (dwconv.hip): dw[c][t] += sum_b slab[b][cblk][t*cb+cc]; dbias from row 9
 __device__ __forceinline__ void fold_depthwise(const float* ws, int nblk, int ncb, int cbw, int C, int csrc, float* dw,
                                                float* dbias, int cblk, int split, int rsplit) {
     const int per = (nblk + rsplit - 1) / rsplit;
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
 }
 
 template <int TN, int TK>
-int launch_wg_bf16(WgParams& p, int groups_n, hipStream_t s) {
+int launch_wg_bf16(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     const size_t slab = (size_t)32 * (SN + SK) * 4;
     const size_t redb = ((size_t)TN * TK * 16 * 64 + TN * 32) * 4;
@@ -555,6 +555,7 @@ int launch_wg_bf16(WgParams& p, int groups_n, hipStream_t s) {
     if (cap < 1) cap = 1;
     const int gx = (int)group_grid(want < cap ? want : cap, p.G);
     dim3 grid(gx, gy, p.taps);
+    if (int rc = fin_standalone(fin, p.cin, p.G, s)) return rc;        // every check has passed
     if (p.pro.act == ISA_ACT_RELU6) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_RELU6>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_LEAKY && TN == 1 && TK == 1) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_LEAKY>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_NONE) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_NONE>), grid, dim3(256), lds, s, p);
@@ -565,7 +566,7 @@ int launch_wg_bf16(WgParams& p, int groups_n, hipStream_t s) {
 
 
 template <typename T, int TN, int TK>
-int launch_wg(WgParams& p, int groups_n, hipStream_t s) {
+int launch_wg(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
     constexpr int LDN = TN * 32 + 4, LDK = TK * 32 + 4;
     const size_t slab = (size_t)PM * (LDN + LDK) * 4 * 4;
     const size_t redb = ((size_t)TN * TK * 16 * 64 + TN * 32) * 4;
@@ -581,6 +582,7 @@ int launch_wg(WgParams& p, int groups_n, hipStream_t s) {
     if (cap < 1) cap = 1;
     const int gx = (int)group_grid(want < cap ? want : cap, p.G);
     dim3 grid(gx, gy, p.taps);
+    if (int rc = fin_standalone(fin, p.cin, p.G, s)) return rc;        // every check has passed
     if (p.pro.act == ISA_ACT_RELU6) hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ISA_ACT_RELU6>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_NONE) hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ISA_ACT_NONE>), grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ACT_RT>), grid, dim3(256), lds, s, p);
@@ -589,7 +591,7 @@ int launch_wg(WgParams& p, int groups_n, hipStream_t s) {
 }
 
 template <typename T>
-int dispatch_wg(WgParams& p, hipStream_t s) {
+int dispatch_wg(WgParams& p, const isa_pro* fin, hipStream_t s) {
     const int nt = (p.N + 31) / 32, kt = (p.cin + 31) / 32;
     int tn, tk;                         // tiles per wave: up to 4 accumulators (64 VGPRs)
     if (nt == 1) { tn = 1; tk = kt >= 4 ? 4 : (kt >= 2 ? 2 : 1); }
@@ -598,20 +600,20 @@ int dispatch_wg(WgParams& p, hipStream_t s) {
     const int groups_n = (nt + tn - 1) / tn;
     p.groups_k = (kt + tk - 1) / tk;
     if constexpr (sizeof(T) == 2) {
-        if (tn == 1 && tk == 1) return launch_wg_bf16<1, 1>(p, groups_n, s);
-        if (tn == 1 && tk == 2) return launch_wg_bf16<1, 2>(p, groups_n, s);
-        if (tn == 2 && tk == 1) return launch_wg_bf16<2, 1>(p, groups_n, s);
-        if (tn == 2 && tk == 2) return launch_wg_bf16<2, 2>(p, groups_n, s);
-        if (tn == 1 && tk == 4) return launch_wg_bf16<1, 4>(p, groups_n, s);
-        if (tn == 4 && tk == 1) return launch_wg_bf16<4, 1>(p, groups_n, s);
+        if (tn == 1 && tk == 1) return launch_wg_bf16<1, 1>(p, groups_n, fin, s);
+        if (tn == 1 && tk == 2) return launch_wg_bf16<1, 2>(p, groups_n, fin, s);
+        if (tn == 2 && tk == 1) return launch_wg_bf16<2, 1>(p, groups_n, fin, s);
+        if (tn == 2 && tk == 2) return launch_wg_bf16<2, 2>(p, groups_n, fin, s);
+        if (tn == 1 && tk == 4) return launch_wg_bf16<1, 4>(p, groups_n, fin, s);
+        if (tn == 4 && tk == 1) return launch_wg_bf16<4, 1>(p, groups_n, fin, s);
         return ISA_EINVAL;
     }
-    if (tn == 1 && tk == 1) return launch_wg<T, 1, 1>(p, groups_n, s);
-    if (tn == 1 && tk == 2) return launch_wg<T, 1, 2>(p, groups_n, s);
-    if (tn == 2 && tk == 1) return launch_wg<T, 2, 1>(p, groups_n, s);
-    if (tn == 2 && tk == 2) return launch_wg<T, 2, 2>(p, groups_n, s);
-    if (tn == 1 && tk == 4) return launch_wg<T, 1, 4>(p, groups_n, s);
-    if (tn == 4 && tk == 1) return launch_wg<T, 4, 1>(p, groups_n, s);
+    if (tn == 1 && tk == 1) return launch_wg<T, 1, 1>(p, groups_n, fin, s);
+    if (tn == 1 && tk == 2) return launch_wg<T, 1, 2>(p, groups_n, fin, s);
+    if (tn == 2 && tk == 1) return launch_wg<T, 2, 1>(p, groups_n, fin, s);
+    if (tn == 2 && tk == 2) return launch_wg<T, 2, 2>(p, groups_n, fin, s);
+    if (tn == 1 && tk == 4) return launch_wg<T, 1, 4>(p, groups_n, fin, s);
+    if (tn == 4 && tk == 1) return launch_wg<T, 4, 1>(p, groups_n, fin, s);
     return ISA_EINVAL;
 }
 
@@ -621,8 +623,8 @@ extern "C" int isa_conv_wgrad(const isa_tensor* x, const isa_pro* pro, const isa
                               float* dw, float* dbias, int32_t in_mode, int32_t out_mode,
                               const int32_t* kmap, int32_t ksrc, float* ws, int64_t ws_floats,
                               isa_slab_arena* defer, void* stream) {
-    if (pro && pro->fin) { if (int rc = fin_standalone(pro, x->c, tensor_groups(x), as_stream(stream))) return rc; }   // no in-kernel form here
     if (!tensor_ok(x, 8) || !tensor_ok(dy, 8) || !dw || x->dtype != dy->dtype || (!ws && !defer)) return ISA_EINVAL;
+    if (!fin_valid(pro)) return ISA_EINVAL;        // a pending finalize (no in-kernel form here) runs after the last check
     if (in_mode == ISA_IN_GATHER2) return ISA_EINVAL;
     WgParams p{};
     p.x = x->data; p.xh = x->h; p.xw = x->w; p.cin = x->c; p.ldx = x->ld;
@@ -647,97 +649,8 @@ extern "C" int isa_conv_wgrad(const isa_tensor* x, const isa_pro* pro, const isa
     if (in_mode == ISA_IN_3X3 && out_mode == ISA_OUT_PLAIN && x->dtype == ISA_BF16 && pro_trivial(p.pro) && !kmap &&
         x->c <= 32 && dy->c <= 32 && p.ksrc == x->c)
         return conv3x3_wgrad_tiled_launch(x, dy, dw, dbias, ws, ws_floats, defer, as_stream(stream));
-    if (x->dtype == ISA_BF16) return dispatch_wg<bf16_t>(p, as_stream(stream));
-    return dispatch_wg<float>(p, as_stream(stream));
-}
-
-// column sums of an NHWC view: out[c] += sum over pixels (bias gradients of transposed convs, heads)
-namespace {
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* x, long pixels, int c, int ld, float* out) {
-    extern __shared__ float red[];
-    for (int i = threadIdx.x; i < c; i += 256) red[i] = 0.f;
-    __syncthreads();
-    const int lanes_c = c < 256 ? c : 256;
-    const int rows_per_pass = 256 / lanes_c;
-    const int ch = threadIdx.x % lanes_c, rsub = threadIdx.x / lanes_c;
-    if (rsub < rows_per_pass) {
-        for (int cc = ch; cc < c; cc += lanes_c) {
-            float s = 0.f;
-            for (long pix = (long)blockIdx.x * rows_per_pass + rsub; pix < pixels; pix += (long)gridDim.x * rows_per_pass)
-                s += st<T>::ld(x + pix * ld + cc);
-            atomicAdd(&red[cc], s);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < c; i += 256)
-        if (red[i] != 0.f) atomicAdd(out + i, red[i]);
-}
-// 16-byte loads: a lane owns one 8-channel group of a pixel (item = pixel * cg + group; grid_keep_cg keeps the group
-// fixed per lane), the lanes of a wave that share a group fold by shuffles, lanes < cg add into the LDS row.  The
-// element-wise walk above moved 2 bytes per lane per load (71 us for a 67 MB tensor).
-template <typename T>
-__global__ __launch_bounds__(256) void colsum8_kernel(const T* x, long pixels, int c, int ld, float* out) {
-    extern __shared__ float red[];
-    const int cg = (c + 7) / 8;
-    for (int i = threadIdx.x; i < c; i += 256) red[i] = 0.f;
-    __syncthreads();
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int last = -1;
-    for (long item = (long)blockIdx.x * 256 + threadIdx.x; item < pixels * cg; item += (long)gridDim.x * 256) {
-        const int c0 = (int)(item % cg) * 8; const long pix = item / cg;
-        if (c0 != last && last >= 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { if (last + j < c) atomicAdd(&red[last + j], s[j]); s[j] = 0.f; }
-        }
-        last = c0;
-        float v[8];
-        load8g<T>(x + pix * ld + c0, v, min(8, c - c0));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (c0 + j < c) s[j] += v[j];
-    }
-    const int lane = threadIdx.x & 63;
-    const bool fixed = ((long)gridDim.x * 256) % cg == 0 && cg < 64;
-    const int cfix = (int)(((long)blockIdx.x * 256 + threadIdx.x) % cg) * 8;
-    if (fixed) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] = fold_stride(s[j], cg, lane);
-        if (lane < cg) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) if (cfix + j < c) atomicAdd(&red[cfix + j], s[j]);
-        }
-    } else if (last >= 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (last + j < c) atomicAdd(&red[last + j], s[j]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < c; i += 256)
-        if (red[i] != 0.f) atomicAdd(out + i, red[i]);
-}
-}  // namespace
-
-extern "C" int isa_colsum(const isa_tensor* x, float* out, void* stream) {
-    if (!tensor_ok(x, 1) || !out) return ISA_EINVAL;
-    const long pixels = (long)x->n * x->h * x->w;
-    if (tensor_ok(x, 8)) {
-        const int cg = (x->c + 7) / 8;
-        const int grid = grid_keep_cg(grid_cap(cdiv(pixels * cg, 256), 1024), cg);
-        if (x->dtype == ISA_BF16)
-            hipLaunchKernelGGL(colsum8_kernel<bf16_t>, dim3(grid), dim3(256), x->c * 4, as_stream(stream),
-                               (const bf16_t*)x->data, pixels, x->c, x->ld, out);
-        else
-            hipLaunchKernelGGL(colsum8_kernel<float>, dim3(grid), dim3(256), x->c * 4, as_stream(stream),
-                               (const float*)x->data, pixels, x->c, x->ld, out);
-        return launch_status();
-    }
-    const int grid = grid_cap(cdiv(pixels, 64), 512);
-    if (x->dtype == ISA_BF16)
-        hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3(grid), dim3(256), x->c * 4, as_stream(stream),
-                           (const bf16_t*)x->data, pixels, x->c, x->ld, out);
-    else
-        hipLaunchKernelGGL(colsum_kernel<float>, dim3(grid), dim3(256), x->c * 4, as_stream(stream),
-                           (const float*)x->data, pixels, x->c, x->ld, out);
-    return launch_status();
+    if (x->dtype == ISA_BF16) return dispatch_wg<bf16_t>(p, pro, as_stream(stream));
+    return dispatch_wg<float>(p, pro, as_stream(stream));
 }
 
 // second-stage reduction for other translation units that write conv_wgrad-format slabs (conv_fused_bwd.hip,

@@ -11,7 +11,7 @@
 //   * per 32-channel block: the (8+2) x (32+2) halo is staged in LDS in its storage type (16-byte global loads land
 //     unconverted; the NEXT block's or tile's loads are already in registers while the current one is computed; an fp32
 //     halo cost 49 KB and left one workgroup per CU: 92 -> 85 us for the 64 -> 32 block at 256x256 x 16), the stencil runs
-//     as in dwconv_tiled.hip (lane = 8 channels x 4 consecutive x, 18 LDS row vectors feed 36 packed FMAs), BN1 + ReLU6 are
+//     as in dwconv.hip (lane = 8 channels x 4 consecutive x, 18 LDS row vectors feed 36 packed FMAs), BN1 + ReLU6 are
 //     applied to the
 //     accumulators and the 256 x 32 result goes to the A tile in LDS as bf16, rows padded by 16 B;
 //   * after the last channel block: A[256 px][C] x W[C'][C] on v_mfma_f32_32x32x16_bf16 (a wave owns two 32-pixel rows

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void axpy8_kernel(AxpyParams p) {
 }
 
 // 2x2 mean pooling and its backward
-struct PoolParams { View x, y; int accumulate; int f; int is_max; };
+struct PoolParams { View x, y; int accumulate; };
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void avgpool2_kernel(PoolParams p) {
     // fwd: x big -> y small.  bwd: (x = dy small) -> (y = dx big), dx (+)= dy/4
@@ -367,26 +367,6 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(PoolParams p) {
                 store8<T>(dp, o);
             }
         }
-    }
-}
-
-// f x f pooling (stride f) of narrow maps; scalar per element
-template <typename T>
-__global__ __launch_bounds__(256) void pool_f_kernel(PoolParams p) {
-    const long items = (long)p.y.n * p.y.h * p.y.w * p.y.c;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % p.y.c); long q = i / p.y.c;
-        const int xo = (int)(q % p.y.w); q /= p.y.w;
-        const int yo = (int)(q % p.y.h); const int b = (int)(q / p.y.h);
-        float acc = p.is_max ? -INFINITY : 0.f;
-        for (int dy = 0; dy < p.f; ++dy)
-            for (int dx = 0; dx < p.f; ++dx) {
-                const float v = st<T>::ld(reinterpret_cast<const T*>(p.x.data) +
-                    (((long)b * p.x.h + yo * p.f + dy) * p.x.w + xo * p.f + dx) * p.x.ld + c);
-                acc = p.is_max ? fmaxf(acc, v) : acc + v;
-            }
-        if (!p.is_max) acc /= (float)(p.f * p.f);
-        st<T>::stv(reinterpret_cast<T*>(p.y.data) + (((long)b * p.y.h + yo) * p.y.w + xo) * p.y.ld + c, acc);
     }
 }
 
@@ -738,13 +718,13 @@ extern "C" int isa_affine_act_res(const isa_tensor* x, const isa_pro* pro, const
     if (res) p.res = mkview(res);
     if (res2) p.res2 = mkview(res2);
     p.groups = G; p.bcast = bcast;
+    p.pixels = (long)(out->n / G) * x->h * x->w; p.cg = (x->c + 7) / 8;       // per group
+    if (p.pixels * G >= (1L << 32)) return ISA_EINVAL;
     if (pro && pro->fin) {
         if (!fin_valid(pro) || (!bcast && tensor_groups(x) != G)) return ISA_EINVAL;
         if (x->c <= ISA_FIN_MAX_C) p.fin = make_fin(pro);
         else if (int rc = fin_standalone(pro, x->c, tensor_groups(x), as_stream(stream))) return rc;
     }
-    p.pixels = (long)(out->n / G) * x->h * x->w; p.cg = (x->c + 7) / 8;       // per group
-    if (p.pixels * G >= (1L << 32)) return ISA_EINVAL;
     const Walk wk = mkwalk(x->c, p.pixels);
     const dim3 grid(walk_grid(wk), 1, G);
     if (p.pro.act == ISA_ACT_NONE)
@@ -778,7 +758,7 @@ extern "C" int isa_axpy(const isa_tensor* src, const isa_tensor* dst, float alph
 extern "C" int isa_avgpool2(const isa_tensor* x, const isa_tensor* y, void* stream) {
     if (!tensor_ok(x, 8) || !tensor_ok(y, 8) || x->dtype != y->dtype || x->c != y->c || x->c % 8 ||
         x->n != y->n || x->h != 2 * y->h || x->w != 2 * y->w) return ISA_EINVAL;
-    PoolParams p{mkview(x), mkview(y), 0, 2, 0};
+    PoolParams p{mkview(x), mkview(y), 0};
     const int grid = grid_cap(cdiv((long)y->n * y->h * y->w * (y->c / 8), 256));
     DISPATCH_T(x->dtype,
         hipLaunchKernelGGL((avgpool2_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, as_stream(stream), p),
@@ -790,23 +770,11 @@ extern "C" int isa_avgpool2_bwd(const isa_tensor* dy, const isa_tensor* dx, int3
                                 void* stream) {
     if (!tensor_ok(dy, 8) || !tensor_ok(dx, 8) || dy->dtype != dx->dtype || dy->c != dx->c ||
         dy->c % 8 || dy->n != dx->n || dx->h != 2 * dy->h || dx->w != 2 * dy->w) return ISA_EINVAL;
-    PoolParams p{mkview(dy), mkview(dx), accumulate, 2, 0};
+    PoolParams p{mkview(dy), mkview(dx), accumulate};
     const int grid = grid_cap(cdiv((long)dy->n * dy->h * dy->w * (dy->c / 8), 256));
     DISPATCH_T(dy->dtype,
         hipLaunchKernelGGL((avgpool2_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, as_stream(stream), p),
         hipLaunchKernelGGL((avgpool2_kernel<float, true>), dim3(grid), dim3(256), 0, as_stream(stream), p));
-    return launch_status();
-}
-
-extern "C" int isa_pool_f(const isa_tensor* x, const isa_tensor* y, int32_t f, int32_t is_max,
-                          void* stream) {
-    if (!tensor_ok(x, 1) || !tensor_ok(y, 1) || x->dtype != y->dtype || x->c != y->c || f < 1 ||
-        x->n != y->n || x->h != f * y->h || x->w != f * y->w) return ISA_EINVAL;
-    PoolParams p{mkview(x), mkview(y), 0, f, is_max};
-    const int grid = grid_cap(cdiv((long)y->n * y->h * y->w * y->c, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(pool_f_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p),
-        hipLaunchKernelGGL(pool_f_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p));
     return launch_status();
 }
 

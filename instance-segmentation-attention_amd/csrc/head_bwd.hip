@@ -379,36 +379,10 @@ __global__ __launch_bounds__(256) void sp_bwd_dbeta_kernel(SpBwd p) {
         if (threadIdx.x == 0 && tb != 0.f) atomicAdd(p.sdot + cur_row, tb);
     }
 }
-// pass 3 (one workgroup per image): softmax + tanh backward on the maps.
-// rowstat[b] = {max, sumexp, cnt, ht}; outputs ddot map, dht[b], atomics into d fcw / d fcb
-__global__ __launch_bounds__(1024) void sp_bwd_row_kernel(const float* beta, const float* dbeta, const float* dot, const float* m,
-                                                          const float* rowstat, const float* fcw, long L, float* ddot, float* dht,
-                                                          float* dfcw, float* dfcb) {
-    __shared__ float sh[16];
-    const int b = blockIdx.x;
-    const float cnt = rowstat[4 * b + 2], ht = rowstat[4 * b + 3], fw = fcw[0];
-    const float* be = beta + (long)b * L; const float* db = dbeta + (long)b * L;
-    float s = 0.f;
-    for (long p = threadIdx.x; p < L; p += 1024) s += be[p] * db[p];
-    const float S = cnt > 0.f ? block_sum(s, sh) / cnt : 0.f;
-    float a_w = 0.f, a_b = 0.f, a_h = 0.f;
-    for (long p = threadIdx.x; p < L; p += 1024) {
-        float du = 0.f;
-        if (m[(long)b * L + p] >= 0.5f) {
-            const float dz = be[p] * (db[p] - S);
-            const float t = tanhf(dot[(long)b * L + p] + ht);
-            a_w += dz * t; a_b += dz;
-            du = dz * fw * (1.f - t * t);
-            a_h += du;
-        }
-        ddot[(long)b * L + p] = du;
-    }
-    a_w = block_sum(a_w, sh); a_b = block_sum(a_b, sh); a_h = block_sum(a_h, sh);
-    if (threadIdx.x == 0) { atomicAdd(dfcw, a_w); atomicAdd(dfcb, a_b); dht[b] = a_h; }
-}
-// pass 3 with many workgroups per row: the row's sum of beta * dbeta comes from pass 2 (sdot), so every chunk of 4096 pixels is
-// independent; the three row sums leave as one atomic per workgroup (dht is part of the zeroed scratch).  The one-workgroup
-// kernel above kept n = 16 CUs busy for 76 us.
+// pass 3: softmax + tanh backward on the maps, rowstat[b] = {max, sumexp, cnt, ht}; outputs the ddot map, dht[b] and atomics
+// into d fcw / d fcb.  Many workgroups per row: the row's sum of beta * dbeta comes from pass 2 (sdot), so every chunk of 4096
+// pixels is independent; the three row sums leave as one atomic per workgroup (dht is part of the zeroed scratch).  One
+// workgroup per image kept only n = 16 CUs busy for 76 us.
 constexpr int SPB_CHUNK = 4096;
 __global__ __launch_bounds__(256) void sp_bwd_rowc_kernel(const float* beta, const float* dbeta, const float* dot, const float* m,
                                                           const float* rowstat, const float* fcw, const float* sdot, long L,

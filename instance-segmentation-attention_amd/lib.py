@@ -69,7 +69,6 @@ SIGNATURES = {
     "isa_conv_gemm_ep": [P_T, P_PRO, VP, I32, VP, P_T, I32, VP, VP],
     "isa_dwpw_eval": [P_T, VP, VP, VP, VP, I32, VP, P_T, VP],
     "isa_conv_wgrad": [P_T, P_PRO, P_T, VP, VP, I32, I32, VP, I32, VP, I64, VP, VP],
-    "isa_colsum": [P_T, VP, VP],
     "isa_dwconv3x3": [P_T, P_PRO, VP, VP, P_T, VP, VP],
     "isa_dwconv3x3_dgrad": [P_T, VP, P_T, I32, VP],
     "isa_dwconv3x3_wgrad": [P_T, P_PRO, P_T, VP, VP, I32, VP, I64, VP, VP],
@@ -96,7 +95,6 @@ SIGNATURES = {
     "isa_axpy": [P_T, P_T, F, I32, VP],
     "isa_avgpool2": [P_T, P_T, VP],
     "isa_avgpool2_bwd": [P_T, P_T, I32, VP],
-    "isa_pool_f": [P_T, P_T, I32, I32, VP],
     "isa_avgpool3": [P_T, P_T, P_T, I32, VP],
     "isa_chan_mean": [P_T, P_PRO, VP, VP],
     "isa_se_fc": [VP, VP, VP, VP, VP, I32, I32, I32, VP, VP, VP],

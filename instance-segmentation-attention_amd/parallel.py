@@ -104,10 +104,3 @@ def shard_batch(global_batch: int, rank: int, world: int):
 def rank_seed(seed: int, rank: int) -> int:
     """Distinct, reproducible data / shuffling seed per rank (rank 0 keeps the single-process seed)."""
     return int(seed) + 1000003 * int(rank)
-
-
-def clip_coef(sum_sq: float, max_norm: float) -> float:
-    """torch.nn.utils.clip_grad_norm_ coefficient (host-side mirror of the device formula)."""
-    if max_norm <= 0:
-        return 1.0
-    return min(1.0, max_norm / (sum_sq ** 0.5 + 1e-6))

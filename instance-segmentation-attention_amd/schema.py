@@ -76,7 +76,3 @@ def state_dict_schema(use_instance_seg=True):
         S.extend([(p2 + ".3.weight", (48, 1, 3, 3)), (p2 + ".3.bias", (48,))]); bn(p2 + ".4", 48)
         S.extend([(p2 + ".6.weight", (24, 48, 1, 1)), (p2 + ".6.bias", (24,))]); bn(p2 + ".7", 24)
     return S
-
-
-def is_bn_prefix(schema_names, prefix):
-    return (prefix + ".running_mean") in schema_names

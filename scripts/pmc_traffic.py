@@ -9,7 +9,7 @@ import csv, glob, json, re, sys
 
 FAMILIES = [("conv_gemm_kernel", "isa_conv_gemm"), ("conv_gemm_tiled_kernel", "isa_conv_gemm"), ("conv3x3_tiled_kernel", "isa_conv_gemm"), ("conv_wgrad", "isa_conv_wgrad"), ("wgrad_reduce", "isa_conv_wgrad(reduce)"), ("wgrad_fold", "isa_wgrad_defer_flush"),
             ("pw_bn_bwd_kernel", "isa_conv1x1_bn_backward"), ("dw_bn_bwd_kernel", "isa_dwconv3x3_bn_backward"),
-            ("dw2_fwd_kernel", "isa_dwconv3x3"), ("dw_fwd_kernel", "isa_dwconv3x3"), ("bn_bwd_kernel", "isa_bn_bwd"),
+            ("dw2_fwd_kernel", "isa_dwconv3x3"), ("bn_bwd_kernel", "isa_bn_bwd"),
             ("materialize_kernel", "isa_affine_act_res"), ("axpy", "isa_axpy")]
 
 

@@ -1,4 +1,4 @@
-// Store pattern of the depthwise kernels (dwconv_tiled.hip): a workgroup owns an 8 x 32-pixel tile x 32 channels; lane =
+// Store pattern of the depthwise kernels (dwconv.hip): a workgroup owns an 8 x 32-pixel tile x 32 channels; lane =
 // (cg = tid & 3: 8 channels, g = tid >> 2: tile row g >> 3, four consecutive x at (g & 7) * 4) and stores its four pixels with
 // four 16-byte stores.  With C = 64 channels a pixel row is one 128-byte line and the two channel blocks (blockIdx.y) write
 // its two halves from different workgroups.  Variants (write-only and read + write, 1 GiB tensors):

@@ -6,11 +6,11 @@ import csv, glob, re, sys
 FAMILIES = [("conv_gemm_kernel", "isa_conv_gemm"), ("conv_gemm_tiled_kernel", "isa_conv_gemm"), ("conv3x3_tiled_kernel", "isa_conv_gemm"),
             ("conv3x3_wgrad", "isa_conv_wgrad"), ("conv_wgrad", "isa_conv_wgrad"), ("wgrad_reduce", "isa_conv_wgrad (immediate fold)"),
             ("wgrad_fold", "isa_slab_arena_flush"), ("pw_bn_bwd_kernel", "isa_conv1x1_bn_backward"),
-            ("dw_bn_bwd_kernel", "isa_dwconv3x3_bn_backward"), ("dw2_fwd_kernel", "isa_dwconv3x3"), ("dw_fwd_kernel", "isa_dwconv3x3"),
-            ("dw2_wgrad", "isa_dwconv3x3_dgrad/_wgrad"), ("dw_wgrad", "isa_dwconv3x3_dgrad/_wgrad"), ("dwpw_eval", "isa_dwpw_eval"),
+            ("dw_bn_bwd_kernel", "isa_dwconv3x3_bn_backward"), ("dw2_fwd_kernel", "isa_dwconv3x3"),
+            ("dw2_wgrad", "isa_dwconv3x3_dgrad/_wgrad"), ("dwpw_eval", "isa_dwpw_eval"),
             ("bn_bwd_kernel", "isa_bn_bwd_reduce/apply"), ("materialize_kernel", "isa_affine_act_res"), ("bn_finalize", "isa_bn_finalize"),
             ("bn_running_update", "isa_bn_running_update"), ("axpy", "isa_axpy"), ("pack_kernel", "isa_pack (param packer)"),
-            ("adadelta", "isa_adadelta"), ("scale_bc", "isa_scale_bc"), ("colsum", "isa_colsum")]
+            ("adadelta", "isa_adadelta"), ("scale_bc", "isa_scale_bc")]
 path = sys.argv[1]
 steps = float(sys.argv[2]) if len(sys.argv) > 2 else 0
 f = glob.glob(path + "/**/*kernel_stats.csv", recursive=True)[0]

@@ -69,7 +69,7 @@ from test_gpu_ops import _gpu, q, rand, rel, to_act  # noqa: E402
 BF = torch.bfloat16
 F32 = torch.float32
 STAT_R = 8
-CB = 32                 # channel block of the depthwise kernels (dwconv_tiled.hip)
+CB = 32                 # channel block of the depthwise kernels (dwconv.hip)
 
 FP32_BOUND = 1e-5
 BF16_STORE = 2.0 ** -8
@@ -220,7 +220,7 @@ GEMM_CASES = [
     ("persist-pro", BF, 2, 250, 262, 128, 512, 1, "relu6", True, True),
     # fp32, M = 196608 -> 1536 tiles, N = 256 -> gy = 2, gx = 384: 4 tiles per workgroup, LEAKY prologue (PRO = 2)
     ("persist-f32", F32, 3, 256, 256, 32, 256, 1, "leaky", False, True),
-    # launch_tiled<2>: bf16, M = 65536 <= ISA_GEMM_TILED_MAX_M, K = 128, N = 128: (65536/128) * (128/128) = 512 >= 512
+    # launch_tiled<2>: bf16, M = 65536 <= TILED_MAX_M (conv_gemm.hip), K = 128, N = 128: (65536/128) * (128/128) = 512 >= 512
     # workgroups -> WN = 2 (one tile each: this kernel is not persistent)
     ("tiled2", BF, 1, 256, 256, 128, 128, 1, "relu6", False, True),
     # conv3x3_tiled.hip: bf16 3x3, cin = 16 (kp 32), N = 16, no prologue / stats: 8x32 tiles, tiles_x = 9 (262 % 32 = 6),
@@ -420,7 +420,7 @@ def test_conv_wgrad_forms(case):
 # ------------------------------------------------------------------------------------------------ 3. depthwise forward
 DW_FWD = [
     # name, dtype, n, h, w, c, G
-    # launch_fwd2 (dwconv_tiled.hip): bf16 gx = 256 / ncb, fp32 gx = 768 / ncb, then group_grid.  Only the bf16
+    # launch_fwd2 (dwconv.hip): bf16 gx = 256 / ncb, fp32 gx = 768 / ncb, then group_grid.  Only the bf16
     # (double-buffered, DB) instantiation walks tile_range's XCD order, when (workgroups per group) % 8 == 0 and tiles
     # per group >= 64: XCD x = bx % 8 owns tiles [x * chunk, min(ntiles, (x + 1) * chunk)), chunk = ceil(ntiles / 8),
     # and its nbx / 8 workgroups stride through that range.  The fp32 form always strides over all tiles from bx.

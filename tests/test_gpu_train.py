@@ -168,7 +168,7 @@ def test_gradients_with_dropout_vs_reference_f64(size):
 
 
 def test_gradients_256_vs_reference_f64():
-    """The same per-tensor check at the production size: 256x256 runs the tiled / persistent kernels (dwconv_tiled,
+    """The same per-tensor check at the production size: 256x256 runs the tiled / persistent kernels (dwconv,
     conv3x3_tiled, the fused backward kernels, deferred folds with hundreds of slabs) at their real tile counts."""
     ReSeg, Trainer = need_gpu()
     z = np.load(os.path.join(ROOT, "tests", "golden", "train_256_f64.npz"))
