@@ -372,6 +372,28 @@ int isa_head_loss(const float* sums /*[5][B][8]*/, const float* alpha, const int
 int isa_sem_loss(const float* sums /*[B][8]*/, int32_t B, float* coef, float* scal, void* stream);
 int isa_mask_loss_grad(const isa_tensor* pred, const float* target, const int64_t* onehot, const float* coef /*[B][4]*/,
                        const isa_tensor* dpred, int32_t accumulate, void* stream);
+/* ---- K-class semantic criterion (Model.__define_criterion + the CE / Dice branches of __minibatch, model.py:102-133,
+ * 255-269; dice.py:10-85; torch.nn.CrossEntropyLoss(weight)), 2 <= K <= ISA_SEM_MAX_CLASSES.  Serves every
+ * (criterion, class_weights, optimize_bg, n_classes) but the shipped 2-class fg-only unweighted Multi, which keeps
+ * isa_mask_loss_sums + isa_sem_loss + isa_mask_loss_grad.  logits NHWC [B,H,W,K] (bf16 | fp32, ld a multiple of 8),
+ * labels uint8 [B,H,W] with values < K (a precondition, not checked: the reference raises IndexError there).
+ * cfg (device, read at run time so that a captured hipGraph follows in-place changes) [4 + K] floats:
+ *   {use_ce, use_dice, optimize_bg, 0, w_0 .. w_{K-1}}; no class weights = all ones.
+ * isa_sem_loss_k_sums: sums [B*3K + 2], zeroed by the caller: per image {sum p*g [K], sum p [K], sum g [K]}, then the
+ *   batch's {sum w_y * nll, sum w_y}.
+ * isa_sem_loss_k_assemble: one workgroup; coef [3*B*K + 1] for the gradient, scal[2] = {CE, Dice} (0 for a term the
+ *   criterion does not compute).
+ * isa_sem_loss_k_grad: d logits (written, or added to when accumulate != 0); channels >= K of a row untouched. */
+#define ISA_SEM_MAX_CLASSES 32
+int isa_sem_loss_k_sums(const isa_tensor* logits, const uint8_t* labels, const float* cfg, float* sums, void* stream);
+int isa_sem_loss_k_assemble(const float* sums, const float* cfg, int32_t B, int32_t K, float* coef, float* scal,
+                            void* stream);
+int isa_sem_loss_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
+                        const isa_tensor* dlogits, int32_t accumulate, void* stream);
+/* reference-format targets: int64 one-hot [n,k,h,w] -> uint8 labels [n,h,w] and / or the fp32 argmax(1) map [n, h*w]
+ * (sem_seg_argmax, reseg.py:118); the first maximum wins, as in torch.argmax.  Either output may be NULL, not both. */
+int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t hw, uint8_t* labels, float* argmax_map,
+                           void* stream);
 int isa_ins_softmax_bwd(const float* alpha, const int64_t* ins, const int32_t* idx, const int32_t* s_t,
                         const float* adv, int32_t n, int32_t nobj, int64_t L, float* dmerge /*[nsrc, L]*/, int32_t nsrc,
                         void* stream);
@@ -453,6 +475,11 @@ int isa_image_ex(const uint8_t* rgb, const isa_tensor* out, void* stream);
  * channel c = (sem == c) as np.eye(2)[sem] (:356-361; a value > 1 is an IndexError there and all-zero here).  k <= 252. */
 int isa_collate_targets(const uint8_t* ins, const uint8_t* sem, int32_t n, int32_t h, int32_t w, int32_t k,
                         int64_t* ins_out, int64_t* sem_out, void* stream);
+/* isa_collate_targets with a K-class semantic one-hot: sem_out int64 [n,n_classes,h,w] = np.eye(n_classes)[sem]
+ * (dataset.py:365-369), 2 <= n_classes <= ISA_SEM_MAX_CLASSES; labels_out (may be NULL) uint8 [n,h,w], a copy of sem for
+ * the K-class criterion.  sem_out may be NULL when labels_out is given. */
+int isa_collate_targets_k(const uint8_t* ins, const uint8_t* sem, int32_t n, int32_t h, int32_t w, int32_t k,
+                          int32_t n_classes, int64_t* ins_out, int64_t* sem_out, uint8_t* labels_out, void* stream);
 
 /* ---- exact augmentations: the index-permuting part of AlignCollate.__preprocess,
  * code/lib/dataset.py:185-233 - horizontal flip, vertical flip, transpose, rotation by k*90 degrees (preprocess.py:171,

@@ -13,6 +13,21 @@ namespace {
 
 constexpr int TP = 256;          // pixels per tile
 
+// the [np][K] byte tile of instance planes at src -> LDS rows of `stride` bytes (between two __syncthreads)
+__device__ __forceinline__ void load_tile(const uint8_t* src, int np, int K, int stride, uint8_t* tile) {
+    const long bytes = (long)np * K;
+    if ((K & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+        for (long i = threadIdx.x * 16L; i < bytes; i += 256 * 16L) {
+            const uint4 v = *reinterpret_cast<const uint4*>(src + i);
+            const int p = (int)(i / K), k = (int)(i % K);
+            uint32_t* d = reinterpret_cast<uint32_t*>(tile + p * stride + k);   // stride and k are multiples of 4
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        }
+    } else {
+        for (long i = threadIdx.x; i < bytes; i += 256) tile[(i / K) * stride + (i % K)] = src[i];
+    }
+}
+
 __global__ __launch_bounds__(256) void collate_targets_kernel(const uint8_t* ins, const uint8_t* sem, int n, long hw, int K,
                                                               int64_t* ins_out, int64_t* sem_out) {
     extern __shared__ uint8_t tile[];                 // [TP][K + 4]
@@ -21,19 +36,8 @@ __global__ __launch_bounds__(256) void collate_targets_kernel(const uint8_t* ins
     for (long t = blockIdx.x; t < (long)n * tiles_per_img; t += gridDim.x) {
         const long b = t / tiles_per_img, p0 = (t % tiles_per_img) * TP;
         const int np = (int)min((long)TP, hw - p0);
-        const uint8_t* src = ins + (b * hw + p0) * K;
-        const long bytes = (long)np * K;
         __syncthreads();                               // the previous tile has been consumed
-        if ((K & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-            for (long i = threadIdx.x * 16L; i < bytes; i += 256 * 16L) {
-                const uint4 v = *reinterpret_cast<const uint4*>(src + i);
-                const int p = (int)(i / K), k = (int)(i % K);
-                uint32_t* d = reinterpret_cast<uint32_t*>(tile + p * stride + k);   // stride and k are multiples of 4
-                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-            }
-        } else {
-            for (long i = threadIdx.x; i < bytes; i += 256) tile[(i / K) * stride + (i % K)] = src[i];
-        }
+        load_tile(ins + (b * hw + p0) * K, np, K, stride, tile);
         __syncthreads();
         const int p = threadIdx.x;
         if (p < np) {
@@ -43,6 +47,32 @@ __global__ __launch_bounds__(256) void collate_targets_kernel(const uint8_t* ins
                 const uint8_t v = sem[b * hw + p0 + p];
                 sem_out[(b * 2) * hw + p0 + p] = v == 0;          // np.eye(2)[v]: channel c = (v == c)
                 sem_out[(b * 2 + 1) * hw + p0 + p] = v == 1;
+            }
+        }
+    }
+}
+
+// the same with a C-class semantic one-hot (np.eye(C)[v]) and, optionally, the uint8 label map itself
+__global__ __launch_bounds__(256) void collate_targets_k_kernel(const uint8_t* ins, const uint8_t* sem, int n, long hw, int K,
+                                                                int C, int64_t* ins_out, int64_t* sem_out, uint8_t* labels) {
+    extern __shared__ uint8_t tile[];                 // [TP][K + 4]
+    const int stride = K + 4;
+    const long tiles_per_img = (hw + TP - 1) / TP;
+    for (long t = blockIdx.x; t < (long)n * tiles_per_img; t += gridDim.x) {
+        const long b = t / tiles_per_img, p0 = (t % tiles_per_img) * TP;
+        const int np = (int)min((long)TP, hw - p0);
+        __syncthreads();
+        load_tile(ins + (b * hw + p0) * K, np, K, stride, tile);
+        __syncthreads();
+        const int p = threadIdx.x;
+        if (p < np) {
+            int64_t* dst = ins_out + (b * K) * hw + p0 + p;
+            for (int k = 0; k < K; ++k) dst[(long)k * hw] = (int64_t)tile[p * stride + k];
+            if (sem) {
+                const uint8_t v = sem[b * hw + p0 + p];
+                if (sem_out)
+                    for (int c = 0; c < C; ++c) sem_out[(b * C + c) * hw + p0 + p] = v == c;
+                if (labels) labels[b * hw + p0 + p] = v;
             }
         }
     }
@@ -58,5 +88,18 @@ extern "C" int isa_collate_targets(const uint8_t* ins, const uint8_t* sem, int32
     const int grid = grid_cap(tiles, 256 * 8);
     hipLaunchKernelGGL(collate_targets_kernel, dim3(grid), dim3(256), (size_t)TP * (k + 4), as_stream(stream),
                        ins, sem, n, hw, k, ins_out, sem_out);
+    return launch_status();
+}
+
+extern "C" int isa_collate_targets_k(const uint8_t* ins, const uint8_t* sem, int32_t n, int32_t h, int32_t w, int32_t k,
+                                     int32_t n_classes, int64_t* ins_out, int64_t* sem_out, uint8_t* labels_out,
+                                     void* stream) {
+    if (!ins || !ins_out || n <= 0 || h <= 0 || w <= 0 || k <= 0 || k > 252) return ISA_EINVAL;
+    if (n_classes < 2 || n_classes > ISA_SEM_MAX_CLASSES || (sem && !sem_out && !labels_out)) return ISA_EINVAL;
+    const long hw = (long)h * w;
+    const long tiles = (long)n * ((hw + TP - 1) / TP);
+    const int grid = grid_cap(tiles, 256 * 8);
+    hipLaunchKernelGGL(collate_targets_k_kernel, dim3(grid), dim3(256), (size_t)TP * (k + 4), as_stream(stream),
+                       ins, sem, n, hw, k, n_classes, ins_out, sem_out, labels_out);
     return launch_status();
 }

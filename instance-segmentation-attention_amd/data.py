@@ -40,12 +40,15 @@ def synth_batch(batch, height, width, seed=0, max_objects=32, kmin=3, kmax=8):
 class SyntheticLoader(object):
     """Iterable of `n_batches` collated minibatches, re-seeded per epoch like a shuffling DataLoader."""
 
-    def __init__(self, n_batches, batch_size, height=256, width=256, seed=0, compact=False):
+    def __init__(self, n_batches, batch_size, height=256, width=256, seed=0, compact=False, n_classes=2):
         """compact=True yields the targets as the reference's collate function holds them before its last five lines
         (dataset.py:349-379): sem uint8 [B,H,W], ins uint8 [B,H,W,32]; the model expands them on the device
-        (isa_collate_targets) - 8x less host-to-device traffic per step."""
+        (isa_collate_targets) - 8x less host-to-device traffic per step.
+        n_classes > 2: semantic labels in [0, n_classes): background 0, instance j of an image class 1 + j % (K - 1)
+        (no extra random draws: the stream, and the output at n_classes = 2, are those of the 2-class loader)."""
         self.n, self.bs, self.h, self.w, self.seed, self.epoch = n_batches, batch_size, height, width, seed, 0
         self.compact = compact
+        self.n_classes = n_classes
 
     def __len__(self):
         return self.n
@@ -54,9 +57,20 @@ class SyntheticLoader(object):
         self.epoch += 1
         for i in range(self.n):
             x, sem, ins, n = synth_batch(self.bs, self.h, self.w, seed=self.seed + 1000 * self.epoch + i)
+            if self.n_classes > 2:
+                sem = class_onehot(ins, self.n_classes)
             if self.compact:
-                sem, ins = sem[:, 1].contiguous().to(torch.uint8), ins.permute(0, 2, 3, 1).contiguous().to(torch.uint8)
+                sem = sem.argmax(1).to(torch.uint8) if self.n_classes > 2 else sem[:, 1].contiguous().to(torch.uint8)
+                ins = ins.permute(0, 2, 3, 1).contiguous().to(torch.uint8)
             yield x, sem, ins, n
+
+
+def class_onehot(ins, n_classes):
+    """Synthetic K-class targets from instance planes [B,M,H,W]: one-hot int64 [B,K,H,W] of the label map that puts
+    instance j in class 1 + j % (K - 1) and the background in class 0."""
+    fg = ins.sum(1) > 0
+    lab = torch.where(fg, 1 + ins.argmax(1) % (n_classes - 1), torch.zeros_like(fg, dtype=torch.int64))
+    return torch.nn.functional.one_hot(lab, n_classes).permute(0, 3, 1, 2).contiguous()
 
 
 def d4_swaps(op):

@@ -88,6 +88,7 @@ SIGNATURES = {
     "isa_resize_nearest_u8": [VP, I32, I32, I32, I32, VP, I32, I32, VP],
     "isa_resize_bilinear_u8": [VP, I32, I32, I32, I32, VP, I32, I32, VP, I64, VP],
     "isa_collate_targets": [VP, VP, I32, I32, I32, I32, VP, VP, VP],
+    "isa_collate_targets_k": [VP, VP, I32, I32, I32, I32, I32, VP, VP, VP, VP],
     "isa_bn_finalize": [VP, F, VP, VP, VP, VP, F, F, VP, VP, VP, VP, I32, I32, I32, VP],
     "isa_bn_bwd_reduce": [P_T, P_T, VP, VP, VP, VP, I32, VP, VP, VP],
     "isa_bn_bwd_apply": [P_T, P_T, VP, VP, VP, VP, I32, VP, VP, VP, F, I32, P_T, VP, VP, VP],
@@ -118,6 +119,10 @@ SIGNATURES = {
     "isa_head_loss": [VP, VP, VP, I64, I32, VP, F, F, F, F, VP, I32, VP, VP, VP, I32, VP],
     "isa_sem_loss": [VP, I32, VP, VP, VP],
     "isa_mask_loss_grad": [P_T, VP, VP, VP, P_T, I32, VP],
+    "isa_sem_loss_k_sums": [P_T, VP, VP, VP, VP],
+    "isa_sem_loss_k_assemble": [VP, VP, I32, I32, VP, VP, VP],
+    "isa_sem_loss_k_grad": [P_T, VP, VP, VP, P_T, I32, VP],
+    "isa_labels_from_onehot": [VP, I32, I32, I64, VP, VP, VP],
     "isa_ins_softmax_bwd": [VP, VP, VP, VP, VP, I32, I32, I64, VP, I32, VP],
     "isa_maskbn_bwd": [P_T, VP, VP, VP, VP, F, VP, I32, VP, VP, VP, VP, P_T, I32, VP],
     "isa_sp_bwd": [P_T, P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, F, I32, VP, P_T, I32,

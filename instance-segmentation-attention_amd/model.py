@@ -46,11 +46,13 @@ class Model(object):
 
     # ------------------------------------------------------------------ training
     def __define_optimizer(self, learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm,
-                           optimizer='Adadelta'):
+                           optimizer='Adadelta', criterion='Multi', class_weights=None, optimize_bg=False):
         assert optimizer in ['RMSprop', 'Adam', 'Adadelta', 'SGD']            # model.py:147
         assert optimizer == 'Adadelta', "the shipped TrainingSettings use Adadelta (training_settings.py:27)"
+        # the criterion of __define_criterion (model.py:102-133): CE(weight) and / or Dice(optimize_bg, weight)
         self.trainer = Trainer(self.model, world_size=self.world, lr=learning_rate, weight_decay=weight_decay,
-                               clip_grad_norm=clip_grad_norm)
+                               clip_grad_norm=clip_grad_norm, criterion=criterion, class_weights=class_weights,
+                               optimize_bg=optimize_bg)
         self._plateau = dict(best=float('inf'), bad=0, factor=lr_drop_factor, patience=lr_drop_patience)
 
     def __plateau_step(self, val):                   # torch ReduceLROnPlateau(mode='min') semantics, rel 1e-4
@@ -85,13 +87,23 @@ class Model(object):
                 if sem.dtype == torch.uint8:              # compact targets: one-hot on the device (isa_collate_targets)
                     sem, _ = self.model.net.collate_targets(sem, ins)
                 costs = self.model.sem_costs(sem)         # the reference logs CE / Dice in validation too (model.py:255-269)
-                row['CE Cost'], row['Dice Cost'] = costs[0], costs[1]
+                row.update(self.__sem_row(costs))
             return row
-        row = {'CE Cost': out['sem'][0].clone(), 'Dice Cost': out['sem'][1].clone()}
+        row = self.__sem_row(out['sem'])
         h = out['head']
         if h is not None:                                 # semantic-only models have no instance head (model.py:244)
             row.update({'INS Cost': h[0] + float('nan'), 'Criterion': h[1].clone(), 'ins_ce_loss': h[2].clone(),
                         'ins_dice_loss': h[3].clone()})
+        return row
+
+    def __sem_row(self, costs):
+        """Only the terms the criterion computes, as the reference's out_metrics (model.py:255-269)."""
+        crit = self.model.net.crit
+        row = {}
+        if crit.ce:
+            row['CE Cost'] = costs[0].clone()
+        if crit.dice:
+            row['Dice Cost'] = costs[1].clone()
         return row
 
     def fit(self, criterion_type, delta_var, delta_dist, norm, learning_rate, weight_decay, clip_grad_norm,
@@ -105,7 +117,8 @@ class Model(object):
             tlog = open(os.path.join(model_save_path, 'training.log'), 'w')
             vlog = open(os.path.join(model_save_path, 'validation.log'), 'w')
             tlog.write('Epoch,Cost\n'); vlog.write('Epoch,Cost\n')
-        self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer)
+        self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
+                                criterion_type, class_weights, optimize_bg)
         best_val_cost = np.inf
         if os.environ.get('ISA_PREFETCH', '1') != '0':      # batch i+1 uploads on a side stream while step i runs
             from .data import DevicePrefetcher
@@ -121,7 +134,13 @@ class Model(object):
             # an empty loader (a validation set smaller than one batch per rank under a dropping sampler) must not take the
             # epoch down on every rank: its mean is NaN and the plateau scheduler sees the training cost instead
             mean = lambda rows, k: float(torch.stack([r[k].float() for r in rows]).mean()) if rows else float("nan")
-            key = 'ins_dice_loss' if self.use_instance_segmentation else 'Dice Cost'
+            # the cost that drives the plateau scheduler and checkpointing (model.py:425-434)
+            if self.use_instance_segmentation:
+                key = 'ins_dice_loss'
+            elif criterion_type in ['Dice', 'Multi']:
+                key = 'Dice Cost'
+            else:
+                key = 'CE Cost'
             # rank-averaged costs: the plateau scheduler must take the same decision on every rank
             train_cost = parallel.mean_over_ranks(mean(tr, key), self.world)
             val_cost = parallel.mean_over_ranks(mean(va, key), self.world)

@@ -14,10 +14,48 @@ from . import lib as L
 from .engine import Act, Engine, Pro, rup
 
 
+CRITERIA = ("CE", "Dice", "Multi")
+
+
+class SemCriterion:
+    """The trainer's semantic criterion (Model.__define_criterion, model.py:102-133): criterion type, class weights,
+    optimize_bg.  Its settings live in ONE device buffer allocated here, once, and rewritten in place: a captured
+    hipGraph reads them at replay time.  Layout (include/isa_kernels.h, isa_sem_loss_k_*): {use_ce, use_dice,
+    optimize_bg, 0, w_0 .. w_{K-1}}; no weights = all ones (the same CE and Dice as unweighted).
+    `legacy`: the shipped combination (K = 2, Multi, no weights, fg only) runs the 2-class kernels it always ran."""
+
+    def __init__(self, n_classes, device):
+        self.K = n_classes
+        self.cfg = torch.zeros(4 + n_classes, dtype=torch.float32, device=device)
+        self.set("Multi", None, False)
+
+    def set(self, criterion="Multi", class_weights=None, optimize_bg=False):
+        assert criterion in CRITERIA, "criterion must be one of %s" % (CRITERIA,)
+        K = self.K
+        if class_weights is not None:
+            class_weights = [float(v) for v in class_weights]
+            if len(class_weights) != K:
+                raise ValueError("class_weights: %d values for %d classes" % (len(class_weights), K))
+            if min(class_weights) < 0 or sum(class_weights[0 if optimize_bg else 1:]) <= 0:
+                raise ValueError("class_weights must be non-negative with a positive sum over the optimised classes")
+        self.criterion, self.class_weights, self.optimize_bg = criterion, class_weights, bool(optimize_bg)
+        self.ce, self.dice = criterion in ("CE", "Multi"), criterion in ("Dice", "Multi")
+        self.legacy = K == 2 and criterion == "Multi" and class_weights is None and not optimize_bg
+        w = class_weights if class_weights is not None else [1.0] * K
+        self.cfg.copy_(torch.tensor([float(self.ce), float(self.dice), float(self.optimize_bg), 0.0] + w))
+
+    @property
+    def weights(self):
+        """The class weights on the device (a view of the settings buffer: in-place writes reach a captured graph)."""
+        return self.cfg[4:]
+
+
 class Network:
-    def __init__(self, eng: Engine, use_instance_seg=True):
+    def __init__(self, eng: Engine, use_instance_seg=True, n_classes=2):
         self.E = eng
         self.use_instance_seg = use_instance_seg
+        self.n_classes = n_classes
+        self.crit = SemCriterion(n_classes, eng.device)
 
     # ------------------------------------------------------------------ blocks
     def block_v1(self, x: Act, pre: str, out: Act):
@@ -117,7 +155,7 @@ class Network:
                                 P.ptr("channelAttend.fc.2.weight"), P.ptr("channelAttend.fc.2.bias"), n, c, 16,
                                 L.ptr(hid), L.ptr(gate), E.st()), "isa_se_fc")
         gated = x_dec.with_pro(Pro(bscale=gate))
-        sem = E.new_act(n, x_dec.h, x_dec.w, 2)
+        sem = E.new_act(n, x_dec.h, x_dec.w, self.n_classes)
         E.conv(gated, "sem_seg_output.weight", sem, bias="sem_seg_output.bias", record_bwd=False)
         reg = E._last_conv["reg"]
         if E.record:
@@ -142,30 +180,56 @@ class Network:
             E.tape.append(bwd)
         return sem
 
-    def sem_loss(self, sem: Act, sem_onehot: torch.Tensor):
-        """Trainer-side CE + Dice(time=1) on the semantic logits (model.py:255-269).
-        Returns device tensor [ce, dice]; records d(sem)."""
+    def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None):
+        """Trainer-side semantic criterion on the logits (model.py:255-269), per self.crit: CE (weighted) and / or
+        Dice (time=1, per class, fg or all).  `labels`: the uint8 label map when the caller has it (compact targets),
+        else taken from the one-hot.  Returns device tensor [ce, dice] (0 for a term the criterion lacks); records
+        d(sem)."""
         E = self.E
         n = sem.n
-        sums = E.scratch(8 * n)
-        L.check(E.lib.isa_mask_loss_sums(sem.d(), None, L.ptr(sem_onehot), L.ptr(sums), E.st()), "isa_mask_loss_sums")
-        coef, scal = E.f32(4 * n), E.f32(2)
-        L.check(E.lib.isa_sem_loss(L.ptr(sums), n, L.ptr(coef), L.ptr(scal), E.st()), "isa_sem_loss")
+        if self.crit.legacy:             # the shipped criterion: its pinned 2-class kernels
+            sums = E.scratch(8 * n)
+            L.check(E.lib.isa_mask_loss_sums(sem.d(), None, L.ptr(sem_onehot), L.ptr(sums), E.st()), "isa_mask_loss_sums")
+            coef, scal = E.f32(4 * n), E.f32(2)
+            L.check(E.lib.isa_sem_loss(L.ptr(sums), n, L.ptr(coef), L.ptr(scal), E.st()), "isa_sem_loss")
+            if E.record:
+                def bwd():
+                    acc = E.grads.claim(sem, E)
+                    L.check(E.lib.isa_mask_loss_grad(sem.d(), None, L.ptr(sem_onehot), L.ptr(coef),
+                                                     E.grads.grad_of(sem).d(), acc, E.st()), "isa_mask_loss_grad(sem)")
+                E.tape.append(bwd)
+            return scal
+        K, cfg = sem.c, self.crit.cfg
+        if labels is None:
+            assert sem_onehot.dtype == torch.int64 and tuple(sem_onehot.shape) == (n, K, sem.h, sem.w)
+            labels = E.arena.alloc((n, sem.h, sem.w), torch.uint8)
+            L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, K, sem.h * sem.w, L.ptr(labels), None, E.st()),
+                    "isa_labels_from_onehot")
+        assert labels.dtype == torch.uint8 and tuple(labels.shape) == (n, sem.h, sem.w)
+        sums = E.scratch(3 * n * K + 2)
+        L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+        coef, scal = E.f32(3 * n * K + 1), E.f32(2)
+        L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
+                "isa_sem_loss_k_assemble")
         if E.record:
             def bwd():
                 acc = E.grads.claim(sem, E)
-                L.check(E.lib.isa_mask_loss_grad(sem.d(), None, L.ptr(sem_onehot), L.ptr(coef),
-                                                 E.grads.grad_of(sem).d(), acc, E.st()), "isa_mask_loss_grad(sem)")
+                L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef),
+                                                  E.grads.grad_of(sem).d(), acc, E.st()), "isa_sem_loss_k_grad")
             E.tape.append(bwd)
         return scal
 
     def onehot_map(self, sem_onehot: torch.Tensor) -> torch.Tensor:
-        """int64 one-hot [n,2,h,w] -> fp32 {0,1} map [n, h*w] (sem_seg_argmax of reseg.py:118, on the device)."""
+        """int64 one-hot [n,K,h,w] -> fp32 argmax(1) map [n, h*w] (sem_seg_argmax of reseg.py:118, on the device)."""
         E = self.E
         n, c, h, w = sem_onehot.shape
-        assert c == 2 and sem_onehot.dtype == torch.int64
+        assert c == self.n_classes and sem_onehot.dtype == torch.int64
         out = E.f32(n, h * w)
-        L.check(E.lib.isa_onehot_map(L.ptr(sem_onehot), n, h * w, L.ptr(out), E.st()), "isa_onehot_map")
+        if c == 2:
+            L.check(E.lib.isa_onehot_map(L.ptr(sem_onehot), n, h * w, L.ptr(out), E.st()), "isa_onehot_map")
+        else:
+            L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, c, h * w, None, L.ptr(out), E.st()),
+                    "isa_labels_from_onehot")
         return out
 
     def softmax_nchw(self, logits: Act) -> torch.Tensor:
@@ -211,20 +275,28 @@ class Network:
             return self.image_ex(x)
         return self.to_nhwc(x.to(device=self.E.device, dtype=torch.float32))
 
-    def collate_targets(self, sem: torch.Tensor, ins: torch.Tensor):
+    def collate_targets(self, sem: torch.Tensor, ins: torch.Tensor, labels=False, onehot=True):
         """Targets as the reference's collate function leaves them before its last five lines (dataset.py:349-379):
-        ins uint8 [n,h,w,K] instance planes, sem uint8 [n,h,w] -> (sem one-hot int64 [n,2,h,w], ins int64 [n,K,h,w])
-        on the device (isa_collate_targets).  8.6x less PCIe traffic than shipping the int64 tensors."""
+        ins uint8 [n,h,w,K] instance planes, sem uint8 [n,h,w] -> (sem one-hot int64 [n,C,h,w], ins int64 [n,K,h,w])
+        on the device (isa_collate_targets; isa_collate_targets_k for C = n_classes > 2).  8.6x less PCIe traffic than
+        shipping the int64 tensors.  labels=True: also the uint8 label map for the K-class criterion, returned third;
+        onehot=False then skips the one-hot (None in its place)."""
         E = self.E
         assert ins.dtype == torch.uint8 and ins.dim() == 4 and sem.dtype == torch.uint8 and sem.dim() == 3
         n, h, w, k = ins.shape
         assert tuple(sem.shape) == (n, h, w)
         ins, sem = ins.to(E.device).contiguous(), sem.to(E.device).contiguous()
+        C = self.n_classes
         ins_out = E.arena.alloc((n, k, h, w), torch.int64)
-        sem_out = E.arena.alloc((n, 2, h, w), torch.int64)
-        L.check(E.lib.isa_collate_targets(L.ptr(ins), L.ptr(sem), n, h, w, k, L.ptr(ins_out), L.ptr(sem_out), E.st()),
-                "isa_collate_targets")
-        return sem_out, ins_out
+        sem_out = E.arena.alloc((n, C, h, w), torch.int64) if onehot or not labels else None
+        if C == 2 and not labels:
+            L.check(E.lib.isa_collate_targets(L.ptr(ins), L.ptr(sem), n, h, w, k, L.ptr(ins_out), L.ptr(sem_out), E.st()),
+                    "isa_collate_targets")
+            return sem_out, ins_out
+        lab = E.arena.alloc((n, h, w), torch.uint8) if labels else None
+        L.check(E.lib.isa_collate_targets_k(L.ptr(ins), L.ptr(sem), n, h, w, k, C, L.ptr(ins_out), L.ptr(sem_out),
+                                            L.ptr(lab), E.st()), "isa_collate_targets_k")
+        return (sem_out, ins_out, lab) if labels else (sem_out, ins_out)
 
     def to_nchw(self, a: Act) -> torch.Tensor:
         E = self.E

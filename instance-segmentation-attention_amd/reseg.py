@@ -27,7 +27,12 @@ class ReSeg(nn.Module):
     def __init__(self, n_classes, use_instance_seg=True, pretrained=True, use_coordinates=False,
                  use_wae=True, usegpu=True, training=True, dtype=torch.float32, device=None):
         super().__init__()
-        assert n_classes == 2, "the reference head is built for 2 classes (data_settings.py:19)"
+        if not 2 <= n_classes <= 32:
+            raise ValueError("n_classes must be in [2, 32] (the K-class criterion kernels), got %d" % n_classes)
+        if use_instance_seg and n_classes != 2:
+            # the instance head reads sem_seg_argmax as a {0,1} foreground mask (reseg.py:118-123)
+            raise ValueError("the instance head needs n_classes == 2 (foreground / background); build "
+                             "ReSeg(n_classes, use_instance_seg=False) for a K-class semantic network")
         if not torch.cuda.is_available():
             raise RuntimeError("ReSeg (MI355X build) needs a GPU: there is no CPU fallback")
         L.lib()                                   # fail loudly if the HIP library is missing
@@ -39,10 +44,10 @@ class ReSeg(nn.Module):
         dev = torch.device(device or "cuda")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        self.store = ParamStore(state_dict_schema(use_instance_seg), dev)
+        self.store = ParamStore(state_dict_schema(use_instance_seg, n_classes), dev)
         self._build_tree()
         self.engine = Engine(self.store, dtype, dev)
-        self.net = Network(self.engine, use_instance_seg)
+        self.net = Network(self.engine, use_instance_seg, n_classes)
         self.head = InstanceHead(self.net)
         self.reset_parameters()
         self.train(training)
@@ -181,14 +186,18 @@ class ReSeg(nn.Module):
         slot["graph"].replay()
         return slot["out"]
 
+    def set_criterion(self, criterion="Multi", class_weights=None, optimize_bg=False):
+        """The semantic criterion of training steps and sem_costs (Model.__define_criterion, model.py:102-133)."""
+        self.net.crit.set(criterion, class_weights, optimize_bg)
+
     def sem_costs(self, sem_seg_target):
-        """Semantic CE + Dice(time=1) of the LAST forward's logits against a one-hot int64 target [B,2,H,W]
-        (validation branch of model.py:244-270).  Returns a device tensor [ce, dice]; must be called before the
-        next forward (the logits live in that step's arena)."""
+        """Semantic criterion (set_criterion; default CE + Dice(time=1)) of the LAST forward's logits against a one-hot
+        int64 target [B,K,H,W] (validation branch of model.py:244-270).  Returns a device tensor [ce, dice] (0 for a
+        term the criterion lacks); must be called before the next forward (the logits live in that step's arena)."""
         sem = getattr(self, "_last_sem", None)
         assert sem is not None, "sem_costs() follows a forward()"
         t = sem_seg_target.to(self.store.device).contiguous()
-        assert t.dtype == torch.int64 and tuple(t.shape) == (sem.n, 2, sem.h, sem.w)
+        assert t.dtype == torch.int64 and tuple(t.shape) == (sem.n, self.n_classes, sem.h, sem.w)
         was = self.engine.record
         self.engine.record = False
         try:
@@ -198,7 +207,7 @@ class ReSeg(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, training, *_input, selected_idx=None, injected_s_t=None, capture=None, _arena_key=None):
-        """reseg.py:106-130.  (x) -> (sem_out, sem_argmax);  (x, sem_onehot[B,2,H,W] i64,
+        """reseg.py:106-130.  (x) -> (sem_out, sem_argmax);  (x, sem_onehot[B,K,H,W] i64,
         ins[B,32,H,W] i64, N[B,1]) [or the compact uint8 pair sem[B,H,W], ins[B,H,W,32]: expanded on device] -> (sem_out, sem_argmax, ins_cost, criterion, ins_ce_loss,
         ins_dice_loss).  BatchNorm mode follows .train()/.eval() like the reference modules; the
         `training` flag drives sampling, F.dropout2d and the loss branch (attenet2.py:377-399).

@@ -7,8 +7,9 @@ attenet2.py:17-50,410-430, utils.py:402-420,457-483,613-630,696-710,777-786,816-
 """
 
 
-def state_dict_schema(use_instance_seg=True):
-    """(name, shape) list in the reference's registration order (probe of reseg.ReSeg(2,...))."""
+def state_dict_schema(use_instance_seg=True, n_classes=2):
+    """(name, shape) list in the reference's registration order (probe of reseg.ReSeg(2,...)); n_classes sets the rows
+    of the semantic 1x1 conv, the only shape that depends on it (reseg.py:73-75)."""
     S = []
 
     def bn(pre, c):
@@ -67,7 +68,7 @@ def state_dict_schema(use_instance_seg=True):
               ("decoder.embedding.sigma.2.weight", (1, 12)), ("decoder.embedding.sigma.2.bias", (1,))])
     S.extend([("channelAttend.fc.0.weight", (16, 32)), ("channelAttend.fc.0.bias", (16,)),
               ("channelAttend.fc.2.weight", (32, 16)), ("channelAttend.fc.2.bias", (32,)),
-              ("sem_seg_output.weight", (2, 32, 1, 1)), ("sem_seg_output.bias", (2,))])
+              ("sem_seg_output.weight", (n_classes, 32, 1, 1)), ("sem_seg_output.bias", (n_classes,))])
     if use_instance_seg:
         p1, p2 = "ins_seg_output_1", "ins_seg_output_2"
         S.extend([(p1 + ".0.weight", (32, 1, 3, 3)), (p1 + ".0.bias", (32,))]); bn(p1 + ".1", 32)

@@ -14,8 +14,13 @@ from .parallel import exchange_and_update
 
 
 class Trainer:
-    def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6):
+    def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6,
+                 criterion='Multi', class_weights=None, optimize_bg=False):
         self.model = model
+        # semantic criterion (model.py:102-133, 255-269): written once into the model's settings buffer, which was
+        # allocated with the model - a captured step keeps reading the same device memory
+        model.set_criterion(criterion, class_weights, optimize_bg)
+        self.criterion = criterion
         self.world = world_size
         self.lr, self.wd, self.clip, self.rho, self.eps = lr, weight_decay, clip_grad_norm, rho, eps
         st = model.store
@@ -53,12 +58,17 @@ class Trainer:
         if getattr(m, "_weights_dirty", True) and E.packer.entries:
             E.packer.pack()
         m._weights_dirty = False
+        labels = None
         if ins.dtype == torch.uint8:         # compact targets (uint8 planes [B,H,W,K] + uint8 map [B,H,W]): expand on device
-            sem, ins = net.collate_targets(sem, ins)
+            if net.crit.legacy:
+                sem, ins = net.collate_targets(sem, ins)
+            else:                            # the K-class criterion reads the label map; the head the one-hot
+                sem, ins, labels = net.collate_targets(sem, ins, labels=True, onehot=m.use_instance_seg)
         xin = net.input_view(x)
         x_dec, feats = net.unet(xin)
         sem_a = net.sem_head(x_dec)
-        sem_scal = net.sem_loss(sem_a, sem)
+        m._last_sem = sem_a                  # the step's logits (arena view: read before the next step)
+        sem_scal = net.sem_loss(sem_a, sem, labels)
         head_scal = None
         if m.use_instance_seg:
             n_ins = n_objects if isinstance(n_objects, list) else [int(v) for v in n_objects.reshape(-1).tolist()]
@@ -77,6 +87,13 @@ class Trainer:
             E.backward()
         self.last = dict(sem=sem_scal, head=head_scal)
         return self.last
+
+    @property
+    def class_weights(self):
+        """The class weights the K-class criterion reads, on the device (ones when none were given); write them in place
+        (`.copy_`) and a captured step follows.  None on the shipped criterion, whose kernels take no weights."""
+        crit = self.model.net.crit
+        return None if crit.legacy else crit.weights
 
     def sync_lr(self):
         """Host lr -> device scalar (outside any graph; a no-op unless the scheduler changed it)."""

@@ -19,50 +19,90 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-import isa_amd  # noqa: F401,E402
-from isa_amd.model import Model  # noqa: E402
-from isa_amd.data import SyntheticLoader  # noqa: E402
 
-parser = argparse.ArgumentParser()
-parser.add_argument('--model', default='', help="Filepath of trained model (to continue training) [Default: '']")
-parser.add_argument('--usegpu', action='store_true', default=True, help='Enables the GPU [always on in this build]')
-parser.add_argument('--nepochs', type=int, default=800, help='Number of epochs to train for [Default: 800]')
-parser.add_argument('--batchsize', type=int, default=2, help='Batch size [Default: 2]')
-parser.add_argument('--debug', action='store_true', help='Activates debug mode [Default: False]')
-parser.add_argument('--nworkers', type=int, default=2, help='accepted for compatibility (synthetic data needs none)')
-parser.add_argument('--dataset', type=str, default='CVPPP', help='Name of the dataset which is "CVPPP"')
-parser.add_argument('--iters-per-epoch', type=int, default=8)
-parser.add_argument('--size', type=int, default=256, help='image height = width (the reference hard-codes 256, config.py:1)')
-parser.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
-parser.add_argument('--compact-targets', action='store_true',
-                    help='loader yields uint8 targets (sem [B,H,W], ins [B,H,W,32]); expanded on the device')
-parser.add_argument('--data', default='', help='directory holding <data>/training-lmdb and <data>/validation-lmdb record '
-                    'stores (the reference\'s key schema over a directory: isa_amd/records.py); default: synthetic batches')
-parser.add_argument('--out', default=os.path.join(ROOT, 'models', 'CVPPP', 'run'))
-opt = parser.parse_args()
-assert opt.dataset in ['CVPPP', ]
 
-from isa_amd import parallel  # noqa: E402
-world, rank, local_rank = parallel.init_from_env()           # binds the GPU before anything else touches it
-assert opt.batchsize % world == 0, "--batchsize is the global batch: it must divide by the number of ranks"
-per_rank = opt.batchsize // world
-SEED = 23                                                     # training_settings.py:53
-random.seed(parallel.rank_seed(SEED, rank)); np.random.seed(parallel.rank_seed(SEED, rank))
-torch.manual_seed(parallel.rank_seed(SEED, rank))             # instance order, glimpse points, dropout: per rank
-model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=True, load_model_path=opt.model, usegpu=True,
-              dtype=torch.bfloat16 if opt.dtype == 'bf16' else torch.float32)
-# every rank draws its own shard of each global batch (weights start identical: the model seed is not per rank)
-train_loader = SyntheticLoader(opt.iters_per_epoch, per_rank, opt.size, opt.size, seed=parallel.rank_seed(SEED, rank),
-                               compact=opt.compact_targets)
-test_loader = SyntheticLoader(max(1, opt.iters_per_epoch // 4), per_rank, opt.size, opt.size,
-                              seed=parallel.rank_seed(SEED + 7, rank), compact=opt.compact_targets)
-if opt.data:                      # the reference's datasets (train.py:87-147): records -> device-side collate
-    from isa_amd.records import RecordDataset, RecordLoader
-    train_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'training-lmdb')), per_rank, opt.size, opt.size,
-                                mode='training', seed=SEED, rank=rank, world=world)
-    test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
-                               mode='test', seed=SEED, rank=rank, world=world)
-model.fit('Multi', 0.5, 1.5, 2, 1.0, 0.001, 10.0, 0.5, 25, False, 'Adadelta', True, opt.nepochs, None,
-          train_loader, test_loader, opt.out, opt.debug)
-if world > 1:
-    torch.distributed.destroy_process_group()
+def build_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--model', default='', help="Filepath of trained model (to continue training) [Default: '']")
+    parser.add_argument('--usegpu', action='store_true', default=True, help='Enables the GPU [always on in this build]')
+    parser.add_argument('--nepochs', type=int, default=800, help='Number of epochs to train for [Default: 800]')
+    parser.add_argument('--batchsize', type=int, default=2, help='Batch size [Default: 2]')
+    parser.add_argument('--debug', action='store_true', help='Activates debug mode [Default: False]')
+    parser.add_argument('--nworkers', type=int, default=2, help='accepted for compatibility (synthetic data needs none)')
+    parser.add_argument('--dataset', type=str, default='CVPPP', help='Name of the dataset which is "CVPPP"')
+    parser.add_argument('--iters-per-epoch', type=int, default=8)
+    parser.add_argument('--size', type=int, default=256, help='image height = width (the reference hard-codes 256, config.py:1)')
+    parser.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
+    parser.add_argument('--compact-targets', action='store_true',
+                        help='loader yields uint8 targets (sem [B,H,W], ins [B,H,W,32]); expanded on the device')
+    parser.add_argument('--data', default='', help='directory holding <data>/training-lmdb and <data>/validation-lmdb record '
+                        'stores (the reference\'s key schema over a directory: isa_amd/records.py); default: synthetic batches')
+    parser.add_argument('--out', default=os.path.join(ROOT, 'models', 'CVPPP', 'run'))
+    # the semantic criterion (settings/CVPPP/training_settings.py: CRITERION, CLASS_WEIGHTS, OPTIMIZE_BG; data_settings.py:
+    # N_CLASSES); the defaults are the shipped settings
+    parser.add_argument('--criterion', default='Multi', choices=['CE', 'Dice', 'Multi'])
+    parser.add_argument('--class-weights', default=None, help='one weight per class, comma separated (w0,w1,...)')
+    parser.add_argument('--optimize-bg', action='store_true', help='Dice over every class, background included')
+    parser.add_argument('--n-classes', type=int, default=2, help='semantic classes, 2..32 (more than 2 needs --semantic-only)')
+    parser.add_argument('--semantic-only', action='store_true', help='train the semantic network alone (no instance head)')
+    return parser
+
+
+def parse_args(argv=None):
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    if opt.dataset not in ['CVPPP', ]:
+        parser.error('--dataset must be CVPPP')
+    if not 2 <= opt.n_classes <= 32:
+        parser.error('--n-classes must be in [2, 32]')
+    if opt.n_classes > 2 and not opt.semantic_only:
+        parser.error('--n-classes > 2 needs --semantic-only: the instance head reads a foreground / background mask')
+    if opt.class_weights is not None:
+        try:
+            opt.class_weights = [float(v) for v in opt.class_weights.split(',')]
+        except ValueError:
+            parser.error('--class-weights: comma separated numbers')
+        if len(opt.class_weights) != opt.n_classes:
+            parser.error('--class-weights: %d values for %d classes' % (len(opt.class_weights), opt.n_classes))
+    return opt
+
+
+def fit_arguments(opt):
+    """Model.fit's arguments ahead of the loaders, as the reference's train.py passes them (training_settings.py)."""
+    return (opt.criterion, 0.5, 1.5, 2, 1.0, 0.001, 10.0, 0.5, 25, opt.optimize_bg, 'Adadelta', True, opt.nepochs,
+            opt.class_weights)
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+    import isa_amd  # noqa: F401
+    from isa_amd.model import Model
+    from isa_amd.data import SyntheticLoader
+    from isa_amd import parallel
+    world, rank, local_rank = parallel.init_from_env()           # binds the GPU before anything else touches it
+    assert opt.batchsize % world == 0, "--batchsize is the global batch: it must divide by the number of ranks"
+    per_rank = opt.batchsize // world
+    SEED = 23                                                     # training_settings.py:53
+    random.seed(parallel.rank_seed(SEED, rank)); np.random.seed(parallel.rank_seed(SEED, rank))
+    torch.manual_seed(parallel.rank_seed(SEED, rank))             # instance order, glimpse points, dropout: per rank
+    model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=not opt.semantic_only,
+                  load_model_path=opt.model, usegpu=True, dtype=torch.bfloat16 if opt.dtype == 'bf16' else torch.float32)
+    # every rank draws its own shard of each global batch (weights start identical: the model seed is not per rank)
+    train_loader = SyntheticLoader(opt.iters_per_epoch, per_rank, opt.size, opt.size, seed=parallel.rank_seed(SEED, rank),
+                                   compact=opt.compact_targets, n_classes=opt.n_classes)
+    test_loader = SyntheticLoader(max(1, opt.iters_per_epoch // 4), per_rank, opt.size, opt.size,
+                                  seed=parallel.rank_seed(SEED + 7, rank), compact=opt.compact_targets,
+                                  n_classes=opt.n_classes)
+    if opt.data:                      # the reference's datasets (train.py:87-147): records -> device-side collate
+        from isa_amd.records import RecordDataset, RecordLoader
+        train_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'training-lmdb')), per_rank, opt.size, opt.size,
+                                    mode='training', seed=SEED, rank=rank, world=world)
+        test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
+                                   mode='test', seed=SEED, rank=rank, world=world)
+    model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+if __name__ == '__main__':
+    main()
