@@ -303,7 +303,8 @@ int isa_chan_mean(const isa_tensor* x, const isa_pro* pro, float* out, void* str
 int isa_se_fc(const float* mean, const float* w1, const float* b1, const float* w2,
               const float* b2, int32_t n, int32_t c, int32_t hidden, float* hid, float* gate,
               void* stream);
-/* argmax over channels -> float map in {0..c-1} (first max wins, torch.argmax) */
+/* argmax over channels -> float map in {0..c-1} (first max wins, torch.argmax; NaN counts as the maximum, so the first
+ * NaN channel wins, as in torch) */
 int isa_chan_argmax(const isa_tensor* x, const isa_tensor* y, void* stream);
 
 /* ---- attention mask head (utils.py:457-663, attenet2.py:304-347) ---------------------------------
@@ -337,7 +338,9 @@ int isa_ins_softmax(const float* merge, const int64_t* ins, const int32_t* idx, 
  * (attenet2.py:384-399) are one launch.  isa_concat_aux's `mask_n` is the same for its shared mask_all map. */
 /* DecoderLayer.sample (attenet2.py:304-324): first argmax per row, on device.  race == NULL: the eval branch
  * (argmax of alpha).  race != NULL ([n, L] draws from Exp(1)): argmax of alpha / race = one draw from
- * Multinomial(alpha), the training branch (torch.multinomial's own single-sample form). */
+ * Multinomial(alpha), the training branch (torch.multinomial's own single-sample form).  alpha / race is an fp32
+ * division, correctly rounded.  NaN never wins (unlike torch.argmax): a pixel with alpha = 0 and race = 0 cannot be
+ * drawn; a row without any value above -inf (all NaN, or all -inf) gives 0.  L >= 1. */
 int isa_row_argmax(const float* a, const float* race, int32_t n, int64_t L, int32_t* out, void* stream);
 /* sem_seg_argmax = GT.argmax(1) (reseg.py:118) of the int64 one-hot target [n,2,h,w] as an fp32 {0,1} map [n, h*w] */
 int isa_onehot_map(const int64_t* onehot, int32_t n, int64_t hw, float* out, void* stream);
@@ -345,10 +348,14 @@ int isa_onehot_map(const int64_t* onehot, int32_t n, int64_t hw, float* out, voi
 int isa_dropout_mask(const float* u, int64_t n, float keep, float* out, void* stream);
 /* softmax over the channels of an NHWC logit map, written NCHW fp32 (Model.predict, model.py:486) */
 int isa_softmax_nchw(const isa_tensor* x, float* out, void* stream);
-/* UpDecoderLayer.resize (utils.py:841-846): f x f max-pool of the instance plane / of an fp32 map */
+/* UpDecoderLayer.resize (utils.py:841-846): f x f max-pool of the instance plane / of an fp32 map.  The instance planes
+ * must hold values in {0, 1}: any nonzero value pools to 1.  The fp32 map's maximum starts from -inf (negative maps pool
+ * exactly).  H % f, W % f and n % nsrc must be 0. */
 int isa_pool_target(const int64_t* ins, const int32_t* idx, const float* src, int32_t nobj, int32_t n,
                     int32_t H, int32_t W, int32_t f, float* out, int32_t nsrc, void* stream);
-/* mask_all + conPosition channels (utils.py:1027-1045,1085) written into a concat slice */
+/* mask_all + conPosition channels (utils.py:1027-1045,1085) written into a concat slice: channel 0 = mask_all of image
+ * b % mask_n, channels 1 .. 2nb = the code bits of (row % f, col % f) of s_t[b] (row bits MSB first, then the column
+ * bits), channel 2nb + 1 = the marker; the code and marker channels are 0 outside the coarse cell of s_t[b]. */
 int isa_concat_aux(const isa_tensor* dst, const float* mask_all, const int32_t* s_t, int32_t W_full,
                    int32_t f, int32_t nb, int32_t mask_n, void* stream);
 /* UpAttenLayer.Mask (utils.py:1047-1056): out = up * softmax2(bilinear_x2(pred))[1] */
@@ -540,7 +547,11 @@ int64_t isa_resize_bilinear_ws_bytes(int32_t n, int32_t h0, int32_t w0, int32_t 
 int isa_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t c, uint8_t* dst,
                            int32_t h, int32_t w, void* ws, int64_t ws_bytes, void* stream);
 
-/* ---- boundary layout converters (the reference passes NCHW fp32: reseg.py:106-110) ----------- */
+/* ---- boundary layout converters (the reference passes NCHW fp32: reseg.py:106-110) -----------
+ * nchw_to_nhwc: channels [csrc, c) are written as 0; bf16 stores round to nearest even.  Channels at or above c: a dst
+ * with ld == rup(c, 8) <= 32, 16-byte aligned src and data and h*w % 4 == 0 is written in whole padded rows (channels
+ * [c, ld) become 0); any other dst is written element by element and channels outside [0, c) are left alone.
+ * nhwc_to_nchw writes the c channels of src. */
 int isa_nchw_to_nhwc(const float* src, int32_t csrc, const isa_tensor* dst, void* stream);
 int isa_nhwc_to_nchw(const isa_tensor* src, float* dst, void* stream);
 

@@ -383,11 +383,12 @@ __global__ __launch_bounds__(256) void row_norm_kernel(float* out, const float* 
 // ---- a11: s_t[b] = argmax_p alpha[b,p], first maximum wins (torch.argmax) -------------------------
 // `race` (optional): the exponential race of DecoderLayer.sample's training branch - argmax_p alpha[p] / race[p] with
 // race ~ Exp(1) draws one index from Multinomial(alpha) (torch.multinomial's own single-sample form, attenet2.py:321)
+// NaN never wins (`v > best` is false); a row without a value above -inf keeps index 0, never one outside [0, L).
 __global__ __launch_bounds__(1024) void row_argmax_kernel(const float* a, const float* race, long L, int32_t* out) {
     __shared__ float shv[16];
     __shared__ int shi[16];
     const int b = blockIdx.x;
-    float best = -INFINITY; int bi = 0x7fffffff;
+    float best = -INFINITY; int bi = 0;
     for (long p = threadIdx.x; p < L; p += 1024) {
         float v = a[(long)b * L + p];
         if (race) v = v / race[(long)b * L + p];
@@ -625,7 +626,7 @@ extern "C" int isa_ins_softmax(const float* merge, const int64_t* ins, const int
 }
 
 extern "C" int isa_row_argmax(const float* a, const float* race, int32_t n, int64_t L, int32_t* out, void* stream) {
-    if (!a || !out || n <= 0) return ISA_EINVAL;
+    if (!a || !out || n <= 0 || L <= 0) return ISA_EINVAL;
     hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(1024), 0, as_stream(stream), a, race, (long)L, out);
     return launch_status();
 }

@@ -506,7 +506,7 @@ __global__ __launch_bounds__(256) void chan_argmax_kernel(View x, View y) {
         float best = st<T>::ld(px); int bi = 0;
         for (int c = 1; c < x.c; ++c) {
             const float v = st<T>::ld(px + c);
-            if (v > best) { best = v; bi = c; }
+            if (v > best || (v != v && best == best)) { best = v; bi = c; }     // NaN is the maximum (torch.argmax)
         }
         st<T>::stv(reinterpret_cast<T*>(y.data) + pix * y.ld, (float)bi);
     }
