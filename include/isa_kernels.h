@@ -114,7 +114,8 @@ typedef struct isa_pack_entry { /* one parameter tensor to repack (see isa_pack_
     int32_t kmap_off;           /* >=0: offset into kmap[] giving, per destination channel of the
                                    K axis (kinds 0,2: contraction index; kinds 1,3: row; kinds 4,5:
                                    column), the source channel or -1 for zero: channel padding and
-                                   concat reordering.  <0: identity */
+                                   concat reordering.  The map has one entry per destination channel:
+                                   kp entries for kinds 0 and 2, `rows` entries for the others.  <0: identity */
     int32_t rows;               /* destination rows (see kind) */
 } isa_pack_entry;
 

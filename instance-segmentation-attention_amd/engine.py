@@ -323,8 +323,13 @@ class Packer:
             return key
         kmap_off = -1
         if kmap is not None:
+            # pack_kernel reads one map entry per destination channel of the K axis: kp of them for kinds 0 and 2, `rows`
+            # for the others.  A shorter map is padded with -1 (zero), or the kernel would read the next entry's map
+            dest = kp if kind in (0, 2) else rows
+            assert len(kmap) <= dest, (name, len(kmap), dest)
             kmap_off = len(self.kmaps)
             self.kmaps.extend(int(v) for v in kmap)
+            self.kmaps.extend([-1] * (dest - len(kmap)))
         if kind in (0, 1):
             size = rows * taps * kp
         elif kind == 2:
