@@ -366,6 +366,30 @@ int isa_gate(const isa_tensor* up, const isa_tensor* pred, const isa_tensor* out
 int isa_mask_loss_sums(const isa_tensor* pred, const float* target, const int64_t* onehot, float* sums,
                        void* stream);
 
+/* ---- ground-truth-free instance inference (ReSeg.segment; the reference has no working form of it) ----------------
+ * State per image b over L = h*w pixels: labels uint8 [n, L] (0 = no instance), count int32 [n] (instances found),
+ * remaining[b,p] = sem[b,p] > 0.5 and labels[b,p] == 0, active[b] = any(remaining[b]), the glimpse point s_t[b].
+ * The point of an image is the first arg-max of merge[b,p] over remaining[b]: a NaN score counts as -inf (it never
+ * beats a number), equal scores go to the smaller pixel index, and if no remaining pixel scores above -inf the point is
+ * the first remaining pixel - so the point of an active image is always one of its remaining pixels; an inactive
+ * image gets 0.
+ * isa_seg_begin: labels = 0, count = 0, then s_t / active from the foreground map sem (fp32 [n, L]), and
+ *   any_active[0] = 1 if any image is active, else 0.
+ * isa_seg_claim: one pass over [n, L].  pred: the decoder's level-4 logits [n,h,w,2] (fp32 | bf16, any ld; ld == 2 with
+ *   16-byte aligned data takes 16-byte loads) for the points s_t.  In an image with active[b] != 0 and count[b] < 255
+ *   every remaining pixel with l1 > l0 (false for NaN), and the pixel s_t[b] if it is remaining, gets label
+ *   count[b] + 1, and count[b] grows by one; other images keep labels and count.  Then s_next / active / any_active
+ *   are set from what stays remaining, as isa_seg_begin sets them.  s_next may be s_t (it is written by the second
+ *   launch, after every read of s_t).
+ * Both run a chunk pass (a row is shared by up to ISA_ROW_CHUNKS workgroups) and a one-workgroup fold of the chunk
+ * candidates, which alone writes count / active / s_next / any_active; the result does not depend on the order in which
+ * workgroups run.  part: caller scratch of n * ISA_ROW_CHUNKS * 2 floats.  L % 4 == 0; sem and merge 16-byte aligned,
+ * labels 4-byte aligned (ISA_EALIGN otherwise); n <= 65535. */
+int isa_seg_begin(const float* sem, const float* merge, int32_t n, int64_t L, uint8_t* labels, int32_t* count,
+                  int32_t* s_t, int32_t* active, int32_t* any_active, float* part, void* stream);
+int isa_seg_claim(const isa_tensor* pred, const float* sem, const float* merge, const int32_t* s_t, uint8_t* labels,
+                  int32_t* count, int32_t* active, int32_t* s_next, int32_t* any_active, float* part, void* stream);
+
 /* ---- losses and hand-derived backward of the head (the reference relies on autograd) ------------
  * isa_head_loss: attenet2.py:239-290 on device (no host sync): per-level gradient coefficients,
  * REINFORCE advantage with the EMA baseline (device scalar), and scal[0..3] += {ins_cost without the

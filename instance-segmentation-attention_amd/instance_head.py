@@ -30,6 +30,7 @@ LAMBDA_L, LAMBDA_R = 0.5, 2.0               # config.py:45-46
 MAX_ITER = 2                                # config.py:56
 DROP_RATE = 0.5                             # config.py:64
 ROW_PART = 64 * 4                           # floats of chunk partials per softmax row (ISA_ROW_CHUNKS * 4, isa_kernels.h)
+SEG_PART = 64 * 2                           # floats of chunk candidates per row of isa_seg_begin / isa_seg_claim
 
 
 class InstanceHead:
@@ -551,6 +552,89 @@ class InstanceHead:
                               preds=[p.images(it * n, n) for p in preds],
                               sums=[sums_all[l * 8 * R + it * 8 * n:l * 8 * R + (it + 1) * 8 * n] for l in range(5)]))
         return dict(iters=iters, max_iter=G, merge=merge, x_enc=x_enc, scal=scal)
+
+    # ------------------------------------------------------------------ ground-truth-free inference (ReSeg.segment)
+    def segment(self, x_dec: Act, feats, sem_map: torch.Tensor, max_objects: int, injected_s_t=None, capture=None):
+        """One glimpse point per object, one decoder pass per point, without ground truth: the point of an iteration is
+        the first arg-max of `merge` over the foreground no instance has claimed yet (the arg-max the ground-truth path
+        takes over an instance plane, isa_ins_softmax + isa_row_argmax, without the softmax: it does not move an
+        arg-max); the instance claims the remaining pixels its level-4 prediction calls foreground, and the point.
+        sem_map: fp32 {0,1} [n, h*w].  Returns (labels uint8 [n,h,w], count int32 [n]) in the step's arena.
+        Eval mode only, so the cross branches (backbone features only) run ONCE and their five concat buffers are kept;
+        an iteration rewrites the gated and aux slices (level_main), on buffers the iterations share (the arena cursor
+        is rewound): 20 of the 30 InvertedResidual blocks of a pass, and memory that does not grow with max_objects.
+        Per iteration: the level chain, isa_seg_claim (two launches: labels + next point, then the fold) and at most
+        one 4-byte device-to-host read, taken one iteration late so that the host never waits for the pass it has just
+        queued - a pass in which no image is active changes nothing."""
+        E = self.E
+        assert not E.bn_train and not E.record, "segment() runs in eval mode, without a tape"
+        n, H, W = x_dec.n, x_dec.h, x_dec.w
+        Lp = H * W
+        assert 1 <= max_objects <= 255, "labels are uint8: max_objects must be in 1..255"
+        x_enc = self.stems(x_dec)
+        s = self.spatial_attention(x_enc, sem_map)
+        merge = self.hard_attention_scores(s, sem_map)
+        mask_all = []
+        for f in FACTORS:
+            if f == 1:
+                mask_all.append(sem_map)
+            else:
+                m = E.f32(n * (H // f) * (W // f))
+                L.check(E.lib.isa_pool_target(None, None, L.ptr(sem_map), 1, n, H, W, f, L.ptr(m), n, E.st()),
+                        "isa_pool_target(sem)")
+                mask_all.append(m)
+        if capture is not None:
+            capture.update(x_enc=x_enc, s_sp=s, merge=merge)
+        skips = [feats[4], feats[3], feats[2], feats[1], feats[0]]
+        cats = [self.level_cross(lvl, skips[lvl], {}) for lvl in range(5)]
+        labels = E.arena.alloc((n, H, W), torch.uint8)
+        ints = E.arena.alloc((3 * n + 4,), torch.int32)          # count | active | s_t | the "any image active" word
+        count, active, s_t, any_dev = ints[:n], ints[n:2 * n], ints[2 * n:3 * n], ints[3 * n:3 * n + 1]
+        part = E.f32(n * SEG_PART)
+        L.check(E.lib.isa_seg_begin(L.ptr(sem_map), L.ptr(merge), n, Lp, L.ptr(labels), L.ptr(count), L.ptr(s_t),
+                                    L.ptr(active), L.ptr(any_dev), L.ptr(part), E.st()), "isa_seg_begin")
+        iters = max_objects if injected_s_t is None else len(injected_s_t)
+        assert iters <= 255
+        flags = self._seg_flags(iters + 1) if injected_s_t is None else None
+        if flags is not None:
+            self._seg_flag_read(flags, 0, any_dev)               # flag t: "iteration t has an active image"
+        mark, smark = E.arena.cursor, E.arena.stats_cursor
+        done = 0
+        for t in range(iters):
+            if flags is not None and t >= 1 and not self._seg_flag_wait(flags, t - 1):
+                break                                            # iteration t-1 had nothing to do, so neither has t
+            E.arena.cursor, E.arena.stats_cursor = mark, smark   # the iterations share their buffers
+            pt = s_t if injected_s_t is None else injected_s_t[t]
+            x = pred = None
+            for lvl in range(5):
+                x, pred = self.level_main(lvl, cats[lvl], x, pred, mask_all[lvl], pt, W, False, {})
+                if capture is not None:                          # copies: the next iteration reuses the buffers
+                    capture["it%d.L%d.pred" % (t, lvl)] = Act(pred.buf.clone(), pred.c0, pred.c)
+            if capture is not None:
+                capture["it%d.s_t" % t] = pt.clone()
+            L.check(E.lib.isa_seg_claim(pred.d(), L.ptr(sem_map), L.ptr(merge), L.ptr(pt), L.ptr(labels), L.ptr(count),
+                                        L.ptr(active), L.ptr(s_t), L.ptr(any_dev), L.ptr(part), E.st()), "isa_seg_claim")
+            if flags is not None:
+                self._seg_flag_read(flags, t + 1, any_dev)
+            done = t + 1
+        self.seg_passes = done                                   # decoder passes issued (tests, bench_segment)
+        return labels, count
+
+    def _seg_flags(self, k):
+        """Pinned host words for the stop test and one event per word (reused from call to call)."""
+        st = getattr(self, "_seg_flag_state", None)
+        if st is None or st[0].numel() < k:
+            st = self._seg_flag_state = (torch.zeros(256, dtype=torch.int32).pin_memory(),
+                                         [torch.cuda.Event() for _ in range(256)])
+        return st
+
+    def _seg_flag_read(self, flags, i, any_dev):
+        flags[0][i:i + 1].copy_(any_dev, non_blocking=True)
+        flags[1][i].record(torch.cuda.current_stream())
+
+    def _seg_flag_wait(self, flags, i):
+        flags[1][i].synchronize()
+        return int(flags[0][i]) != 0
 
     @staticmethod
     def order_tensor(selected_idx, max_iter, n):

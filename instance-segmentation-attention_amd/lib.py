@@ -142,6 +142,9 @@ SIGNATURES = {
     "isa_image_ex": [VP, P_T, VP],
     "isa_nchw_to_nhwc": [VP, I32, P_T, VP],
     "isa_nhwc_to_nchw": [P_T, VP, VP],
+    # ground-truth-free instance inference (ReSeg.segment)
+    "isa_seg_begin": [VP, VP, I32, I64, VP, VP, VP, VP, VP, VP, VP],
+    "isa_seg_claim": [P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP],
 }
 
 

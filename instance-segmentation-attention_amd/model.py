@@ -171,3 +171,17 @@ class Model(object):
             raise RuntimeError("predict() needs a model built with use_instance_segmentation=False")
         m(False, images.contiguous())
         return m.net.softmax_nchw(m._last_sem).cpu()                          # softmax over classes (model.py:486)
+
+    def predict_instances(self, images, max_objects=None):
+        """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
+        instance prediction is dead at HEAD).  images: [b,21,h,w] float or raw uint8 RGB [b,h,w,3].  Returns host tensors
+        (fg_prob [b,h,w] = softmax probability of the foreground class, labels uint8 [b,h,w] with 0 = no instance,
+        n_objects int32 [b]); at most max_objects (default: the constructor's max_n_objects) instances per image."""
+        assert len(images.size()) == 4
+        m = self.model
+        if not m.use_instance_seg:
+            raise RuntimeError("predict_instances() needs a model built with use_instance_segmentation=True")
+        m.eval()
+        _, _, labels, n_objects = m.segment(images.contiguous(), self.max_n_objects if max_objects is None else max_objects)
+        fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
+        return fg_prob.cpu(), labels.cpu(), n_objects.cpu()

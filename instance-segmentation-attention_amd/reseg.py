@@ -205,6 +205,54 @@ class ReSeg(nn.Module):
         finally:
             self.engine.record = was
 
+    # ------------------------------------------------------------------ ground-truth-free instance inference
+    def segment(self, x, max_objects=32, *, sem_map=None, injected_s_t=None, capture=None):
+        """(sem_out, sem_argmax, labels, n_objects) for images `x` (either input form of forward) without ground truth:
+        labels uint8 [B,H,W] (0 = background or unexplained foreground, 1..n_objects[b] = instances in the order they
+        were found), n_objects int32 [B], both on the device.  One glimpse point per object - the arg-max of the
+        hard-attention score map over the foreground no instance has claimed yet - and one decoder pass per point;
+        the instance takes the unclaimed pixels its full-resolution prediction calls foreground, and its point
+        (InstanceHead.segment; DESIGN.md "Instance inference").  Stops when every image is explained or after
+        `max_objects` (1..255) instances per image.  Eval mode only.
+        sem_map (fp32 {0,1} [B,H*W]) replaces the predicted foreground; injected_s_t (list of int32 device vectors)
+        replaces the point of iteration t and fixes the iteration count to its length; capture receives `merge` and per
+        iteration `it%d.s_t` and `it%d.L%d.pred`, the names forward uses."""
+        assert not self.training, "segment is for eval mode (running BatchNorm statistics, no Dropout2d)"
+        if not self.use_instance_seg:
+            raise RuntimeError("segment() needs a model built with use_instance_seg=True")
+        max_objects = int(max_objects)
+        if not 1 <= max_objects <= 255:
+            raise ValueError("max_objects must be in 1..255 (labels are uint8), got %d" % max_objects)
+        E, net = self.engine, self.net
+        if x.dtype == torch.uint8:
+            assert x.dim() == 4 and x.shape[3] == 3, "uint8 input must be RGB [B,H,W,3]"
+            B, H, W = x.shape[0], x.shape[1], x.shape[2]
+        else:
+            assert x.dim() == 4 and x.shape[1] == 21, "expects [B,21,H,W] (ImageEx tensor, utils.py:109)"
+            B, H, W = x.shape[0], x.shape[2], x.shape[3]
+        assert H % 16 == 0 and W % 16 == 0
+        dev = self.store.device
+        with torch.no_grad():
+            E.begin(bn_train=False, record=False, key=("segment", tuple(x.shape), x.dtype))
+            if getattr(self, "_weights_dirty", True) and E.packer.entries:
+                E.packer.pack()
+            self._weights_dirty = False
+            x_dec, feats = net.unet(net.input_view(x))
+            sem = net.sem_head(x_dec)
+            self._last_sem = sem
+            sem_out = net.to_nchw(sem)
+            sem_argmax = net.to_nchw(net.argmax_map(sem))
+            if sem_map is None:
+                fg = sem_argmax.reshape(B, -1)
+            else:
+                fg = sem_map.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous()
+                assert fg.shape[1] == H * W, "sem_map must be [B, H*W]"
+            if injected_s_t is not None:
+                injected_s_t = [v.to(device=dev, dtype=torch.int32).contiguous() for v in injected_s_t]
+                assert all(v.numel() == B for v in injected_s_t)
+            labels, count = self.head.segment(x_dec, feats, fg, max_objects, injected_s_t, capture)
+            return sem_out, sem_argmax, labels.clone(), count.clone()    # (the state lives in the step's arena)
+
     # ------------------------------------------------------------------ forward
     def forward(self, training, *_input, selected_idx=None, injected_s_t=None, capture=None, _arena_key=None):
         """reseg.py:106-130.  (x) -> (sem_out, sem_argmax);  (x, sem_onehot[B,K,H,W] i64,

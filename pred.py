@@ -5,6 +5,8 @@ device: isa_image_ex), semantic forward, probability of class 1 up-sampled to th
 cv2.INTER_NEAREST index rule, `> 0.5` -> x255 -> float32 image -> `.convert('P')` -> <name>-fg_mask.png.
 softmax(l)[1] > 0.5 is l1 > l0, i.e. the arg-max map the library already returns (isa_chan_argmax), so no probability
 map is materialised.  `--synthetic` predicts one random image when no file is at hand (nothing ships with the repo).
+`--instances` builds the instance model and also writes <name>-ins_mask.png, <name>-ins_mask_color.png and
+<name>-n_objects.npy as pred_list.py --instances does (ReSeg.segment, at most `--max-objects` instances).
 The reference's hard-coded checkpoint and image paths (pred.py:25-26,112) are flags here."""
 import argparse
 import os
@@ -17,10 +19,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import isa_amd  # noqa: F401,E402
 from isa_amd.model import Model  # noqa: E402
-from pred_list import H, W, nearest_upsample  # noqa: E402
+from pred_list import H, W, nearest_upsample, write_instances  # noqa: E402
 
 
-def predict_file(model, image, out_dir, name):
+def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
     """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask."""
     from PIL import Image
     from isa_amd.data import resize_bilinear
@@ -28,14 +30,20 @@ def predict_file(model, image, out_dir, name):
                                                                # BILINEAR resize (prediction.py:37); ImageEx follows there
     net = model.model
     net.eval()
+    labels = None
     with torch.no_grad():
-        _, sem_arg = net(False, x)                             # arg-max map == (softmax[:, 1] > 0.5)
+        if instances:
+            _, sem_arg, labels, counts = net.segment(x, max_objects)
+        else:
+            _, sem_arg = net(False, x)                         # arg-max map == (softmax[:, 1] > 0.5)
     fg = sem_arg[0, 0].cpu().numpy() > 0.5
     full = nearest_upsample(fg, image.shape[0], image.shape[1])            # prediction.py:47-50
     fg_seg_pred_norm = (full * 255).astype(np.float32)                     # pred.py:117
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, name + '-fg_mask.png')
     Image.fromarray(fg_seg_pred_norm).convert('P').save(path)              # pred.py:122-123
+    if instances:
+        write_instances(out_dir, name, labels[0].cpu().numpy(), int(counts[0]), image.shape[0], image.shape[1])
     return path
 
 
@@ -48,6 +56,8 @@ def main():
     parser.add_argument('--n_workers', type=int, default=1, help='accepted for compatibility')
     parser.add_argument('--dataset', type=str, default='CVPPP')
     parser.add_argument('--synthetic', action='store_true', help='predict one random 530x500 image instead of --image')
+    parser.add_argument('--instances', action='store_true', help='also write -ins_mask.png, -ins_mask_color.png, -n_objects.npy')
+    parser.add_argument('--max-objects', type=int, default=32, help='most instances with --instances (1..255)')
     opt = parser.parse_args()
     assert opt.dataset in ['CVPPP', ]                          # pred.py:29
     assert opt.image or opt.synthetic, "give --image or --synthetic"
@@ -57,8 +67,9 @@ def main():
         from PIL import Image
         assert os.path.isfile(opt.image), 'Image : {} does not exists!'.format(opt.image)
         image, name = np.asarray(Image.open(opt.image).convert('RGB')), os.path.splitext(os.path.basename(opt.image))[0]
-    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=False, load_model_path=opt.model, usegpu=True)
-    path = predict_file(model, image, opt.output, name)
+    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=opt.instances, load_model_path=opt.model,
+                  usegpu=True)
+    path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects)
     print('wrote', path)
 
 

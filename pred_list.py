@@ -5,9 +5,13 @@ outputs/<dataset>/<model dir>-<model name>/<subset>/).
 
 Per image (lib/prediction.py:33-50,116-124): read RGB, resize to 256x256 (bilinear, `image_resizer`), ImageEx +
 standardization (on the device here: isa_image_ex), network forward, softmax > 0.5 (= the arg-max map), nearest-neighbour up-sampling
-to the original size (cv2.INTER_NEAREST index rule), x255, PNG.  The instance outputs of the reference
-(-ins_mask*.png, -n_objects.npy) come from `Prediction.cluster`, which is dead at HEAD (the
-GT-free instance path raises UnboundLocalError, reseg.py:126) and are not produced.
+to the original size (cv2.INTER_NEAREST index rule), x255, PNG.
+`--instances` builds the instance model and also writes the reference's instance outputs (pred_list.py:88-99), the
+files evaluate.py reads: <name>-ins_mask.png (uint8 label map, 0 = no instance, brought to the original size by the
+same nearest-neighbour rule), <name>-ins_mask_color.png (the labels through a fixed palette) and <name>-n_objects.npy.
+The reference fills them from `Prediction.cluster`, which is dead at HEAD (its GT-free instance path
+raises UnboundLocalError, reseg.py:126); here they come from ReSeg.segment - one glimpse point and one decoder pass per
+object, at most `--max-objects` per image.  Without the flag nothing but the two foreground files is written.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -33,6 +37,24 @@ def nearest_upsample(mask, out_h, out_w):
     return mask[ys][:, xs]
 
 
+def label_palette():
+    """256 fixed RGB colours for label maps: 0 is black, the others are spread by a multiplicative hash so that
+    neighbouring labels differ clearly.  No plotting library."""
+    k = np.arange(256, dtype=np.uint32)
+    pal = np.stack([(k * 97 + 59) % 200 + 56, (k * 173 + 101) % 200 + 56, (k * 41 + 7) % 200 + 56], 1).astype(np.uint8)
+    pal[0] = 0
+    return pal
+
+
+def write_instances(d, name, labels, n_objects, out_h, out_w):
+    """The reference's three instance files for one image (pred_list.py:91-99).  labels: uint8 [h,w]."""
+    from PIL import Image
+    full = nearest_upsample(labels, out_h, out_w).astype(np.uint8)
+    Image.fromarray(full).save(os.path.join(d, name + '-ins_mask.png'))
+    Image.fromarray(label_palette()[full]).save(os.path.join(d, name + '-ins_mask_color.png'))
+    np.save(os.path.join(d, name + '-n_objects.npy'), np.int64(n_objects))
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--lst', default='', help='Text file that contains image paths')
@@ -42,6 +64,8 @@ def main():
     parser.add_argument('--output', default='', help='output directory (default: the reference layout under outputs/)')
     parser.add_argument('--batch', type=int, default=16)
     parser.add_argument('--synthetic', type=int, default=0, help='predict N random images instead of --lst')
+    parser.add_argument('--instances', action='store_true', help='also write -ins_mask.png, -ins_mask_color.png, -n_objects.npy')
+    parser.add_argument('--max-objects', type=int, default=32, help='most instances per image with --instances (1..255)')
     opt = parser.parse_args()
     assert opt.dataset in ['CVPPP', ]                    # pred_list.py:26
     assert opt.lst or opt.synthetic, "give --lst or --synthetic N"
@@ -63,7 +87,8 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
 
     from PIL import Image
-    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=False, load_model_path=opt.model, usegpu=True)
+    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=opt.instances, load_model_path=opt.model,
+                  usegpu=True)
     net = model.model
     net.eval()
     done = 0
@@ -71,15 +96,22 @@ def main():
         imgs = [ld() for ld in loaders[s:s + opt.batch]]
         # resize on the device (isa_resize_bilinear_u8, bit-identical to PIL's BILINEAR): one launch per source size
         x = torch.cat([resize_bilinear(torch.from_numpy(im[None]), (H, W)) for im in imgs])   # uint8 [B,H,W,3]; ImageEx follows
-        _, sem_arg = net.infer_graphed(x) if len(imgs) == opt.batch else net(False, x)
+        labels = counts = None
+        if opt.instances:
+            _, sem_arg, labels, counts = net.segment(x, opt.max_objects)
+            labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
+        else:
+            _, sem_arg = net.infer_graphed(x) if len(imgs) == opt.batch else net(False, x)
         # softmax(l)[1] > 0.5 (pred.py:117-121) is l1 > l0: the arg-max map the library already returns
         fg = (sem_arg[:, 0] > 0.5).to(torch.uint8).cpu().numpy()
-        for im, name, m in zip(imgs, names[s:s + opt.batch], fg):
+        for i, (im, name, m) in enumerate(zip(imgs, names[s:s + opt.batch], fg)):
             d = os.path.join(out_dir, name)
             os.makedirs(d, exist_ok=True)
             full = nearest_upsample(m, im.shape[0], im.shape[1]) * 255
             Image.fromarray(im).save(os.path.join(d, name + '.png'))
             Image.fromarray(full.astype(np.uint8)).save(os.path.join(d, name + '-fg_mask.png'))
+            if opt.instances:
+                write_instances(d, name, labels[i], counts[i], im.shape[0], im.shape[1])
             done += 1
     print('wrote %d predictions under %s' % (done, out_dir))
 
