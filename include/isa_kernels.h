@@ -452,6 +452,22 @@ int isa_scale_bc(const isa_tensor* src, const float* s_bc, const isa_tensor* dst
 int isa_sqnorm(const float* g, int64_t n, float scale, float* out /*zeroed*/, void* stream);
 int isa_adadelta(float* p, const float* g, float* sq, float* acc, int64_t n, float lr, float rho, float eps, float wd,
                  const float* sqnorm, float max_norm, float gscale, const float* lr_dev, void* stream);
+/* The other optimizers model.py:145-166 accepts, with the semantics of torch.optim.{Adam, RMSprop, SGD} as constructed
+ * there (L2 weight decay added to the gradient; no amsgrad, no RMSprop momentum or centring, SGD dampening 0 and no
+ * Nesterov), fused with the clip exactly like isa_adadelta: gr = g*gscale*clip + wd*p, state update, parameter write,
+ * clip = min(1, max_norm / (sqrt(sqnorm[0]) + 1e-6)) when max_norm > 0; lr_dev as above.  One streaming launch over n
+ * floats each; p, g and the state ranges must be 16-byte aligned (ISA_EALIGN), state starts zeroed.  Decay rates are
+ * doubles so that 1 - beta is rounded once, as torch rounds it.
+ * isa_adam: `step` (device int32[1], starts 0) counts the updates in device memory - a one-thread launch ahead of the
+ * update increments it and writes aux (device float[4], 16-byte aligned) = {gscale*clip, 1 - beta1^step, 1 - beta2^step,
+ * sqrt(1 - beta2^step)}, which the update reads - so a launch recorded in a hipGraph keeps its bias correction exact. */
+int isa_adam(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int32_t* step, float* aux, int64_t n, float lr,
+             double beta1, double beta2, float eps, float wd, const float* sqnorm, float max_norm, float gscale,
+             const float* lr_dev, void* stream);
+int isa_rmsprop(float* p, const float* g, float* square_avg, int64_t n, float lr, double alpha, float eps, float wd,
+                const float* sqnorm, float max_norm, float gscale, const float* lr_dev, void* stream);
+int isa_sgd(float* p, const float* g, float* momentum_buffer, int64_t n, float lr, double momentum, float wd,
+            const float* sqnorm, float max_norm, float gscale, const float* lr_dev, void* stream);
 
 /* ---- the reference's named attention operators (modules/utils.py; dead at HEAD) --
  * a19 ScaledDotProductAttention.forward (utils.py:316-327) as MultiHeadAttention calls it (utils.py:167-225):

@@ -60,6 +60,7 @@ class IsaPackEntry(C.Structure):
 
 P_T, P_PRO, VP, I32, F = C.POINTER(IsaTensor), C.POINTER(IsaPro), C.c_void_p, C.c_int32, C.c_float
 I64 = C.c_int64
+F64 = C.c_double
 P_BN = C.POINTER(IsaBnBwd)
 
 # name -> argtypes, exactly mirroring include/isa_kernels.h
@@ -132,6 +133,9 @@ SIGNATURES = {
     "isa_scale_bc": [P_T, VP, P_T, I32, VP],
     "isa_sqnorm": [VP, I64, F, VP, VP],
     "isa_adadelta": [VP, VP, VP, VP, I64, F, F, F, F, VP, F, F, VP, VP],
+    "isa_adam": [VP, VP, VP, VP, VP, VP, I64, F, F64, F64, F, F, VP, F, F, VP, VP],
+    "isa_rmsprop": [VP, VP, VP, I64, F, F64, F, F, VP, F, F, VP, VP],
+    "isa_sgd": [VP, VP, VP, I64, F, F64, F, VP, F, F, VP, VP],
     "isa_sdp_attention": [VP, VP, VP, VP, VP, VP, I32, I32, I64, I32, I32, F, I32, I32, I32, VP, I64, I32, VP],
     "isa_sdp_attention_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, I64, I32, I32, F, I32, I32, VP],
     "isa_sdp_scores": [VP, VP, VP, I32, I32, I32, I64, I32, I32, I32, VP],

@@ -46,13 +46,13 @@ class Model(object):
 
     # ------------------------------------------------------------------ training
     def __define_optimizer(self, learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm,
-                           optimizer='Adadelta', criterion='Multi', class_weights=None, optimize_bg=False):
+                           optimizer='Adadelta', criterion='Multi', class_weights=None, optimize_bg=False,
+                           train_cnn=True):
         assert optimizer in ['RMSprop', 'Adam', 'Adadelta', 'SGD']            # model.py:147
-        assert optimizer == 'Adadelta', "the shipped TrainingSettings use Adadelta (training_settings.py:27)"
         # the criterion of __define_criterion (model.py:102-133): CE(weight) and / or Dice(optimize_bg, weight)
         self.trainer = Trainer(self.model, world_size=self.world, lr=learning_rate, weight_decay=weight_decay,
                                clip_grad_norm=clip_grad_norm, criterion=criterion, class_weights=class_weights,
-                               optimize_bg=optimize_bg)
+                               optimize_bg=optimize_bg, optimizer=optimizer, train_cnn=train_cnn)
         self._plateau = dict(best=float('inf'), bad=0, factor=lr_drop_factor, patience=lr_drop_patience)
 
     def __plateau_step(self, val):                   # torch ReduceLROnPlateau(mode='min') semantics, rel 1e-4
@@ -118,7 +118,7 @@ class Model(object):
             vlog = open(os.path.join(model_save_path, 'validation.log'), 'w')
             tlog.write('Epoch,Cost\n'); vlog.write('Epoch,Cost\n')
         self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
-                                criterion_type, class_weights, optimize_bg)
+                                criterion_type, class_weights, optimize_bg, train_cnn)
         best_val_cost = np.inf
         if os.environ.get('ISA_PREFETCH', '1') != '0':      # batch i+1 uploads on a side stream while step i runs
             from .data import DevicePrefetcher

@@ -4,6 +4,8 @@ One step = zero the flat gradient buffer, forward with the backward tape recorde
 attention-head losses assembled on device), hand-written backward, one RCCL all-reduce of the flat
 gradient buffer when world_size > 1, global-norm clip (10) + Adadelta(lr=1,
 weight_decay=1e-3) fused in one kernel over the trainable slice.  No host sync inside the step.
+optimizer= selects Adam, RMSprop or SGD instead (csrc/optim.hip: the same fused clip + decay + update); train_cnn=False
+freezes the backbone: norm, all-reduce and update cover the trainable slice behind the `base.*` prefix only.
 """
 import random
 
@@ -13,10 +15,26 @@ from . import lib as L
 from .parallel import exchange_and_update
 
 
+OPTIMIZERS = ('Adadelta', 'Adam', 'RMSprop', 'SGD')                         # model.py:147
+
+
+def frozen_prefix(store):
+    """Floats of the `base.*` parameters, which open the schema and therefore the trainable slice: [0, n_base)."""
+    base = [n for n in store.names if n.startswith("base.") and n not in store.int_buffers
+            and store.offsets[n] < store.n_train]
+    n_base = sum((store.numel(n) + 3) // 4 * 4 for n in base)
+    rest = [store.offsets[n] for n in store.names if n not in store.int_buffers and not n.startswith("base.")]
+    assert base and max(store.offsets[n] for n in base) < n_base <= min(rest) and n_base % 4 == 0, \
+        "base.* is not a contiguous prefix of the trainable slice"
+    return n_base
+
+
 class Trainer:
     def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6,
-                 criterion='Multi', class_weights=None, optimize_bg=False):
+                 criterion='Multi', class_weights=None, optimize_bg=False, optimizer='Adadelta', train_cnn=True):
+        assert optimizer in OPTIMIZERS, optimizer
         self.model = model
+        self.optimizer, self.train_cnn = optimizer, bool(train_cnn)
         # semantic criterion (model.py:102-133, 255-269): written once into the model's settings buffer, which was
         # allocated with the model - a captured step keeps reading the same device memory
         model.set_criterion(criterion, class_weights, optimize_bg)
@@ -24,9 +42,27 @@ class Trainer:
         self.world = world_size
         self.lr, self.wd, self.clip, self.rho, self.eps = lr, weight_decay, clip_grad_norm, rho, eps
         st = model.store
-        n = st.n_train
-        self.sq = torch.zeros(n, dtype=torch.float32, device=st.device)       # Adadelta square_avg
-        self.acc = torch.zeros(n, dtype=torch.float32, device=st.device)      # Adadelta acc_delta
+        # the updated range [lo, n_train) of the flat buffers.  train_cnn=False (model.py:196-202: requires_grad=False on
+        # model.base): the backbone has no gradient there, so clip_grad_norm_ and the optimizer skip it, decay included
+        self.lo = 0 if self.train_cnn else frozen_prefix(st)
+        n = st.n_train - self.lo
+        zeros = lambda: torch.zeros(n, dtype=torch.float32, device=st.device)
+        # torch.optim's state names; library defaults for what the reference does not set (model.py:150-162)
+        if optimizer == 'Adadelta':
+            self.state = dict(square_avg=zeros(), acc_delta=zeros())
+            self.sq, self.acc = self.state["square_avg"], self.state["acc_delta"]
+        elif optimizer == 'Adam':
+            self.betas, self.adam_eps = (0.9, 0.999), 1e-8
+            # step: the update count, advanced on the device so that a replayed graph keeps its bias correction exact;
+            # aux: the scalars isa_adam's first launch hands its second
+            self.state = dict(exp_avg=zeros(), exp_avg_sq=zeros(), step=torch.zeros(1, dtype=torch.int32, device=st.device))
+            self._adam_aux = torch.zeros(4, dtype=torch.float32, device=st.device)
+        elif optimizer == 'RMSprop':
+            self.alpha, self.rms_eps = 0.99, 1e-8
+            self.state = dict(square_avg=zeros())
+        else:
+            self.momentum = 0.9                                               # model.py:161
+            self.state = dict(momentum_buffer=zeros())
         self.sqnorm = torch.zeros(4, dtype=torch.float32, device=st.device)
         # the step size lives in a device scalar the optimizer kernel reads at run time: a captured hipGraph follows
         # ReduceLROnPlateau (model.py:164,437) without re-capture
@@ -102,21 +138,35 @@ class Trainer:
             self._lr_on_dev = float(self.lr)
 
     def apply_update(self):
-        """all-reduce (world > 1) -> norm of the averaged gradient -> clip + Adadelta: parallel.exchange_and_update
-        owns the ordering (the CPU test drives the same function with stand-in kernels)."""
+        """all-reduce (world > 1) -> norm of the averaged gradient -> clip + the optimizer's update, over the updated range:
+        parallel.exchange_and_update owns the ordering (the CPU test drives the same function with stand-in kernels)."""
         st = self.model.store
         lib = self.model.engine.lib
         self.sqnorm.zero_()
+        lo, n_upd = self.lo, st.n_train - self.lo
+        params, S = st.flat[lo:st.n_train], self.state
+        tail = (L.ptr(self.sqnorm), float(self.clip))       # ..., gscale, lr_dev, stream follow in every entry
 
         def sqnorm_fn(grad, n, gscale):
             L.check(lib.isa_sqnorm(L.ptr(grad), n, gscale, L.ptr(self.sqnorm), L.stream_ptr()), "isa_sqnorm")
 
         def update_fn(grad, n, gscale):
-            L.check(lib.isa_adadelta(L.ptr(st.flat), L.ptr(grad), L.ptr(self.sq), L.ptr(self.acc), n, self.lr, self.rho,
-                                     self.eps, self.wd, L.ptr(self.sqnorm), float(self.clip), gscale, L.ptr(self.lr_dev),
-                                     L.stream_ptr()), "isa_adadelta")
+            p, g, end = L.ptr(params), L.ptr(grad), (gscale, L.ptr(self.lr_dev), L.stream_ptr())
+            if self.optimizer == 'Adadelta':
+                rc = lib.isa_adadelta(p, g, L.ptr(self.sq), L.ptr(self.acc), n, self.lr, self.rho, self.eps, self.wd,
+                                      *tail, *end)
+            elif self.optimizer == 'Adam':
+                rc = lib.isa_adam(p, g, L.ptr(S["exp_avg"]), L.ptr(S["exp_avg_sq"]), L.ptr(S["step"]),
+                                  L.ptr(self._adam_aux), n, self.lr, self.betas[0], self.betas[1], self.adam_eps, self.wd,
+                                  *tail, *end)
+            elif self.optimizer == 'RMSprop':
+                rc = lib.isa_rmsprop(p, g, L.ptr(S["square_avg"]), n, self.lr, self.alpha, self.rms_eps, self.wd,
+                                     *tail, *end)
+            else:
+                rc = lib.isa_sgd(p, g, L.ptr(S["momentum_buffer"]), n, self.lr, self.momentum, self.wd, *tail, *end)
+            L.check(rc, "isa_" + self.optimizer.lower())
 
-        exchange_and_update(st.grad, st.n_train, self.world, sqnorm_fn, update_fn, self.clip)
+        exchange_and_update(st.grad[lo:st.n_train], n_upd, self.world, sqnorm_fn, update_fn, self.clip)
         self.model.mark_weights_dirty()
 
     def train_step(self, x, sem, ins, n_objects, selected_idx=None, injected_s_t=None, arena_key=None):

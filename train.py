@@ -45,6 +45,12 @@ def build_parser():
     parser.add_argument('--optimize-bg', action='store_true', help='Dice over every class, background included')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes, 2..32 (more than 2 needs --semantic-only)')
     parser.add_argument('--semantic-only', action='store_true', help='train the semantic network alone (no instance head)')
+    # the optimizer (training_settings.py: OPTIMIZER, LEARNING_RATE, WEIGHT_DECAY, TRAIN_CNN); the defaults are the shipped
+    # settings.  lr 1.0 is an Adadelta value: Adam and RMSprop want about 1e-3, SGD about 1e-2
+    parser.add_argument('--optimizer', default='Adadelta', choices=['Adadelta', 'Adam', 'RMSprop', 'SGD'])
+    parser.add_argument('--lr', type=float, default=1.0, help='learning rate [Default: 1.0]')
+    parser.add_argument('--weight-decay', type=float, default=0.001, help='L2 weight decay [Default: 0.001]')
+    parser.add_argument('--freeze-cnn', action='store_true', help='do not update the backbone (fit\'s train_cnn=False)')
     return parser
 
 
@@ -69,8 +75,8 @@ def parse_args(argv=None):
 
 def fit_arguments(opt):
     """Model.fit's arguments ahead of the loaders, as the reference's train.py passes them (training_settings.py)."""
-    return (opt.criterion, 0.5, 1.5, 2, 1.0, 0.001, 10.0, 0.5, 25, opt.optimize_bg, 'Adadelta', True, opt.nepochs,
-            opt.class_weights)
+    return (opt.criterion, 0.5, 1.5, 2, opt.lr, opt.weight_decay, 10.0, 0.5, 25, opt.optimize_bg, opt.optimizer,
+            not opt.freeze_cnn, opt.nepochs, opt.class_weights)
 
 
 def main(argv=None):
