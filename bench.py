@@ -10,10 +10,11 @@ inputs resident in HBM.  Workloads:
   train_step : forward + backward + grad all-reduce (N>1) + fused Adadelta   [default when built]
   train_fwd  : ReSeg.forward(True, x, sem, ins, N) — conv backbone + attention mask head, 2 iterations
   infer      : ReSeg(False, x) sem-only inference (configs[2])
-Extra objects: `roofline` (dominant kernel family, HIP-event timed in an instrumented extra step on
-the launch stream; algorithmic bytes = input read once + output written once per conv)
-and `cpu_baseline` (the CPU oracle = port of the reference path, timed on the host cores on a
-bounded sample; rank 0, N=1 only).
+A plain run does what that figure needs and nothing else: set-up, the warm-up steps, the timed steps, the result line.
+`--full` adds, after the timed steps, the measurements that take runs of their own, as extra objects of the same line:
+`roofline` (dominant kernel family, HIP-event timed in an instrumented extra step on the launch stream; algorithmic
+bytes = input read once + output written once per conv) and `cpu_baseline` (the CPU oracle = port of the
+reference path, timed on the host cores on a bounded sample; rank 0, N=1 only; `--no-cpu-baseline` leaves it out).
 `--dump-outputs DIR` (rank 0): after the timed steps, what the last one returned to its caller, as DIR/<name>.npy
 (float32 / float64, at most 64 MB).  Inputs, weights and random draws are seeded, and the last timed step of a training
 workload starts from the initial state, so the same arguments dump the same step.
@@ -95,7 +96,10 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--workload", default="auto", choices=["auto", "train_step", "train_fwd", "infer"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the roofline object "
+                         "(one instrumented eager step) and the cpu_baseline object (the CPU oracle, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline object out")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy, "
@@ -229,7 +233,7 @@ def main():
         res = step()
     sync_all()
     dt = time.perf_counter() - t0
-    if args.dump_outputs and rank == 0:         # before the instrumented step below overwrites the step's buffers
+    if args.dump_outputs and rank == 0:         # before --full's instrumented step below overwrites the step's buffers
         names = dump_outputs(args.dump_outputs, step_outputs(workload, res))
         log("wrote %s under %s" % (", ".join(n + ".npy" for n in names), args.dump_outputs))
     if world > 1:
@@ -252,7 +256,7 @@ def main():
             "launch": "eager" if args.no_graph else "hipGraph replay"},
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline: one extra instrumented step, events on the launch stream -----------------
         E = model.engine
         E.profile = True
@@ -341,6 +345,7 @@ def main():
             out["cpu_baseline"] = {"value": round(cb / cdt, 3), "unit": "images/s", "cores": torch.get_num_threads(),
                                    "kind": "port", "sample": "median of %d reps of the same workload at bs=%d %dx%d fp32 (oracle; "
                                    "fastest %.3f, slowest %.3f images/s)" % (reps, cb, S, S, cb / times[0], cb / times[-1])}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

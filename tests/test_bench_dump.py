@@ -52,6 +52,7 @@ def test_bench_dump_outputs_run(tmp_path, workload, names):
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert "roofline" not in d and "cpu_baseline" not in d         # a plain run measures the headline figure alone
     assert sorted(os.listdir(out)) == [n + ".npy" for n in names]
     total = 0
     for n in names:
@@ -63,6 +64,40 @@ def test_bench_dump_outputs_run(tmp_path, workload, names):
         assert np.load(os.path.join(out, "sem_out.npy")).shape == (2, 2, 64, 64)
     else:
         assert np.load(os.path.join(out, "head_losses.npy")).shape == (4,)
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_roofline_and_cpu_baseline():
+    """--full: the same result line, with the objects whose measurements take runs of their own after the timed steps
+    (the instrumented eager step and the CPU oracle)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+           "--size", "64", "--full"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    roof = d["roofline"]
+    assert roof["launches_per_step"] > 0 and roof["achieved"] > 0 and roof["avg_launch_us"] > 0
+    cpu = d["cpu_baseline"]
+    assert cpu["value"] > 0 and cpu["unit"] == "images/s" and cpu["kind"] == "port"
+    r = subprocess.run(cmd + ["--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert "roofline" in d and "cpu_baseline" not in d
+
+
+def test_bench_options():
+    """--full is off by default, and --no-cpu-baseline keeps its meaning under it (argument parsing alone: no GPU)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--no-cpu-baseline" in r.stdout and "--dump-outputs" in r.stdout
 
 
 @pytest.mark.gpu

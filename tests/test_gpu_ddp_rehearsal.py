@@ -20,7 +20,7 @@ def test_two_ranks_one_gpu_bench_line():
     env = dict(os.environ, ISA_DIST_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--size", "64", "--no-cpu-baseline"]
+           "--batch", "2", "--size", "64", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -28,3 +28,4 @@ def test_two_ranks_one_gpu_bench_line():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 4 and d["config"]["parallelism"] == "dp2"
     assert d["value"] > 0 and d["scaling"] == "weak"
+    assert d["roofline"]["launches_per_step"] > 0                  # --full: rank 0's instrumented step, collective-free
