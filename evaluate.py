@@ -9,7 +9,10 @@ pair (O(HW) instead of O(G*P*HW)); tests/test_evaluate.py checks it against the 
 
 Differences, all additive: `--data_root` (the reference hard-codes ../data), and `--fg_only` to score the
 foreground masks that pred_list.py writes when no instance outputs exist (the reference skips such images: its
-instance clustering is dead at HEAD, see pred_list.py)."""
+instance clustering is dead at HEAD, see pred_list.py), and `--device` to score every image through the HIP kernels
+behind ReSeg.score_instances (isa_label_pair_hist, isa_instance_scores) instead of numpy: the same walk, the same
+three lines.  Two things differ there: label ids must fit the kernels' histogram (at most 256 ids a map and 16384 id
+pairs, an error otherwise), and an image whose prediction holds no object scores SBD 0.0 where `calc_bd` raises."""
 import argparse
 import os
 
@@ -61,8 +64,37 @@ def calc_sbd(ins_seg_gt, ins_seg_pred):
     return min(calc_bd(ins_seg_gt, ins_seg_pred), calc_bd(ins_seg_pred, ins_seg_gt))
 
 
-def evaluate_cvppp(pred_dir, data_root, fg_only=False):
-    """Walk the validation list like evaluate.py:59-111.  Returns (sbds, dics, fg_dices, names_scored)."""
+def device_scores(map_a, map_b, n_a=None, n_b=None):
+    """The eight scores of include/isa_kernels.h (isa_instance_scores) for ONE pair of integer label maps, computed on
+    the GPU: [best Dice a->b, best Dice b->a, SBD, objects in a, objects in b, |n_a - n_b|, foreground Dice, 0]."""
+    import torch
+    import isa_amd  # noqa: F401
+    from isa_amd import lib as L
+    a, b = np.asarray(map_a).reshape(-1), np.asarray(map_b).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError("label maps differ in size: %s vs %s" % (np.shape(map_a), np.shape(map_b)))
+    na, nb = int(a.max()) + 1, int(b.max()) + 1
+    if a.min() < 0 or b.min() < 0 or na > 256 or nb > 256 or na * nb > 16384:
+        raise ValueError("label ids 0..%d and 0..%d: --device counts at most 256 ids a map and 16384 id pairs "
+                         "(isa_label_pair_hist)" % (na - 1, nb - 1))
+    pad = -a.size % 4                    # the kernel reads 4 pixels per load; (0, 0) pixels change none of the scores
+    dev = lambda m: torch.from_numpy(np.concatenate([m.astype(np.uint8), np.zeros(pad, np.uint8)])).cuda()
+    cnt = lambda v: None if v is None else torch.tensor([int(v)], dtype=torch.int32, device="cuda")
+    ta, tb, ca, cb = dev(a), dev(b), cnt(n_a), cnt(n_b)
+    hist = torch.empty(na * nb, dtype=torch.int32, device="cuda")
+    oob = torch.empty(1, dtype=torch.int32, device="cuda")
+    out = torch.empty(8, dtype=torch.float64, device="cuda")
+    lib, st = L.lib(), L.stream_ptr()
+    L.check(lib.isa_label_pair_hist(L.ptr(ta), L.ptr(tb), 1, ta.numel(), na, nb, L.ptr(hist), L.ptr(oob),
+                                    L.HIST_AGGREGATE, st), "isa_label_pair_hist")
+    L.check(lib.isa_instance_scores(L.ptr(hist), 1, na, nb, L.ptr(ca), L.ptr(cb), L.ptr(out), st), "isa_instance_scores")
+    assert int(oob.cpu()[0]) == 0
+    return out.cpu().numpy()
+
+
+def evaluate_cvppp(pred_dir, data_root, fg_only=False, device=False):
+    """Walk the validation list like evaluate.py:59-111.  Returns (sbds, dics, fg_dices, names_scored).
+    device=True: every image is scored by device_scores."""
     from PIL import Image
     names = np.atleast_1d(np.loadtxt(os.path.join(data_root, 'metadata/CVPPP/validation_image_paths.txt'),
                                      dtype='str', delimiter=','))
@@ -84,11 +116,16 @@ def evaluate_cvppp(pred_dir, data_root, fg_only=False):
             n_objects_pred = np.load(base + '-n_objects.npy')    # plain array: allow_pickle stays False
             ins_seg_gt = np.array(Image.open(os.path.join(img_dir, stem + '_label.png')))
             ins_seg_pred = np.array(Image.open(base + '-ins_mask.png'))
-            sbds.append(calc_sbd(ins_seg_gt, ins_seg_pred))
-            dics.append(calc_dic(n_objects_gt, n_objects_pred))
+            if device:
+                sc = device_scores(ins_seg_gt, ins_seg_pred, n_objects_gt, n_objects_pred)
+                sbds.append(float(sc[2]))
+                dics.append(int(sc[5]))
+            else:
+                sbds.append(calc_sbd(ins_seg_gt, ins_seg_pred))
+                dics.append(calc_dic(n_objects_gt, n_objects_pred))
         fg_seg_gt = np.array(Image.open(os.path.join(img_dir, stem + '_fg.png'))) == 1
         fg_seg_pred = np.array(Image.open(base + '-fg_mask.png')) == 255
-        fg_dices.append(calc_dice(fg_seg_gt, fg_seg_pred))
+        fg_dices.append(float(device_scores(fg_seg_gt, fg_seg_pred)[6]) if device else calc_dice(fg_seg_gt, fg_seg_pred))
         scored.append(name)
     return sbds, dics, fg_dices, scored
 
@@ -99,9 +136,10 @@ def main():
     parser.add_argument('--dataset', type=str, required=True, help='Name of the dataset which is "CVPPP"')
     parser.add_argument('--data_root', default='../data', help='where metadata/ and raw/ live (reference: ../data)')
     parser.add_argument('--fg_only', action='store_true', help='score foreground masks only (no instance outputs)')
+    parser.add_argument('--device', action='store_true', help='score every image on the GPU (the HIP scoring kernels)')
     opt = parser.parse_args()
     assert opt.dataset in ['CVPPP', ]
-    sbds, dics, fg_dices, scored = evaluate_cvppp(opt.pred_dir, opt.data_root, opt.fg_only)
+    sbds, dics, fg_dices, scored = evaluate_cvppp(opt.pred_dir, opt.data_root, opt.fg_only, opt.device)
     if not opt.fg_only:
         print('MEAN SBD     : ', np.mean(sbds))
         print('MEAN |DIC|   : ', np.mean(dics))

@@ -390,6 +390,41 @@ int isa_seg_begin(const float* sem, const float* merge, int32_t n, int64_t L, ui
 int isa_seg_claim(const isa_tensor* pred, const float* sem, const float* merge, const int32_t* s_t, uint8_t* labels,
                   int32_t* count, int32_t* active, int32_t* s_next, int32_t* any_active, float* part, void* stream);
 
+/* ---- scoring instance predictions on the device (code/evaluate.py:18-56: calc_dic, calc_dice, calc_bd, calc_sbd) ------
+ * Every entry checks all its arguments before it launches anything (ISA_EINVAL / ISA_EALIGN); n <= 65535.
+ * isa_labels_from_planes: ground-truth instance planes -> uint8 label map [n, hw].  The label of a pixel is 1 + the
+ *   smallest plane index whose value is non-zero, 0 if there is none; where planes overlap the FIRST plane gets the pixel.
+ *   form ISA_PLANES_U8_NHWK: uint8 [n,h,w,k] (the compact targets); ISA_PLANES_I64_NKHW: int64 [n,k,h,w] (the
+ *   reference's, 8-byte aligned); ISA_PLANES_F32_NKHW: fp32 [n,k,h,w] (k = 1: the sem_argmax map the model returns; NaN
+ *   counts as non-zero).  1 <= k <= 255.
+ * isa_label_pair_hist: hist[i][p][q] (int32 [n][na][nb]) = number of pixels of image i with a == p and b == q, for the
+ *   uint8 maps a, b [n, L].  A pixel with a >= na or b >= nb is counted in oob[i] (int32 [n]) instead.  The entry zeroes
+ *   hist and oob on the stream itself: nothing has to be cleared by the caller.  1 <= na, nb <= 256, na * nb <= 16384 (the
+ *   64 KiB of LDS counters of a workgroup); L % 4 == 0; a, b, hist, oob 4-byte aligned (16-byte aligned maps with
+ *   L % 16 == 0 are read 16 pixels per load).  A row is shared by up to ISA_ROW_CHUNKS workgroups that add their non-zero
+ *   counters with integer atomics: the result does not depend on the order in which they run.  mode ISA_HIST_AGGREGATE
+ *   counts a wave's dominant pair once per wave and merges a lane's equal consecutive pairs; ISA_HIST_NAIVE is one LDS
+ *   atomic per pixel, kept as the figure to measure the former against (scripts/bench_score.py).  Same result.
+ * isa_instance_scores: out[i][0..7] (double, 8-byte aligned) from hist[i].  An object of a map is a non-zero label with a
+ *   non-empty row (map a) or column (map b) of hist, as np.unique in evaluate.py sees it; dice[p][q] = 2 hist[p][q] /
+ *   (size_a[p] + size_b[q]), the sizes counting the pixels shared with the other map's label 0 too.
+ *     0: best Dice a -> b, the mean over a's objects of the max over b's objects     1: best Dice b -> a
+ *     2: SBD = fmin(0, 1)          3, 4: objects present in a, in b          5: |n_a[i] - n_b[i]|
+ *     6: foreground Dice 2 |a != 0 & b != 0| / (|a != 0| + |b != 0|) (calc_dice when na == nb == 2)          7: 0
+ *   n_a / n_b (int32 [n]): the reported object counts; NULL: the number of objects present.
+ *   Empty maps: 0 is NaN when a has no object and 0.0 when a has objects and b has none, 1 mirrors it; so SBD is NaN only
+ *   when both maps are empty (calc_sbd: min(nan, nan)) and 0.0 when exactly one is.  THAT case differs from the
+ *   reference: its calc_bd raises ValueError (np.max of an empty list), which a kernel cannot.  6 is NaN for two empty
+ *   maps, where calc_dice divides by zero. */
+enum { ISA_PLANES_U8_NHWK = 0, ISA_PLANES_I64_NKHW = 1, ISA_PLANES_F32_NKHW = 2 };
+enum { ISA_HIST_AGGREGATE = 0, ISA_HIST_NAIVE = 1 };
+int isa_labels_from_planes(const void* planes, int32_t form, int32_t n, int32_t k, int64_t hw, uint8_t* labels,
+                           void* stream);
+int isa_label_pair_hist(const uint8_t* a, const uint8_t* b, int32_t n, int64_t L, int32_t na, int32_t nb, int32_t* hist,
+                        int32_t* oob, int32_t mode, void* stream);
+int isa_instance_scores(const int32_t* hist, int32_t n, int32_t na, int32_t nb, const int32_t* n_a, const int32_t* n_b,
+                        double* out, void* stream);
+
 /* ---- losses and hand-derived backward of the head (the reference relies on autograd) ------------
  * isa_head_loss: attenet2.py:239-290 on device (no host sync): per-level gradient coefficients,
  * REINFORCE advantage with the EMA baseline (device scalar), and scal[0..3] += {ins_cost without the

@@ -16,6 +16,8 @@ F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_LEAKY, ACT_TANH = 0, 1, 2, 3, 4
 IN_1X1, IN_3X3, IN_GATHER2 = 0, 1, 2
 OUT_PLAIN, OUT_SHUFFLE2 = 0, 1
+PLANES_U8_NHWK, PLANES_I64_NKHW, PLANES_F32_NKHW = 0, 1, 2
+HIST_AGGREGATE, HIST_NAIVE = 0, 1
 
 _ERR = {-1: "ISA_EINVAL", -2: "ISA_EALIGN", -3: "ISA_EDTYPE", -4: "ISA_ELAUNCH", -5: "ISA_ENOMEM"}
 
@@ -149,6 +151,10 @@ SIGNATURES = {
     # ground-truth-free instance inference (ReSeg.segment)
     "isa_seg_begin": [VP, VP, I32, I64, VP, VP, VP, VP, VP, VP, VP],
     "isa_seg_claim": [P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP],
+    # scoring instance predictions (ReSeg.score_instances)
+    "isa_labels_from_planes": [VP, I32, I32, I32, I64, VP, VP],
+    "isa_label_pair_hist": [VP, VP, I32, I64, I32, I32, VP, VP, I32, VP],
+    "isa_instance_scores": [VP, I32, I32, I32, VP, VP, VP, VP],
 }
 
 

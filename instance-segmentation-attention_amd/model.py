@@ -33,6 +33,8 @@ class Model(object):
         self.__load_weights()
         self.trainer = None
         self.lr_scheduler = None
+        # fit(): also segment and score every validation minibatch (SBD, |DiC|, FG Dice -> validation_scores.log)
+        self.val_scores = False
 
     def __load_weights(self):
         if self.load_model_path != '':
@@ -88,6 +90,8 @@ class Model(object):
                     sem, _ = self.model.net.collate_targets(sem, ins)
                 costs = self.model.sem_costs(sem)         # the reference logs CE / Dice in validation too (model.py:255-269)
                 row.update(self.__sem_row(costs))
+                if self.val_scores and self.use_instance_segmentation:
+                    row['scores'] = self.__score_batch(batch, self.max_n_objects, check=False)
             return row
         row = self.__sem_row(out['sem'])
         h = out['head']
@@ -95,6 +99,30 @@ class Model(object):
             row.update({'INS Cost': h[0] + float('nan'), 'Criterion': h[1].clone(), 'ins_ce_loss': h[2].clone(),
                         'ins_dice_loss': h[3].clone()})
         return row
+
+    def __score_batch(self, batch, max_objects, check):
+        """segment() + score_instances() of one loader batch: the device tensor [B,8], and the number of pixels whose
+        label the histograms do not hold (a device scalar: the callers read it with their one copy and raise)."""
+        images, sem, ins, n_objects = batch
+        m = self.model
+        _, sem_arg, labels, count = m.segment(images.contiguous(), max_objects)
+        out = m.score_instances(labels, count, ins, n_objects, sem_arg, sem, max_objects=max_objects, check=check)
+        return out, m.last_score_oob.sum()
+
+    @staticmethod
+    def __refuse_oob(n_oob):
+        if n_oob:
+            raise ValueError("%d pixels carry a label outside the score histograms (ReSeg.score_instances: at most 256 ids "
+                             "a side and 16384 pairs)" % n_oob)
+
+    @staticmethod
+    def __score_means(per_image):
+        """Means of SBD, |DiC| and FG Dice over the images whose value is not NaN, as evaluate.py's main takes them over
+        the images it scored; device tensors (means [3], number of NaN images of the SBD column)."""
+        cols = per_image[:, [2, 5, 6]]
+        ok = ~torch.isnan(cols)
+        means = torch.where(ok, cols, torch.zeros_like(cols)).sum(0) / ok.sum(0)
+        return means, (~ok[:, 0]).sum()
 
     def __sem_row(self, costs):
         """Only the terms the criterion computes, as the reference's out_metrics (model.py:255-269)."""
@@ -111,12 +139,16 @@ class Model(object):
             train_loader, test_loader, model_save_path, debug):
         assert criterion_type in ['CE', 'Dice', 'Multi']                       # model.py:364
         main = self.rank == 0                   # only rank 0 writes logs and checkpoints (parallel.py: policy)
-        tlog = vlog = None
+        tlog = vlog = slog = None
+        scoring = bool(self.val_scores) and self.use_instance_segmentation
         if main:
             os.makedirs(model_save_path, exist_ok=True)
             tlog = open(os.path.join(model_save_path, 'training.log'), 'w')
             vlog = open(os.path.join(model_save_path, 'validation.log'), 'w')
             tlog.write('Epoch,Cost\n'); vlog.write('Epoch,Cost\n')
+            if scoring:
+                slog = open(os.path.join(model_save_path, 'validation_scores.log'), 'w')
+                slog.write('Epoch,SBD,DiC,FG Dice\n')
         self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
                                 criterion_type, class_weights, optimize_bg, train_cnn)
         best_val_cost = np.inf
@@ -157,8 +189,22 @@ class Model(object):
             if main:
                 tlog.write('{},{}\n'.format(epoch, train_cost)); vlog.write('{},{}\n'.format(epoch, val_cost))
                 tlog.flush(); vlog.flush()
+            if scoring:
+                # per-epoch means over this rank's validation images, then over the ranks, as the costs are
+                rows = [r['scores'][0] for r in va]
+                means = [float('nan')] * 3
+                if rows:
+                    got = torch.cat([self.__score_means(torch.cat(rows))[0],
+                                     torch.stack([r['scores'][1] for r in va]).sum().double().view(1)]).tolist()
+                    self.__refuse_oob(int(got[3]))
+                    means = got[:3]
+                means = [parallel.mean_over_ranks(v, self.world) for v in means]
+                if main:
+                    slog.write('{},{},{},{}\n'.format(epoch, *means)); slog.flush()
         if main:
             tlog.close(); vlog.close()
+            if slog is not None:
+                slog.close()
 
     # ------------------------------------------------------------------ inference (model.py:466-499)
     def predict(self, images):
@@ -185,3 +231,30 @@ class Model(object):
         _, _, labels, n_objects = m.segment(images.contiguous(), self.max_n_objects if max_objects is None else max_objects)
         fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
+
+    def evaluate(self, loader, max_objects=None):
+        """Scores of ground-truth-free instance inference over a loader of (images, sem, ins, n_objects) batches, either
+        target form: every batch is segmented (ReSeg.segment, at most max_objects instances per image; default: the
+        constructor's max_n_objects) and scored on the device (ReSeg.score_instances); one device-to-host copy at the end.
+        Returns {'SBD', '|DiC|', 'FG Dice', 'n_images', 'n_skipped', 'per_image'}: per_image is the float64 ndarray
+        [N,8] of score_instances, the three means are taken over the images whose value is not NaN (evaluate.py's main
+        averages the images it scored), n_skipped counts the images whose SBD is NaN (neither map holds an object).
+        It scores what the loader yields on THIS rank; reducing over ranks is left to the caller."""
+        m = self.model
+        if not m.use_instance_seg:
+            raise RuntimeError("evaluate() needs a model built with use_instance_segmentation=True")
+        m.eval()
+        max_objects = self.max_n_objects if max_objects is None else max_objects
+        rows = [self.__score_batch(b, max_objects, check=False) for b in loader]
+        if not rows:
+            nan = float('nan')
+            return {'SBD': nan, '|DiC|': nan, 'FG Dice': nan, 'n_images': 0, 'n_skipped': 0,
+                    'per_image': np.zeros((0, 8))}
+        per_image = torch.cat([r[0] for r in rows])
+        means, skipped = self.__score_means(per_image)
+        n_oob = torch.stack([r[1] for r in rows]).sum()
+        host = torch.cat([per_image.reshape(-1), means, skipped.double().view(1), n_oob.double().view(1)]).cpu().numpy()
+        self.__refuse_oob(int(host[-1]))
+        per = host[:-5].reshape(-1, 8)
+        return {'SBD': float(host[-5]), '|DiC|': float(host[-4]), 'FG Dice': float(host[-3]), 'n_images': per.shape[0],
+                'n_skipped': int(host[-2]), 'per_image': per}

@@ -253,6 +253,101 @@ class ReSeg(nn.Module):
             labels, count = self.head.segment(x_dec, feats, fg, max_objects, injected_s_t, capture)
             return sem_out, sem_argmax, labels.clone(), count.clone()    # (the state lives in the step's arena)
 
+    # ------------------------------------------------------------------ scoring instance predictions on the device
+    def _label_map(self, planes, what):
+        """uint8 label map [B, H*W] of ground-truth planes in either form forward() takes (isa_labels_from_planes)."""
+        E = self.engine
+        t = planes.to(self.store.device).contiguous()
+        assert t.dim() == 4, "%s must be uint8 [B,H,W,K] or int64 [B,K,H,W]" % what
+        if t.dtype == torch.uint8:
+            (n, h, w, k), form = t.shape, L.PLANES_U8_NHWK
+        elif t.dtype == torch.int64:
+            (n, k, h, w), form = t.shape, L.PLANES_I64_NKHW
+        elif t.dtype == torch.float32:
+            (n, k, h, w), form = t.shape, L.PLANES_F32_NKHW
+        else:
+            raise TypeError("%s: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % (what, t.dtype))
+        out = torch.empty((n, h * w), dtype=torch.uint8, device=t.device)
+        L.check(E.lib.isa_labels_from_planes(L.ptr(t), form, n, k, h * w, L.ptr(out), E.st()), "isa_labels_from_planes")
+        return out, k
+
+    def _pair_scores(self, a, b, na, nb, n_a, n_b, oob):
+        """[B,8] scores (isa_instance_scores) of the uint8 maps a, b [B, L]; the out-of-range counts go to oob [B]."""
+        E = self.engine
+        n, Lp = a.shape
+        if not (1 <= na <= 256 and 1 <= nb <= 256 and na * nb <= 16384):
+            raise ValueError("label ids: %d x %d counters; each side at most 256 and the product at most 16384" % (na, nb))
+        hist = torch.empty((n, na, nb), dtype=torch.int32, device=a.device)
+        out = torch.empty((n, 8), dtype=torch.float64, device=a.device)
+        L.check(E.lib.isa_label_pair_hist(L.ptr(a), L.ptr(b), n, Lp, na, nb, L.ptr(hist), L.ptr(oob), L.HIST_AGGREGATE,
+                                          E.st()), "isa_label_pair_hist")
+        L.check(E.lib.isa_instance_scores(L.ptr(hist), n, na, nb, L.ptr(n_a), L.ptr(n_b), L.ptr(out), E.st()),
+                "isa_instance_scores")
+        return out
+
+    def score_instances(self, labels, n_objects, ins_target, n_target, sem_argmax=None, sem_target=None, *,
+                        max_objects=255, check=True):
+        """Scores of predicted label maps (segment's `labels` uint8 [B,H,W] and `n_objects` int32 [B]) against the ground
+        truth, on the device: a double tensor [B,8] whose columns are
+          0 best Dice ground truth -> prediction, 1 best Dice prediction -> ground truth, 2 Symmetric Best Dice,
+          3 objects present in the ground truth, 4 objects present in the prediction, 5 |n_target - n_objects| (|DiC|),
+          6 foreground Dice, 7 zero
+        (calc_bd / calc_sbd / calc_dic / calc_dice of evaluate.py, from one joint histogram per image: isa_label_pair_hist,
+        isa_instance_scores).  ins_target: the instance planes in either form forward() takes (uint8 [B,H,W,K] or int64
+        [B,K,H,W]); where planes overlap the first one gets the pixel.  n_target: the ground-truth object counts [B] or
+        [B,1].  Column 6 compares sem_argmax (segment's fp32 [B,1,H,W]) with the foreground of sem_target (uint8 [B,H,W] or
+        one-hot int64 [B,C,H,W]) when both are given, and the foregrounds of the two label maps otherwise.
+        max_objects: the largest label the prediction can hold (segment's cap).  (K + 1) * (max_objects + 1) counters must
+        not exceed 16384; a pixel whose label lies outside is not scored, and with check=True (one device read, the only
+        host synchronisation of the call) that raises ValueError - there is no other path for such maps; with check=False
+        the counts stay on the device in self.last_score_oob (int32 [2,B]) for the caller to read.
+        Empty maps: column 0 is NaN for a ground truth without objects and 0.0 when only the prediction has none (column
+        1 mirrors it), so SBD is NaN when both are empty and 0.0 when one is - where evaluate.calc_bd raises ValueError,
+        which the device cannot; column 6 is NaN when both foregrounds are empty."""
+        dev = self.store.device
+        with torch.no_grad():
+            labels = labels.to(dev)
+            assert labels.dtype == torch.uint8 and labels.dim() == 3, "labels: uint8 [B,H,W]"
+            B = labels.shape[0]
+            pred = labels.contiguous().view(B, -1)
+            if pred.shape[1] % 4:
+                raise ValueError("H*W must be a multiple of 4, got %d" % pred.shape[1])
+            gt, k = self._label_map(ins_target, "ins_target")
+            assert tuple(gt.shape) == tuple(pred.shape), "ins_target and labels differ in size"
+            n_pred = n_objects.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            n_gt = n_target.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            assert n_pred.numel() == B and n_gt.numel() == B
+            oob = torch.empty((2, B), dtype=torch.int32, device=dev)
+            out = self._pair_scores(gt, pred, k + 1, int(max_objects) + 1, n_gt, n_pred, oob[0])
+            limits = ["ground-truth labels 0..%d, predicted labels 0..%d" % (k, int(max_objects))]
+            if sem_argmax is not None and sem_target is not None:
+                fg_pred, _ = self._label_map(sem_argmax.to(dev).float().reshape(B, 1, 1, -1), "sem_argmax")
+                st = sem_target.to(dev).contiguous()
+                if st.dtype == torch.uint8:
+                    assert st.dim() == 3, "compact sem_target: uint8 [B,H,W]"
+                    fg_gt, nc = st.view(B, -1), self.n_classes
+                else:
+                    assert st.dtype == torch.int64 and st.dim() == 4, "sem_target: one-hot int64 [B,C,H,W]"
+                    nc = st.shape[1]
+                    fg_gt = torch.empty((B, st.shape[2] * st.shape[3]), dtype=torch.uint8, device=dev)
+                    L.check(self.engine.lib.isa_labels_from_onehot(L.ptr(st), B, nc, fg_gt.shape[1], L.ptr(fg_gt), None,
+                                                                   self.engine.st()), "isa_labels_from_onehot")
+                assert tuple(fg_gt.shape) == tuple(pred.shape) == tuple(fg_pred.shape)
+                sem = self._pair_scores(fg_gt, fg_pred, nc, 2, None, None, oob[1])
+                out[:, 6].copy_(sem[:, 6])
+                limits.append("semantic classes 0..%d" % (nc - 1))
+            else:
+                oob[1].zero_()
+            self.last_score_oob = oob                     # for callers that pass check=False and read it with their own copy
+            if check:
+                bad = oob.cpu()
+                for row, limit in zip(bad, limits):
+                    if int(row.sum()):
+                        raise ValueError("score_instances: %d pixels of images %s carry a label outside the histogram (%s); "
+                                         "at most 256 ids a side and 16384 pairs are counted"
+                                         % (int(row.sum()), torch.nonzero(row).view(-1).tolist(), limit))
+            return out
+
     # ------------------------------------------------------------------ forward
     def forward(self, training, *_input, selected_idx=None, injected_s_t=None, capture=None, _arena_key=None):
         """reseg.py:106-130.  (x) -> (sem_out, sem_argmax);  (x, sem_onehot[B,K,H,W] i64,

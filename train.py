@@ -51,6 +51,8 @@ def build_parser():
     parser.add_argument('--lr', type=float, default=1.0, help='learning rate [Default: 1.0]')
     parser.add_argument('--weight-decay', type=float, default=0.001, help='L2 weight decay [Default: 0.001]')
     parser.add_argument('--freeze-cnn', action='store_true', help='do not update the backbone (fit\'s train_cnn=False)')
+    parser.add_argument('--val-scores', action='store_true', help='also segment and score every validation minibatch: '
+                        'per-epoch SBD, |DiC| and FG Dice in <out>/validation_scores.log (Model.val_scores)')
     return parser
 
 
@@ -93,6 +95,7 @@ def main(argv=None):
     torch.manual_seed(parallel.rank_seed(SEED, rank))             # instance order, glimpse points, dropout: per rank
     model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=not opt.semantic_only,
                   load_model_path=opt.model, usegpu=True, dtype=torch.bfloat16 if opt.dtype == 'bf16' else torch.float32)
+    model.val_scores = opt.val_scores
     # every rank draws its own shard of each global batch (weights start identical: the model seed is not per rank)
     train_loader = SyntheticLoader(opt.iters_per_epoch, per_rank, opt.size, opt.size, seed=parallel.rank_seed(SEED, rank),
                                    compact=opt.compact_targets, n_classes=opt.n_classes)
