@@ -623,6 +623,58 @@ int64_t isa_resize_bilinear_ws_bytes(int32_t n, int32_t h0, int32_t w0, int32_t 
 int isa_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t c, uint8_t* dst,
                            int32_t h, int32_t w, void* ws, int64_t ws_bytes, void* stream);
 
+/* Lanczos image resize: the two `img.resize(size, Image.ANTIALIAS)` of the reference's random_resolution
+ * (code/lib/preprocess.py:443-454; ANTIALIAS was Pillow's name for LANCZOS = 1) for uint8 [n,h0,w0,c] (c <= 4) ->
+ * [n,h,w,c], out of place, bit-identical to Pillow: the same Resample.c passes as the bilinear entry with the filter
+ * sinc(x) * sinc(x/3), support 3.  The coefficient tables are computed on the HOST inside the call, in IEEE double with
+ * libm's sin (the device's sin may differ from it in the last bit, which now and then flips a 22-bit rounding), copied
+ * into ws on the stream, and the call returns only once that copy has been made.  ws: device scratch of the *bytes that
+ * isa_resize_lanczos_ws_bytes reports (a status like every entry but the bilinear one's; ISA_EINVAL for sizes the
+ * resize would refuse), 4-byte aligned; ISA_ENOMEM when smaller.  Every size at most 65535. */
+int isa_resize_lanczos_ws_bytes(int32_t n, int32_t h0, int32_t w0, int32_t c, int32_t h, int32_t w, int64_t* bytes);
+int isa_resize_lanczos_u8(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t c, uint8_t* dst,
+                          int32_t h, int32_t w, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- photometric augmentations: the four of AlignCollate.__preprocess that work pixel by pixel
+ * (code/lib/dataset.py:147-155,271-281), which the reference runs as up to seven PIL passes per image:
+ *   colour jitter  utils.py:58-59 -> torchvision ColorJitter(0.4, 0.4, 0.4, 0.2): ImageEnhance.Brightness / Contrast /
+ *                  Color and the HSV hue shift, in a drawn order
+ *   gamma          preprocess.py:405-439 Image.point over a 256-entry table
+ *   channel swap   preprocess.py:381-401 img_np[:, :, np.random.choice([0, 1, 2], 3, True)]
+ *   grayscale      utils.py:62-63 -> RandomGrayscale: convert('L') copied to three channels
+ * Here one pass: every pixel is read once, taken through its image's program in registers - jitter ops in the listed
+ * order -> LUT -> channel map -> grayscale, each stage rounding to uint8 exactly where Pillow holds a uint8 image - and
+ * written once.  Bit-identical to the installed Pillow (tests/photometric_np.py, tests/test_photometric_ref.py).
+ *   brightness  blend(0, x, f);  contrast  blend(m, x, f), m = int(mean(L) + 0.5) of the image as it stands when the op
+ *   is applied;  saturation  blend(L, x, f);  blend(d, x, f) = float32 d + f * (x - d), clipped to [0, 255], truncated;
+ *   L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.
+ *   hue  RGB -> HSV (Pillow's mix of float and double), H += hue_shift mod 256, HSV -> RGB.  The caller computes
+ *   hue_shift = int(hue_factor * 255) & 255.  For hue_factor >= 0 that is numpy's `np_h += np.uint8(hue_factor * 255)`
+ *   of torchvision's PIL path; the uint8 cast of a NEGATIVE float is platform-defined in numpy, so for those this
+ *   definition (two's-complement wrap) is this library's own.
+ * A program lists each op at most once; op[k] outside the four codes is skipped, chan[] entries above 2 read as 2. */
+#define ISA_PHOTO_BRIGHTNESS 0
+#define ISA_PHOTO_CONTRAST   1
+#define ISA_PHOTO_SATURATION 2
+#define ISA_PHOTO_HUE        3
+typedef struct {
+    int32_t n_ops;        /* 0..4 jitter ops, applied in the order op[0], op[1], ... */
+    uint8_t op[4];        /* ISA_PHOTO_* */
+    float factor[4];      /* blend factor of op[k] (unused for hue) */
+    uint8_t hue_shift;    /* added to H mod 256 */
+    uint8_t use_lut;      /* != 0: every channel through lut[] (gamma) */
+    uint8_t gray;         /* != 0: L of the result to all three channels */
+    uint8_t chan[3];      /* output channel c takes channel chan[c]; duplicates allowed; {0,1,2} = none */
+    uint8_t pad[2];
+    uint8_t lut[256];
+} isa_photo_prog;         /* 288 bytes */
+/* src uint8 [n,h,w,3] -> dst uint8 [n,h,w,3]; src == dst is allowed (the pass is elementwise).  progs_dev: n programs
+ * on the device, one per image.  has_contrast != 0: some program holds a contrast op; a pre-pass then sums L of those
+ * images (after the ops listed before contrast) into sums_ws, device int64 [n], which the call zeroes itself.  With
+ * has_contrast == 0 sums_ws may be NULL and a contrast op in a program is skipped.  n <= 65535. */
+int isa_photometric_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, const isa_photo_prog* progs_dev,
+                       int32_t has_contrast, int64_t* sums_ws, void* stream);
+
 /* ---- boundary layout converters (the reference passes NCHW fp32: reseg.py:106-110) -----------
  * nchw_to_nhwc: channels [csrc, c) are written as 0; bf16 stores round to nearest even.  Channels at or above c: a dst
  * with ld == rup(c, 8) <= 32, 16-byte aligned src and data and h*w % 4 == 0 is written in whole padded rows (channels

@@ -7,6 +7,8 @@
 // loop in IEEE double - bit-identical to Pillow - and travel as kernel arguments; the device pass is a gather of
 // pixel vectors.  oracle/resize_ref.py restates the same rule and is pinned against the installed Pillow.
 #include "common.hpp"
+#include <cmath>
+#include <vector>
 
 namespace {
 
@@ -119,7 +121,101 @@ static int bilin_ksize(int n_in, int n_out) {
     return (int)ceil(fs) * 2 + 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Lanczos image resize, the two `img.resize(size, Image.ANTIALIAS)` of the reference's random_resolution
+// (code/lib/preprocess.py:443-454, dataset.py:156-157,182-183; ANTIALIAS was Pillow's name for LANCZOS): the same
+// Resample.c, hence the same two passes above, with the filter sinc(x) * sinc(x / 3) of support 3.  Its coefficients
+// need sin: they are computed here on the host, in IEEE double with libm's sin as Pillow does, since a last-bit
+// difference of the device's sin flips a 22-bit rounding once in a long while.  The weight is scaled by 1 / filterscale
+// before it is normalised, as in precompute_coeffs.
+static int lanczos_ksize(int n_in, int n_out) {
+    const double scale = (double)n_in / (double)n_out, fs = scale < 1.0 ? 1.0 : scale;
+    return (int)ceil(3.0 * fs) * 2 + 1;
+}
+static double sinc_filter(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static double lanczos_filter(double x) { return (-3.0 <= x && x < 3.0) ? sinc_filter(x) * sinc_filter(x / 3) : 0.0; }
+
+void lanczos_coeffs_host(int n_in, int n_out, int ksize, int* bounds, int* kk) {
+#pragma clang fp contract(off)
+    const double scale = (double)n_in / (double)n_out;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 3.0 * filterscale, ss = 1.0 / filterscale;
+    std::vector<double> k(ksize);
+    for (int xx = 0; xx < n_out; ++xx) {
+        const double center = (xx + 0.5) * scale;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > n_in) xmax = n_in;
+        xmax -= xmin;
+        double ww = 0.0;
+        for (int x = 0; x < xmax; ++x) {
+            k[x] = lanczos_filter((x + xmin - center + 0.5) * ss) * ss;
+            ww += k[x];
+        }
+        for (int x = 0; x < ksize; ++x) {
+            int v = 0;
+            if (x < xmax) {
+                const double w = ww != 0.0 ? k[x] / ww : k[x];
+                v = w < 0.0 ? (int)(-0.5 + w * (double)(1 << RS_PREC)) : (int)(0.5 + w * (double)(1 << RS_PREC));
+            }
+            kk[(long)xx * ksize + x] = v;
+        }
+        bounds[2 * xx] = xmin; bounds[2 * xx + 1] = xmax;
+    }
+}
+
 }  // namespace
+
+static bool lanczos_sizes_ok(int n, int h0, int w0, int c, int h, int w) {
+    return n > 0 && h0 > 0 && w0 > 0 && c > 0 && c <= 4 && h > 0 && w > 0 && h0 <= 65535 && w0 <= 65535 && h <= 65535 && w <= 65535;
+}
+static int64_t lanczos_table_ints(int h0, int w0, int h, int w) {
+    return 2L * w + (int64_t)w * lanczos_ksize(w0, w) + 2L * h + (int64_t)h * lanczos_ksize(h0, h);
+}
+
+extern "C" int isa_resize_lanczos_ws_bytes(int32_t n, int32_t h0, int32_t w0, int32_t c, int32_t h, int32_t w, int64_t* bytes) {
+    if (!bytes || !lanczos_sizes_ok(n, h0, w0, c, h, w)) return ISA_EINVAL;
+    *bytes = ((lanczos_table_ints(h0, w0, h, w) * 4 + 255) & ~255L) + (int64_t)n * h0 * w * c;
+    return ISA_OK;
+}
+
+extern "C" int isa_resize_lanczos_u8(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t c, uint8_t* dst,
+                                     int32_t h, int32_t w, void* ws, int64_t ws_bytes, void* stream) {
+    if (!src || !dst || src == dst || !ws || !lanczos_sizes_ok(n, h0, w0, c, h, w)) return ISA_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) % 4) return ISA_EALIGN;
+    int64_t need = 0;
+    isa_resize_lanczos_ws_bytes(n, h0, w0, c, h, w, &need);
+    if (ws_bytes < need) return ISA_ENOMEM;
+    hipStream_t s = as_stream(stream);
+    const int kx = lanczos_ksize(w0, w), ky = lanczos_ksize(h0, h);
+    const int64_t ints = lanczos_table_ints(h0, w0, h, w);
+    int* xb = reinterpret_cast<int*>(ws); int* xk = xb + 2 * w; int* yb = xk + (long)w * kx; int* yk = yb + 2 * h;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(ws) + ((ints * 4 + 255) & ~255L);
+    if (w0 == w && h0 == h)
+        return hipMemcpyAsync(dst, src, (size_t)n * h * w * c, hipMemcpyDeviceToDevice, s) == hipSuccess ? ISA_OK : ISA_ELAUNCH;
+    // Both tables in one host buffer with the workspace's layout and one copy.  The buffer must outlive the copy, which
+    // is asynchronous for pageable memory only up to the runtime's discretion: wait for it before the buffer goes.  The
+    // callers read back from the device once per sample anyway; the kernels below stay asynchronous.
+    std::vector<int> tabs((size_t)ints, 0);
+    if (w0 != w) lanczos_coeffs_host(w0, w, kx, tabs.data(), tabs.data() + 2 * w);
+    if (h0 != h) lanczos_coeffs_host(h0, h, ky, tabs.data() + (yb - xb), tabs.data() + (yk - xb));
+    if (hipMemcpyAsync(ws, tabs.data(), (size_t)ints * 4, hipMemcpyHostToDevice, s) != hipSuccess) return ISA_ELAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess) return ISA_ELAUNCH;
+    const uint8_t* hsrc = src;
+    if (w0 != w) {                                    // horizontal pass first (ImagingResample), skipped on an unchanged axis
+        uint8_t* out = h0 != h ? tmp : dst;
+        hipLaunchKernelGGL(resample_h_kernel, dim3(grid_cap(cdiv((long)n * h0 * w, 256), 4096)), dim3(256), 0, s, src, out, n, h0, w0, w, c, xb, xk, kx);
+        hsrc = out;
+    }
+    if (h0 != h)
+        hipLaunchKernelGGL(resample_v_kernel, dim3(grid_cap(cdiv((long)n * h * w, 256), 4096)), dim3(256), 0, s, hsrc, dst, n, h0, h, w, c, yb, yk, ky);
+    return launch_status();
+}
 
 extern "C" int64_t isa_resize_bilinear_ws_bytes(int32_t n, int32_t h0, int32_t w0, int32_t c, int32_t h, int32_t w) {
     if (n <= 0 || h0 <= 0 || w0 <= 0 || c <= 0 || h <= 0 || w <= 0) return 0;

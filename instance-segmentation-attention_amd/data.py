@@ -276,6 +276,97 @@ def resize_bilinear(images, size, device="cuda"):
     return dst
 
 
+def resize_lanczos(images, size, device="cuda"):
+    """PIL Image.resize(size, LANCZOS) - the reference's `Image.ANTIALIAS` (preprocess.py:451-452) - on the device:
+    uint8 [n,h0,w0,c] (c <= 4) -> uint8 [n,size_h,size_w,c], bit-identical to Pillow (isa_resize_lanczos_u8; the
+    coefficient tables are computed on the host inside the call)."""
+    import ctypes as C
+    from . import lib as L
+    h, w = (size, size) if isinstance(size, int) else size
+    src = images.to(device).contiguous()
+    assert src.dtype == torch.uint8 and src.dim() == 4
+    n, h0, w0, c = src.shape
+    dst = torch.empty((n, h, w, c), dtype=torch.uint8, device=src.device)
+    need = C.c_int64(0)
+    L.check(L.lib().isa_resize_lanczos_ws_bytes(n, h0, w0, c, h, w, C.byref(need)), "isa_resize_lanczos_ws_bytes")
+    need = need.value
+    ws = _RESIZE_WS.get(src.device)
+    if ws is None or ws.numel() < need:
+        ws = _RESIZE_WS[src.device] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=src.device)
+    L.check(L.lib().isa_resize_lanczos_u8(L.ptr(src), n, h0, w0, c, L.ptr(dst), h, w, L.ptr(ws), ws.numel(), L.stream_ptr()),
+            "isa_resize_lanczos_u8")
+    return dst
+
+
+def resolution_degrade(rgb, ratio, device="cuda"):
+    """The reference's random_resolution (preprocess.py:443-454) for a drawn ratio on the device: Lanczos resize to
+    (size * ratio).astype('int'), then back.  uint8 [n,h,w,c] -> the same shape."""
+    n, h, w, c = rgb.shape
+    nw, nh = (int(v) for v in (np.array([w, h]) * ratio).astype('int'))
+    assert nw >= 1 and nh >= 1 and h >= 1 and w >= 1, "resolution ratio %r leaves no pixel of %dx%d" % (ratio, w, h)
+    return resize_lanczos(resize_lanczos(rgb, (nh, nw), device), (h, w), device)
+
+
+def gamma_lut(gamma, gain=1):
+    """adjust_gamma's table (preprocess.py:424) as Image.point applies it: every entry through Python's round()."""
+    return [round(255 * gain * pow(i / 255., gamma)) for i in range(256)]
+
+
+_PHOTO_OPS = dict(brightness=0, contrast=1, saturation=2, hue=3)
+
+
+def photo_program(ops=(), lut=None, chan=(0, 1, 2), gray=False):
+    """One image's program for `photometric`.  ops: sequence of (name, factor), name in brightness / contrast /
+    saturation / hue, each at most once, applied in the given order (hue's factor is torchvision's hue_factor in
+    [-0.5, 0.5]: H moves by int(factor * 255) & 255); lut: 256 bytes or None; chan: the source channel of each output
+    channel, duplicates allowed; gray: L to all three channels."""
+    from . import lib as L
+    p = L.IsaPhotoProg()
+    ops = list(ops)
+    names = [name for name, _ in ops]
+    assert len(ops) <= 4 and len(set(names)) == len(names) and all(name in _PHOTO_OPS for name in names), names
+    p.n_ops = len(ops)
+    for k, (name, factor) in enumerate(ops):
+        p.op[k] = _PHOTO_OPS[name]
+        p.factor[k] = float(factor)
+        if name == "hue":
+            assert -0.5 <= factor <= 0.5, factor
+            p.hue_shift = int(factor * 255) & 255
+        else:
+            assert factor >= 0, (name, factor)
+    if lut is not None:
+        lut = [int(v) for v in lut]
+        assert len(lut) == 256 and all(0 <= v <= 255 for v in lut)
+        p.use_lut = 1
+        p.lut[:] = lut
+    chan = [int(v) for v in chan]
+    assert len(chan) == 3 and all(0 <= v <= 2 for v in chan), chan
+    p.chan[:] = chan
+    p.gray = 1 if gray else 0
+    return p
+
+
+def photometric(rgb, programs, device="cuda", out=None):
+    """Colour jitter, gamma, channel swap and grayscale (dataset.py:271-281) in one pass on the device
+    (isa_photometric_u8): uint8 [n,h,w,3] and one `photo_program` per image -> uint8 [n,h,w,3], bit-identical to the
+    reference's sequence of PIL calls.  out: the tensor to write (may be `rgb` itself), a new one by default."""
+    from . import lib as L
+    src = rgb.to(device).contiguous()
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+    n, h, w, _ = src.shape
+    programs = list(programs)
+    assert len(programs) == n, (len(programs), n)
+    packed = (L.IsaPhotoProg * n)(*programs)
+    progs = torch.frombuffer(bytearray(bytes(packed)), dtype=torch.uint8).to(src.device)
+    contrast = any(L.PHOTO_CONTRAST in list(p.op[:p.n_ops]) for p in programs)
+    sums = torch.empty(n, dtype=torch.int64, device=src.device) if contrast else None
+    dst = torch.empty_like(src) if out is None else out
+    assert dst.is_contiguous() and dst.dtype == torch.uint8 and dst.shape == src.shape and dst.device == src.device
+    L.check(L.lib().isa_photometric_u8(L.ptr(src), L.ptr(dst), n, h, w, L.ptr(progs), int(contrast), L.ptr(sums),
+                                       L.stream_ptr()), "isa_photometric_u8")
+    return dst
+
+
 class DevicePrefetcher(object):
     """Wraps an iterable of collated host batches (x, sem, ins, n): batch i+1 travels to the device on its own HIP
     stream while step i computes, so the host-to-device time of the reference's hand-over (373 MB per step at bs=16:

@@ -18,6 +18,7 @@ IN_1X1, IN_3X3, IN_GATHER2 = 0, 1, 2
 OUT_PLAIN, OUT_SHUFFLE2 = 0, 1
 PLANES_U8_NHWK, PLANES_I64_NKHW, PLANES_F32_NKHW = 0, 1, 2
 HIST_AGGREGATE, HIST_NAIVE = 0, 1
+PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SATURATION, PHOTO_HUE = 0, 1, 2, 3
 
 _ERR = {-1: "ISA_EINVAL", -2: "ISA_EALIGN", -3: "ISA_EDTYPE", -4: "ISA_ELAUNCH", -5: "ISA_ENOMEM"}
 
@@ -60,6 +61,12 @@ class IsaPackEntry(C.Structure):
                 ("kmap_off", C.c_int32), ("rows", C.c_int32)]
 
 
+class IsaPhotoProg(C.Structure):
+    _fields_ = [("n_ops", C.c_int32), ("op", C.c_uint8 * 4), ("factor", C.c_float * 4), ("hue_shift", C.c_uint8),
+                ("use_lut", C.c_uint8), ("gray", C.c_uint8), ("chan", C.c_uint8 * 3), ("pad", C.c_uint8 * 2),
+                ("lut", C.c_uint8 * 256)]
+
+
 P_T, P_PRO, VP, I32, F = C.POINTER(IsaTensor), C.POINTER(IsaPro), C.c_void_p, C.c_int32, C.c_float
 I64 = C.c_int64
 F64 = C.c_double
@@ -90,6 +97,9 @@ SIGNATURES = {
     "isa_crop_planes_u8": [VP, I32, I32, I32, I32, I32, I32, VP, I32, I32, I32, VP, VP],
     "isa_resize_nearest_u8": [VP, I32, I32, I32, I32, VP, I32, I32, VP],
     "isa_resize_bilinear_u8": [VP, I32, I32, I32, I32, VP, I32, I32, VP, I64, VP],
+    "isa_resize_lanczos_ws_bytes": [I32, I32, I32, I32, I32, I32, C.POINTER(C.c_int64)],
+    "isa_resize_lanczos_u8": [VP, I32, I32, I32, I32, VP, I32, I32, VP, I64, VP],
+    "isa_photometric_u8": [VP, VP, I32, I32, I32, VP, I32, VP, VP],
     "isa_collate_targets": [VP, VP, I32, I32, I32, I32, VP, VP, VP],
     "isa_collate_targets_k": [VP, VP, I32, I32, I32, I32, I32, VP, VP, VP, VP],
     "isa_bn_finalize": [VP, F, VP, VP, VP, VP, F, F, VP, VP, VP, VP, I32, I32, I32, VP],

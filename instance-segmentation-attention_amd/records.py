@@ -17,8 +17,16 @@ applies the augmentations the reference ships ENABLED (settings/CVPPP/training_s
 the reference's order (dataset.py:185-269): horizontal / vertical flip, transpose, 90x rotation (`data.d4_augment`, on
 the original non-square image), rotation by an integer angle in [-9, 9] with expand (annotations nearest, image
 bilinear over a drawn background: `data.rotate_nearest`, `data.rotate_image`) and the centre cut with its has-object
-filter (`data.center_cut`).  The ones it ships disabled (colour jitter, gamma, channel swap, grayscale, resolution:
-dataset.py:271-285) are not part of this build."""
+filter (`data.center_cut`).  The five it ships disabled (dataset.py:104-106,147-157,182-183,271-281) are here as
+well, each behind a flag that is off by default, drawn and applied at the reference's position: `resolution`
+(preprocess.py:443-463: Lanczos there and back at a drawn ratio, `data.resolution_degrade`) before the flips, then after
+the centre cut `color_jitter` (utils.py:58-59: torchvision ColorJitter(0.4, 0.4, 0.4, 0.2)), `gamma`
+(preprocess.py:405-439), `channel_swap` (preprocess.py:381-401) and `grayscale` (utils.py:62-63), which travel
+together as ONE program through one pass over the sample (`data.photometric`, isa_photometric_u8).  All of them are
+bit-identical to the reference's PIL calls (tests/test_photometric_ref.py, tests/test_gpu_photometric*.py).
+The jitter draws follow torchvision's ColorJitter.get_params of the reference's era on Python's generator:
+brightness, contrast, saturation from uniform(0.6, 1.4) each, hue from uniform(-0.2, 0.2), then random.shuffle of the
+four ops.  torchvision is not a dependency of this build, so that order is a stated choice, not a pinned one."""
 import io
 import os
 import random
@@ -113,12 +121,19 @@ class RecordLoader(object):
     others would wait in its gradient all-reduce forever."""
 
     def __init__(self, dataset, batch_size, height=256, width=256, max_n_objects=32, mode='test', seed=0, device='cuda',
-                 rank=0, world=1, d4=True, rotation=True, center_cut=True):
+                 rank=0, world=1, d4=True, rotation=True, center_cut=True, color_jitter=False, gamma=False,
+                 channel_swap=False, grayscale=False, resolution=False):
         assert mode in ('training', 'test')
         self.ds, self.bs, self.h, self.w, self.k, self.mode = dataset, batch_size, height, width, max_n_objects, mode
         self.seed, self.epoch, self.device, self.rank, self.world = seed, 0, device, rank, world
         self.d4, self.rotation, self.center_cut = d4, rotation, center_cut
-        self.last_draws = []             # per image of the last batch: dict(op, angle, bg_key, pick) - tests / logging
+        # the five photometric augmentations (AlignCollate's random_color_jittering, random_gamma,
+        # random_channel_swapping, random_grayscaling, random_resolution); off: no draw is made for them
+        self.color_jitter, self.gamma, self.channel_swap, self.grayscale = color_jitter, gamma, channel_swap, grayscale
+        self.resolution = resolution
+        # per image of the last batch: dict(op, angle, bg_key, pick) and, for the flags that are on, ratio / jitter (the
+        # four (name, factor) in shuffled order) / gamma / channels (None: no swap) / gray - tests / logging
+        self.last_draws = []
 
     def indices(self):
         idx = list(range(len(self.ds)))
@@ -146,6 +161,10 @@ class RecordLoader(object):
         semt = torch.from_numpy(np.array(sem)[None, :, :, None]).to(dev)
         draws = dict(op=0, angle=0, bg_key=None, pick=None)
         if self.mode == 'training':
+            if self.resolution:                                          # dataset.py:182-183, preprocess.py:459-463
+                draws["ratio"] = float(np_rng.choice(np.arange(0.7, 1.3, 0.05)))
+                rgb = D.resolution_degrade(rgb, draws["ratio"], dev)
+                rgb_host = None
             if self.d4:
                 # the reference's call order: hflip, vflip, transpose (random.random() < 0.5 each), then 90x rotation
                 op = int(py_rng.random() < 0.5) | (int(py_rng.random() < 0.5) << 1) | (int(py_rng.random() < 0.5) << 2) | \
@@ -169,6 +188,25 @@ class RecordLoader(object):
                     draws["pick"] = int(np_rng.choice(count, 1)[0])
                     return draws["pick"]
                 rgb, semt, planes, n_obj = D.center_cut(rgb, semt, planes, n_obj, draw, self.h, self.w, self.k, dev)
+            prog = dict()
+            if self.color_jitter:                                        # dataset.py:271-272 (order: see the module docstring)
+                ops = [("brightness", py_rng.uniform(0.6, 1.4)), ("contrast", py_rng.uniform(0.6, 1.4)),
+                       ("saturation", py_rng.uniform(0.6, 1.4)), ("hue", py_rng.uniform(-0.2, 0.2))]
+                py_rng.shuffle(ops)
+                draws["jitter"] = prog["ops"] = ops
+            if self.gamma:                       # dataset.py:274-275, preprocess.py:438 (max - min = 0.6000000000000001)
+                draws["gamma"] = float(np_rng.rand() * (1.3 - 0.7) + 0.7)
+                prog["lut"] = D.gamma_lut(draws["gamma"])
+            if self.channel_swap:                                        # dataset.py:277-278, preprocess.py:388,398
+                draws["channels"] = None
+                if not np_rng.rand() >= 0.5:
+                    draws["channels"] = prog["chan"] = [int(v) for v in np_rng.choice([0, 1, 2], 3, True)]
+            if self.grayscale:                                           # dataset.py:280-281: RandomGrayscale(p=0.3)
+                draws["gray"] = bool(py_rng.random() < 0.3)
+                if draws["gray"]:
+                    prog["gray"] = True
+            if prog:                                                     # one pass for whatever was drawn, in place
+                rgb = D.photometric(rgb, [D.photo_program(**prog)], dev, out=rgb)
         self.last_draws.append(draws)
         h1, w1 = planes.shape[1:3]
         if planes.shape[3] != self.k:                                   # zero planes up to max_n_objects (dataset.py:305-311)

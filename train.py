@@ -53,6 +53,13 @@ def build_parser():
     parser.add_argument('--freeze-cnn', action='store_true', help='do not update the backbone (fit\'s train_cnn=False)')
     parser.add_argument('--val-scores', action='store_true', help='also segment and score every validation minibatch: '
                         'per-epoch SBD, |DiC| and FG Dice in <out>/validation_scores.log (Model.val_scores)')
+    # AlignCollate's five photometric augmentations, which the reference ships disabled (training_settings.py:42-46 COLOR_JITTERING,
+    # GAMMA_ADJUSTMENT, CHANNEL_SWAPPING, GRAYSCALING, RESOLUTION_DEGRADING): for the training loader of --data only
+    parser.add_argument('--color-jitter', action='store_true', help='random brightness / contrast / saturation / hue')
+    parser.add_argument('--gamma', action='store_true', help='random gamma in [0.7, 1.3]')
+    parser.add_argument('--channel-swap', action='store_true', help='random channel map, with probability 0.5')
+    parser.add_argument('--grayscale', action='store_true', help='grayscale with probability 0.3')
+    parser.add_argument('--resolution', action='store_true', help='Lanczos resize by a ratio in [0.7, 1.3] and back')
     return parser
 
 
@@ -81,6 +88,12 @@ def fit_arguments(opt):
             not opt.freeze_cnn, opt.nepochs, opt.class_weights)
 
 
+def photometric_arguments(opt):
+    """RecordLoader's photometric flags: the training loader's alone."""
+    return dict(color_jitter=opt.color_jitter, gamma=opt.gamma, channel_swap=opt.channel_swap, grayscale=opt.grayscale,
+                resolution=opt.resolution)
+
+
 def main(argv=None):
     opt = parse_args(argv)
     import isa_amd  # noqa: F401
@@ -105,7 +118,7 @@ def main(argv=None):
     if opt.data:                      # the reference's datasets (train.py:87-147): records -> device-side collate
         from isa_amd.records import RecordDataset, RecordLoader
         train_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'training-lmdb')), per_rank, opt.size, opt.size,
-                                    mode='training', seed=SEED, rank=rank, world=world)
+                                    mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt))
         test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
                                    mode='test', seed=SEED, rank=rank, world=world)
     model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug)
