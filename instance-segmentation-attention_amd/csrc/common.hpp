@@ -87,6 +87,51 @@ template <typename T> __device__ __forceinline__ void store8g(T* p, const float 
     for (int i = 0; i < 8; ++i) if (i < nv) st<T>::stv(p + i, v[i]);
 }
 
+// 8 storage elements kept packed in registers (4 VGPRs for bf16) until they are consumed
+template <typename T> struct raw8;
+template <> struct raw8<bf16_t> {
+    bf16x8 v;
+    __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const bf16x8*>(p); }
+    __device__ __forceinline__ float get(int j) const { return (float)v[j]; }
+    __device__ __forceinline__ void store(bf16_t* p) const { *reinterpret_cast<bf16x8*>(p) = v; }
+    __device__ __forceinline__ void zero() { v = bf16x8{}; }
+    __device__ __forceinline__ void pack(const float (&f)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (bf16_t)f[i];
+    }
+    __device__ __forceinline__ void store1(bf16_t* p, int j) const { p[j] = v[j]; }
+};
+template <> struct raw8<float> {
+    f32x4 a, b;
+    __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const f32x4*>(p); b = *reinterpret_cast<const f32x4*>(p + 4); }
+    __device__ __forceinline__ float get(int j) const { return j < 4 ? a[j] : b[j - 4]; }
+    __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<f32x4*>(p) = a; *reinterpret_cast<f32x4*>(p + 4) = b; }
+    __device__ __forceinline__ void zero() { a = f32x4{}; b = f32x4{}; }
+    __device__ __forceinline__ void pack(const float (&f)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { a[i] = f[i]; b[i] = f[4 + i]; }
+    }
+    __device__ __forceinline__ void store1(float* p, int j) const { p[j] = get(j); }
+};
+
+// Maskable forms of load8g / store8g for loops that keep several loads in flight: the 16-byte load is issued for EVERY
+// lane, with no branch in front of it, and the elements past `nv` are zeroed by selects when the registers are unpacked
+// (after the wait).  The whole vector of a channel-tail group lies inside the row: tensor_ok(t, 8) gives an 8-element
+// aligned base and ld % 8 == 0 with ld >= c, so rup(c, 8) <= ld (dwconv.hip relies on the same fact).  What the pad
+// elements hold (NaN in a concat buffer's neighbours) never leaves unpack8m.  load8g's branch on the per-lane nv puts
+// every load into a divergent region of its own, each followed by a full wait.
+template <typename T> __device__ __forceinline__ raw8<T> load8raw(const T* p) { raw8<T> r; r.load(p); return r; }
+template <typename T> __device__ __forceinline__ void unpack8m(const raw8<T>& r, float (&v)[8], int nv) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = i < nv ? r.get(i) : 0.f;
+}
+// as store8g: a full group is one 16-byte store, a tail group goes out per element (its neighbours stay untouched)
+template <typename T> __device__ __forceinline__ void store8raw(T* p, const raw8<T>& r, int nv) {
+    if (nv >= 8) { r.store(p); return; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) if (i < nv) r.store1(p, i);
+}
+
 // Sum over the lanes of a 16-lane row that share (lane % CLS), CLS = 4 or 8: DPP row rotations, no LDS traffic.  The
 // end-of-kernel folds used __shfl_xor trees (ds_bpermute: a dependent LDS round trip per step) per value: a phase
 // trace of dw_bn_bwd on a one-tile problem showed 26 k of the launch's 47 k cycles in its fold.  Lanes 0..CLS-1 of

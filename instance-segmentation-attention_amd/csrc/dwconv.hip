@@ -41,22 +41,7 @@ struct Dw2Params {
     FinDev fin;                  // pending BatchNorm finalize of the lazy input (forward only), or stats == NULL
 };
 
-// 8 storage elements kept packed in registers (4 VGPRs for bf16) until they are consumed
-template <typename T> struct raw8;
-template <> struct raw8<bf16_t> {
-    bf16x8 v;
-    __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const bf16x8*>(p); }
-    __device__ __forceinline__ float get(int j) const { return (float)v[j]; }
-    __device__ __forceinline__ void store(bf16_t* p) const { *reinterpret_cast<bf16x8*>(p) = v; }
-    __device__ __forceinline__ void zero() { v = bf16x8{}; }
-};
-template <> struct raw8<float> {
-    f32x4 a, b;
-    __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const f32x4*>(p); b = *reinterpret_cast<const f32x4*>(p + 4); }
-    __device__ __forceinline__ float get(int j) const { return j < 4 ? a[j] : b[j - 4]; }
-    __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<f32x4*>(p) = a; *reinterpret_cast<f32x4*>(p + 4) = b; }
-    __device__ __forceinline__ void zero() { a = f32x4{}; b = f32x4{}; }
-};
+// raw8<T> (common.hpp): 8 storage elements kept packed in registers until they are consumed
 
 // per-lane prologue constants: a lane stages the same 8-channel group on every iteration (i += 256 keeps i & 3)
 struct ProRegs { float sc[8], sh[8], bs[8]; };

@@ -116,9 +116,42 @@ static inline Walk mkwalk(int c, long pixels) {
 // the wide, low-resolution levels (4096 px x 512 ch: the epilogue atomics outnumbered the data 16:1)
 static inline int walk_grid(const Walk& w, int iters = 1) { return grid_cap(cdiv(w.pixels, (long)(256 >> w.sh) * iters)); }
 
+// Trips of the pixel walk whose loads a lane issues together (bn_bwd_kernel reduce / apply, materialize_kernel).  One trip
+// at a time left a wave with a single 1-KB request outstanding: every 16-byte load sat in a divergent region of its own
+// (load8g branches on the per-lane nv) and was followed by a full wait, so a trip was two to four dependent round trips.
+// Measured on MI355X, bf16, batch 16, operands rotated through HBM (scripts/ab_streaming.py, profiles/ab_streaming.txt),
+// us per launch, one trip at a time -> U = 2 -> U = 4:
+//   reduce  256x256x64 62.8 -> 52.5 -> 53.4   128x128x128 46.4 -> 35.9 -> 35.3   64x64x256 24.9 -> 20.0 -> 20.8
+//           32x32x512  18.0 -> 15.8 -> 15.9   16x16x1024  13.6 -> 11.6 -> 11.6          (U = 4 buys nothing more)
+//   apply   256x256x64 85.2 -> 82.1   64x64x256 36.2 -> 35.6   32x32x512 20.7 -> 19.4   16x16x1024 12.6 -> 11.4
+//   materialise (x + res)  256x256x64 82.9 -> 80.9   256x256x32 43.8 -> 42.3
+// U = 4 does not fit the register budget below for apply (runtime-activation variant) and materialise (scratch): not
+// measured.  axpy8_kernel stays one item at a time: batched the same way it measured slower (128x128x64: 19.8 -> 21.4 us).
+constexpr int STREAM_U_REDUCE = 2, STREAM_U_APPLY = 2, STREAM_U_MAT = 2;
+// The constants count bf16 trips (one 16-byte load per tensor); an fp32 trip is two such loads, so fp32 batches half as many.
+template <typename T> constexpr int stream_u(int u) { return sizeof(T) == 2 ? u : (u > 1 ? u / 2 : 1); }
+// The batches must not cost occupancy (the walkers hide latency with waves too): the register allocator is held to the
+// waves per SIMD these kernels had with one trip in flight.
+#define STREAM_WAVES(n) __attribute__((amdgpu_waves_per_eu(n, n)))
+
+// Eight consecutive floats of a per-image multiplier row ([C] floats per image, so only 4-byte aligned): two 16-byte loads
+// for a full channel group; a tail group reads its own channels only (the pad elements multiply values nobody keeps).
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void load_row8(const float* row, float (&v)[8], int nv) {
+    if (nv >= 8) {
+        const f32x4u a = *reinterpret_cast<const f32x4u*>(row), b = *reinterpret_cast<const f32x4u*>(row + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = j < nv ? row[j] : 0.f;
+}
+
 // z = scale*y+shift ; dz = dt * bscale * act'(z)
-template <typename T, bool APPLY, int ACT>
-__global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p, Walk wk) {
+// PI: a per-image multiplier (bscale) is present
+template <typename T, bool APPLY, int ACT, bool PI>
+__global__ __launch_bounds__(256) STREAM_WAVES((!APPLY && ACT == ISA_ACT_NONE) ? 5 : 4) void bn_bwd_kernel(BnBwdParams p, Walk wk) {
     extern __shared__ float red[];              // [2*C]: reduce pass partial sums / apply pass folded sums
     const int C = p.y.c;
     if (p.groups > 1 && blockIdx.z) {           // this workgroup's statistic group: its images and its constants
@@ -174,21 +207,65 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p, Walk wk) {
             s0[j] = 0.f; s1[j] = 0.f;
         }
         const long step = (long)gridDim.x * ppb;
-        for (long pix = (long)blockIdx.x * ppb + psub; pix < wk.pixels; pix += step) {
-            float dt[8], yv[8], out[8];
-            load8g<T>(reinterpret_cast<const T*>(p.dt.data) + pix * p.dt.ld + c0, dt, nv);
-            load8g<T>(reinterpret_cast<const T*>(p.y.data) + pix * p.y.ld + c0, yv, nv);
-            const float* bs = p.bscale ? p.bscale + (long)((unsigned)pix / hw) * C : nullptr;
+        const long pix_first = (long)blockIdx.x * ppb + psub;
+        // the per-image multiplier row of this lane's channel group lives in registers and is fetched again only when the
+        // pixel's image changes: the first one here, next to the per-channel constants
+        float bsr[8];
+        unsigned bimg = 0;
+        if (PI && pix_first < wk.pixels) {
+            bimg = (unsigned)pix_first / hw;
+            load_row8(p.bscale + (long)bimg * C + c0, bsr, nv);
+        }
+        // U trips of the grid-stride walk at a time: first every load of the batch, back to back into packed registers,
+        // then the arithmetic trip by trip in ascending order, then the stores.  A trip past the end repeats the batch's
+        // first trip: the same loads and the same result, which the reduce pass adds as zero and the apply pass stores
+        // again (a lane rewrites its own 16 bytes with the value it has just written; in place too, since every load of
+        // the batch precedes its stores).  With a branch around that trip's sums or store the compiler sinks the trip's
+        // loads behind the branch, each with a full wait: the serial chain again.
+        constexpr int U = PI ? 1 : stream_u<T>(APPLY ? STREAM_U_APPLY : STREAM_U_REDUCE);
+        for (long pix0 = pix_first; pix0 < wk.pixels; pix0 += U * step) {
+            raw8<T> rdt[U], ry[U], rout[U];
+            unsigned pixu[U]; bool ok[U];                    // pixel indices fit 32 bits (checked by the host)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float z = fmaf(yv[j], sc[j], sh[j]);
-                float dz = dt[j] * act_grad_t<ACT>(z, p.act);
-                if (bs) dz *= bs[min(c0 + j, C - 1)];
-                const float yh = (yv[j] - mu[j]) * is[j];
-                if (!APPLY) { s0[j] += dz; s1[j] += dz * yh; }
-                else out[j] = sc[j] * (dz - k0[j] - yh * k1[j]);
+            for (int u = 0; u < U; ++u) {
+                const long pix = pix0 + u * step;
+                ok[u] = pix < wk.pixels;
+                pixu[u] = (unsigned)(ok[u] ? pix : pix0);
             }
-            if (APPLY) store8g<T>(reinterpret_cast<T*>(p.dy.data) + pix * p.dy.ld + c0, out, nv);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                rdt[u] = load8raw<T>(reinterpret_cast<const T*>(p.dt.data) + (long)pixu[u] * p.dt.ld + c0);
+                ry[u] = load8raw<T>(reinterpret_cast<const T*>(p.y.data) + (long)pixu[u] * p.y.ld + c0);
+            }
+            __builtin_amdgcn_sched_barrier(0);               // no unpack (and its wait) between the loads of a batch
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float dt[8], yv[8], out[8];
+                unpack8m<T>(rdt[u], dt, nv);
+                unpack8m<T>(ry[u], yv, nv);
+                if (PI) {
+                    const unsigned img = pixu[u] / hw;
+                    if (img != bimg) {
+                        bimg = img;
+                        load_row8(p.bscale + (long)img * C + c0, bsr, nv);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float z = fmaf(yv[j], sc[j], sh[j]);
+                    float dz = dt[j] * act_grad_t<ACT>(z, p.act);
+                    if (PI) dz *= bsr[j];
+                    const float yh = (yv[j] - mu[j]) * is[j];
+                    if (!APPLY) { if (!ok[u]) dz = 0.f; s0[j] += dz; s1[j] += dz * yh; }
+                    else out[j] = sc[j] * (dz - k0[j] - yh * k1[j]);
+                }
+                if (APPLY) rout[u].pack(out);
+            }
+            if (APPLY) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    store8raw<T>(reinterpret_cast<T*>(p.dy.data) + (long)pixu[u] * p.dy.ld + c0, rout[u], nv);
+            }
         }
         if (!APPLY) {
             // lanes that differ only above bit `sh` hold the same channel group: fold them inside the wave first, so a
@@ -221,8 +298,9 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p, Walk wk) {
 // groups (blockIdx.z): pixels / wk.pixels are per group.  bcast: x (and res) hold ONE group of images that every output
 // group reads (an identical sub-network evaluated once for all decoder iterations; only the per-image oscale differs).
 struct MatParams { View x, res, res2, out; ProDev pro; const float* oscale; long pixels; int cg; int has_res, has_res2; int groups, bcast; FinDev fin; };
-template <typename T, int ACT>
-__global__ __launch_bounds__(256) void materialize_kernel(MatParams p, Walk wk) {
+// PI: a per-image multiplier (pro.bscale or oscale) is present
+template <typename T, int ACT, bool PI>
+__global__ __launch_bounds__(256) STREAM_WAVES(sizeof(T) == 2 ? 5 : 4) void materialize_kernel(MatParams p, Walk wk) {
     const int C = p.x.c;
     // a pending finalize of x's BatchNorm runs here (isa_pro.fin): x's statistic group of this workgroup into LDS
     __shared__ float fin_tab[2 * ISA_FIN_MAX_C];
@@ -254,35 +332,76 @@ __global__ __launch_bounds__(256) void materialize_kernel(MatParams p, Walk wk) 
             sc[j] = fin ? fin_tab[c] : (p.pro.scale ? p.pro.scale[c] : 1.f);
             sh[j] = fin ? fin_tab[ISA_FIN_MAX_C + c] : (p.pro.shift ? p.pro.shift[c] : 0.f);
         }
-        const bool per_image = p.pro.bscale || p.oscale;
         const long step = (long)gridDim.x * ppb;
-        for (long pix = (long)blockIdx.x * ppb + psub; pix < wk.pixels; pix += step) {
-            float v[8];
-            load8g<T>(reinterpret_cast<const T*>(p.x.data) + pix * p.x.ld + c0, v, nv);
-            const long bofs = per_image ? (long)((unsigned)pix / hw) * C : 0;
+        const long pix_first = (long)blockIdx.x * ppb + psub;
+        // per-image multiplier rows in registers, fetched again only when the pixel's image changes (as in bn_bwd_kernel)
+        float bsr[8], osr[8];
+        unsigned bimg = 0;
+        auto load_rows = [&](unsigned img) {
+            bimg = img;
+            const long bofs = (long)img * C + c0;
+            if (p.pro.bscale) load_row8(p.pro.bscale + bofs, bsr, nv);       // wave-uniform: not a test per element
+            if (p.oscale) load_row8(p.oscale + bofs, osr, nv);
+        };
+        if (PI && pix_first < wk.pixels) load_rows((unsigned)pix_first / hw);
+        // U trips at a time: all loads of the batch (x, res, res2) first, then the arithmetic in ascending trip order,
+        // then the stores; a trip past the end repeats the batch's first trip, store included (see bn_bwd_kernel)
+        constexpr int U = PI ? 1 : stream_u<T>(STREAM_U_MAT);
+        for (long pix0 = pix_first; pix0 < wk.pixels; pix0 += U * step) {
+            raw8<T> rx[U], rr[U], rr2[U], rout[U];
+            unsigned pixu[U]; bool ok[U];                    // pixel indices fit 32 bits (checked by the host)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = act_t<ACT>(fmaf(v[j], sc[j], sh[j]), p.pro.act);
-            if (p.pro.bscale) {                              // wave-uniform: not a test per element
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] *= p.pro.bscale[bofs + min(c0 + j, C - 1)];
+            for (int u = 0; u < U; ++u) {
+                const long pix = pix0 + u * step;
+                ok[u] = pix < wk.pixels;
+                pixu[u] = (unsigned)(ok[u] ? pix : pix0);
             }
-            if (p.has_res) {
-                float rr[8];
-                load8g<T>(reinterpret_cast<const T*>(p.res.data) + pix * p.res.ld + c0, rr, nv);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += rr[j];
+            for (int u = 0; u < U; ++u) rx[u] = load8raw<T>(reinterpret_cast<const T*>(p.x.data) + (long)pixu[u] * p.x.ld + c0);
+            if (p.has_res) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) rr[u] = load8raw<T>(reinterpret_cast<const T*>(p.res.data) + (long)pixu[u] * p.res.ld + c0);
             }
             if (p.has_res2) {
-                float rr[8];
-                load8g<T>(reinterpret_cast<const T*>(p.res2.data) + pix * p.res2.ld + c0, rr, nv);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += rr[j];
+                for (int u = 0; u < U; ++u) rr2[u] = load8raw<T>(reinterpret_cast<const T*>(p.res2.data) + (long)pixu[u] * p.res2.ld + c0);
             }
-            if (p.oscale) {
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] *= p.oscale[bofs + min(c0 + j, C - 1)];
+            for (int u = 0; u < U; ++u) {
+                float v[8];
+                unpack8m<T>(rx[u], v, nv);
+                if (PI) {
+                    const unsigned img = pixu[u] / hw;
+                    if (img != bimg) load_rows(img);
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = act_t<ACT>(fmaf(v[j], sc[j], sh[j]), p.pro.act);
+                if (PI && p.pro.bscale) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] *= bsr[j];
+                }
+                if (p.has_res) {
+                    float r[8];
+                    unpack8m<T>(rr[u], r, nv);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] += r[j];
+                }
+                if (p.has_res2) {
+                    float r[8];
+                    unpack8m<T>(rr2[u], r, nv);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] += r[j];
+                }
+                if (PI && p.oscale) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] *= osr[j];
+                }
+                rout[u].pack(v);
             }
-            store8g<T>(reinterpret_cast<T*>(p.out.data) + pix * p.out.ld + c0, v, nv);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                store8raw<T>(reinterpret_cast<T*>(p.out.data) + (long)pixu[u] * p.out.ld + c0, rout[u], nv);
         }
     }
 }
@@ -659,10 +778,12 @@ static int bn_bwd_common(const isa_tensor* dt, const isa_tensor* y, const isa_te
         if (!apply && grid > 1024) grid = 1024;     // every block ends with 2C global atomics (8 replicas)
     }
     const size_t lds = 2 * (size_t)y->c * 4;
+#define BN_BWD_LAUNCH_T(TT, AP, ACTV) \
+    do { if (p.bscale) hipLaunchKernelGGL((bn_bwd_kernel<TT, AP, ACTV, true>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk); \
+         else hipLaunchKernelGGL((bn_bwd_kernel<TT, AP, ACTV, false>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk); } while (0)
 #define BN_BWD_LAUNCH(AP, ACTV) \
     DISPATCH_T(y->dtype, \
-        hipLaunchKernelGGL((bn_bwd_kernel<bf16_t, AP, ACTV>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk), \
-        hipLaunchKernelGGL((bn_bwd_kernel<float, AP, ACTV>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk))
+        BN_BWD_LAUNCH_T(bf16_t, AP, ACTV), BN_BWD_LAUNCH_T(float, AP, ACTV))
     if (apply) {
         if (p.act == ISA_ACT_RELU6) BN_BWD_LAUNCH(true, ISA_ACT_RELU6);
         else if (p.act == ISA_ACT_NONE) BN_BWD_LAUNCH(true, ISA_ACT_NONE);
@@ -673,6 +794,7 @@ static int bn_bwd_common(const isa_tensor* dt, const isa_tensor* y, const isa_te
         else BN_BWD_LAUNCH(false, ACT_RT);
     }
 #undef BN_BWD_LAUNCH
+#undef BN_BWD_LAUNCH_T
     return launch_status();
 }
 
@@ -727,14 +849,13 @@ extern "C" int isa_affine_act_res(const isa_tensor* x, const isa_pro* pro, const
     }
     const Walk wk = mkwalk(x->c, p.pixels);
     const dim3 grid(walk_grid(wk), 1, G);
-    if (p.pro.act == ISA_ACT_NONE)
-        DISPATCH_T(x->dtype,
-            hipLaunchKernelGGL((materialize_kernel<bf16_t, ISA_ACT_NONE>), grid, dim3(256), 0, as_stream(stream), p, wk),
-            hipLaunchKernelGGL((materialize_kernel<float, ISA_ACT_NONE>), grid, dim3(256), 0, as_stream(stream), p, wk));
-    else
-        DISPATCH_T(x->dtype,
-            hipLaunchKernelGGL((materialize_kernel<bf16_t, ACT_RT>), grid, dim3(256), 0, as_stream(stream), p, wk),
-            hipLaunchKernelGGL((materialize_kernel<float, ACT_RT>), grid, dim3(256), 0, as_stream(stream), p, wk));
+    const bool pi = p.pro.bscale || p.oscale;
+#define MAT_LAUNCH(TT, ACTV) \
+    do { if (pi) hipLaunchKernelGGL((materialize_kernel<TT, ACTV, true>), grid, dim3(256), 0, as_stream(stream), p, wk); \
+         else hipLaunchKernelGGL((materialize_kernel<TT, ACTV, false>), grid, dim3(256), 0, as_stream(stream), p, wk); } while (0)
+    if (p.pro.act == ISA_ACT_NONE) DISPATCH_T(x->dtype, MAT_LAUNCH(bf16_t, ISA_ACT_NONE), MAT_LAUNCH(float, ISA_ACT_NONE));
+    else DISPATCH_T(x->dtype, MAT_LAUNCH(bf16_t, ACT_RT), MAT_LAUNCH(float, ACT_RT));
+#undef MAT_LAUNCH
     return launch_status();
 }
 
