@@ -46,8 +46,7 @@ class PendingFin:
         if self.running_taken:
             return None, None
         self.running_taken = True
-        P = self.eng.params
-        return P.ptr(self.pre + ".running_mean"), P.ptr(self.pre + ".running_var")
+        return self.eng.running_ptrs(self.pre)
 
     def settled(self):
         E = self.eng
@@ -56,12 +55,9 @@ class PendingFin:
     def resolve(self):
         if self.settled():
             return
-        E, P = self.eng, self.eng.params
-        rm, rv = self._running()
-        L.check(E.lib.isa_bn_finalize(L.ptr(self.stats), self.count, P.ptr(self.pre + ".weight"), P.ptr(self.pre + ".bias"),
-                                      rm, rv, E.BN_MOMENTUM, E.BN_EPS, L.ptr(self.scale), L.ptr(self.shift),
-                                      L.ptr(self.mean), L.ptr(self.invstd), self.c, self.groups, self.rep, E.st()),
-                "isa_bn_finalize")
+        E = self.eng
+        E.bn_finalize(self.stats, self.count, self.pre, self._running(), self.scale, self.shift, self.mean, self.invstd,
+                      self.c, self.groups, self.rep, "isa_bn_finalize")
         self.done.add(E.cur)
 
     def inline(self, pro):
@@ -96,6 +92,29 @@ class Pro:
         if self.fin is None or self.fin.settled():
             return C.byref(self._c)
         return self.fin.inline(self)
+
+
+class BnLayer:
+    """One BatchNorm as its backward needs it (Act.bn).  bwd_fn: its tape closure; red_done: sums a fused conv backward
+    left for it (_bn_backward takes and clears them)."""
+    __slots__ = ("pre", "scale", "shift", "mean", "invstd", "act", "count", "train", "raw", "bwd_fn", "red_done")
+
+    def __init__(self, pre, scale, shift, mean, invstd, act, count, train, raw):
+        self.pre, self.scale, self.shift, self.mean, self.invstd = pre, scale, shift, mean, invstd
+        self.act, self.count, self.train, self.raw = act, count, train, raw
+        self.bwd_fn = self.red_done = None
+
+
+class ConvFusion:
+    """What a conv's backward takes over from the BatchNorms around it.  xbn: the BN that produced its input, if this backward
+    can produce that BN's reduce.  ybn, yred, g: the BN behind it left its apply here - record, sums, gradient tensor.
+    addend: a residual gradient to add to dx; done: the backward ran."""
+    __slots__ = ("xbn", "ybn", "yred", "g", "addend", "done")
+
+    def __init__(self, xbn):
+        self.xbn = xbn
+        self.ybn = self.yred = self.g = self.addend = None
+        self.done = False
 
 
 class Act:
@@ -556,7 +575,7 @@ class Engine:
         # fused BN-apply + depthwise backward + next BN-reduce (isa_dwconv3x3_bn_backward); ISA_FUSE_DW_BN=0
         # selects the separate kernels (A/B measurements, bisecting)
         self.fuse_dw_bn = os.environ.get("ISA_FUSE_DW_BN", "1") != "0"
-        self._dw_out: Dict[tuple, dict] = {}
+        self._dw_out: Dict[tuple, ConvFusion] = {}
         # the same for bias-free 1x1 convs with <= 64 channels either side (isa_conv1x1_bn_backward, bf16 only)
         self.fuse_pw_bn = os.environ.get("ISA_FUSE_PW_BN", "1") != "0"
         # eval mode: BatchNorm (a constant affine), activation and residual ride in the conv's output epilogue
@@ -566,8 +585,8 @@ class Engine:
         self.fuse_block = os.environ.get("ISA_FUSE_BLOCK", "1") != "0"
         # train-mode BatchNorm finalizes run inside the consumer of the lazy tensor (PendingFin); 0: one launch each
         self.inline_fin = os.environ.get("ISA_INLINE_FIN", "1") != "0"
-        self._pw_out: Dict[tuple, dict] = {}
-        self._pw_in: Dict[tuple, dict] = {}      # conv input -> the same records: residual gradients ride along
+        self._pw_out: Dict[tuple, ConvFusion] = {}
+        self._pw_in: Dict[tuple, ConvFusion] = {}      # conv input -> the same records: residual gradients ride along
         # eval-mode BN constants per layer: persistent buffers (a captured inference graph reads them), recomputed in
         # place by refresh_eval_bn() after the parameters changed
         self.eval_bn_cache: Dict[str, tuple] = {}
@@ -687,10 +706,21 @@ class Engine:
             L.check(self.lib.isa_bn_running_update(arr, len(run), self.BN_MOMENTUM, self.st()), "isa_bn_running_update")
         self.bn_running_queue = []
 
+    def running_ptrs(self, pre):
+        P = self.params
+        return P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var")
+
+    def bn_finalize(self, stats, count, pre, running, scale, shift, mean, invstd, c, groups, rep, label):
+        """The stand-alone isa_bn_finalize launch.  stats = None: eval constants (count unread); running = None: leave them."""
+        P = self.params
+        rm, rv = running or (None, None)
+        L.check(self.lib.isa_bn_finalize(L.ptr(stats), count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"), rm, rv,
+                                         self.BN_MOMENTUM, self.BN_EPS, L.ptr(scale), L.ptr(shift), L.ptr(mean),
+                                         L.ptr(invstd), c, groups, rep, self.st()), label)
+
     def _finalize_train(self, stats, count, pre, c, scale, shift, mean, invstd, groups=1):
         """Train-mode finalize of one BatchNorm.  With inline_fin (default) nothing is launched here: the PendingFin that is
         returned travels with the lazy tensor and its first consumer does the work (see PendingFin)."""
-        P = self.params
         defer = self.defer_bn_running
         rep = self.bn_repeat
         assert not (defer and (groups > 1 or rep > 1)), "deferred running statistics are a single-group mechanism"
@@ -698,14 +728,11 @@ class Engine:
         if self.inline_fin:
             fin = PendingFin(self, stats, count, pre, c, scale, shift, mean, invstd, groups, rep, running_taken=defer)
         else:
-            L.check(self.lib.isa_bn_finalize(L.ptr(stats), count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"),
-                                             None if defer else P.ptr(pre + ".running_mean"),
-                                             None if defer else P.ptr(pre + ".running_var"), self.BN_MOMENTUM, self.BN_EPS,
-                                             L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), c, groups, rep, self.st()),
-                    "isa_bn_finalize")
+            self.bn_finalize(stats, count, pre, None if defer else self.running_ptrs(pre), scale, shift, mean, invstd,
+                             c, groups, rep, "isa_bn_finalize")
         if defer:
             self.bn_running_queue.append((stats, count, pre, c))
-        P.int_buffers[pre + ".num_batches_tracked"] += groups * rep
+        self.params.int_buffers[pre + ".num_batches_tracked"] += groups * rep
         return fin
 
     def defer_handle(self):
@@ -727,12 +754,9 @@ class Engine:
 
     def refresh_eval_bn(self):
         """Recompute the cached eval-mode BN constants in place (same buffers: captured graphs keep reading them)."""
-        P = self.params
-        for pre, (scale, shift, mean, invstd) in self.eval_bn_cache.items():
-            L.check(self.lib.isa_bn_finalize(None, 1.0, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"),
-                                             P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var"),
-                                             self.BN_MOMENTUM, self.BN_EPS, L.ptr(scale), L.ptr(shift), L.ptr(mean),
-                                             L.ptr(invstd), scale.numel(), 1, 1, self.st()), "isa_bn_finalize(eval refresh)")
+        for pre, consts in self.eval_bn_cache.items():
+            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *consts, consts[0].numel(), 1, 1,
+                             "isa_bn_finalize(eval refresh)")
         self.eval_bn_stale = False
 
     def scratch(self, numel) -> torch.Tensor:
@@ -805,13 +829,9 @@ class Engine:
         weight version and cached (captured graphs keep reading the same buffers)."""
         cached = self.eval_bn_cache.get(pre)
         if cached is None:
-            P = self.params
             cached = tuple(torch.empty(c, dtype=torch.float32, device=self.device) for _ in range(4))
             self.eval_bn_cache[pre] = cached
-            L.check(self.lib.isa_bn_finalize(None, 1.0, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"),
-                                             P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var"),
-                                             self.BN_MOMENTUM, self.BN_EPS, L.ptr(cached[0]), L.ptr(cached[1]),
-                                             L.ptr(cached[2]), L.ptr(cached[3]), c, 1, 1, self.st()), "isa_bn_finalize")
+            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *cached, c, 1, 1, "isa_bn_finalize")
             self._eval_bn_filled(pre)
         else:
             self._eval_bn_wait(pre)
@@ -865,46 +885,32 @@ class Engine:
         st = self.scratch(2 * out.c * STAT_R * out.groups) if stats else None
         job = (x, reg, bias, out, in_mode, out_mode, st)
         self._launch_conv(*job)
-        self._last_conv = dict(reg=reg, in_mode=in_mode)
         if self.record and record_bwd:
-            info = None
+            rec = None
             if self.fuse_pw_bn and self.bn_train and self.dtype == torch.bfloat16 and taps == 1 and not transposed \
                     and kmap is None and bias is None and x.needs_grad and out.c <= 64 and x.c <= 64 \
                     and out.c % 8 == 0 and x.c % 8 == 0 and (x.pro is None or x.pro.bscale is None):
-                xb = getattr(x, "bn", None)
-                ok_x = xb is not None and xb["train"] and self.tape.last_fn() is xb.get("bwd_fn")
-                info = dict(xbn=xb if ok_x else None, ybn=None, addend=None, done=False)
-                self._pw_out[(out.buf.data_ptr(), out.c0, out.c)] = info
-                self._pw_in[(x.buf.data_ptr(), x.c0, x.c)] = info
+                rec = self._pw_out[self._key(out)] = self._pw_in[self._key(x)] = ConvFusion(self._bn_just_recorded(x))
+            # weight gradient: K is axis 1 of [N, K, kh, kw] and axis 0 of a ConvTranspose2d's [K, Co, 2, 2], whose bias
+            # gradient (sum over all output pixels) rides in the four quadrant slabs
+            wshape = self.params.shapes[wname]
+            wg_in, ksrc = (L.IN_1X1, wshape[0]) if transposed else (in_mode, wshape[1])
 
             def bwd():
-                if info is not None:
-                    info["done"] = True
-                    if info["ybn"] is not None:
-                        self._fused_pw_backward(x, wname, info)
+                if rec is not None:
+                    rec.done = True
+                    if rec.ybn is not None:
+                        self._fused_pw_backward(x, wname, rec)
                         return
-                    if info["addend"] is not None:        # deferred residual gradient, conv ended up unfused
-                        acc0 = self.grads.claim(x, self)
-                        L.check(self.lib.isa_axpy(info["addend"].d(), self.grads.grad_of(x).d(), 1.0, acc0, self.st()),
-                                "isa_axpy(res, deferred)")
+                    self._flush_addend(x, rec)
                 dy = self.grads.grad_of(out)
                 pk = self.packer
-                def wgrad(ws):
-                    if transposed:      # the bias gradient (sum over all output pixels) rides in the four quadrant slabs
-                        L.check(self.lib.isa_conv_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
-                                                        self.params.gptr(bias) if bias else None,
-                                                        L.IN_1X1, L.OUT_SHUFFLE2, pk.kmap_ptr(reg["fwd"]),
-                                                        self.params.shapes[wname][0], L.ptr(ws), ws.numel(),
-                                                        self.defer_handle(), self.st()), "isa_conv_wgrad")
-                    else:
-                        if self.profile:
-                            self.next_bytes = (x.n * x.h * x.w * x.c + dy.n * dy.h * dy.w * dy.c) * x.buf.element_size()
-                        L.check(self.lib.isa_conv_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
-                                                        self.params.gptr(bias) if bias else None, in_mode,
-                                                        L.OUT_PLAIN, pk.kmap_ptr(reg["fwd"]),
-                                                        self.params.shapes[wname][1], L.ptr(ws), ws.numel(),
-                                                        self.defer_handle(), self.st()), "isa_conv_wgrad")
-                wgrad(self.ws)
+                if self.profile and not transposed:
+                    self.next_bytes = (x.n * x.h * x.w * x.c + dy.n * dy.h * dy.w * dy.c) * x.buf.element_size()
+                L.check(self.lib.isa_conv_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
+                                                self.params.gptr(bias) if bias else None, wg_in, out_mode,
+                                                pk.kmap_ptr(reg["fwd"]), ksrc, L.ptr(self.ws), self.ws.numel(),
+                                                self.defer_handle(), self.st()), "isa_conv_wgrad")
                 if x.needs_grad:
                     acc = self.grads.claim(x, self)
                     dx = self.grads.grad_of(x)
@@ -923,29 +929,47 @@ class Engine:
 
     def _bn_desc(self, b, red=None, out_red=None, with_params=True):
         P = self.params
-        return L.IsaBnBwd(L.addr(b["scale"]), L.addr(b["shift"]), L.addr(b["mean"]), L.addr(b["invstd"]),
-                          L.addr(red), L.addr(out_red),
-                          P.gptr(b["pre"] + ".weight").value if with_params else None,
-                          P.gptr(b["pre"] + ".bias").value if with_params else None, b["count"], b["act"])
+        return L.IsaBnBwd(L.addr(b.scale), L.addr(b.shift), L.addr(b.mean), L.addr(b.invstd), L.addr(red), L.addr(out_red),
+                          P.gptr(b.pre + ".weight").value if with_params else None,
+                          P.gptr(b.pre + ".bias").value if with_params else None, b.count, b.act)
 
-    def _fused_pw_backward(self, x: Act, wname, info):
+    @staticmethod
+    def _key(a: Act):       # of a tensor in _dw_out / _pw_out / _pw_in
+        return (a.buf.data_ptr(), a.c0, a.c)
+
+    def _bn_just_recorded(self, x: Act):
+        """The train-mode BN that produced x, if recorded immediately before the conv being recorded now (every other consumer
+        of x has then accumulated its gradient when that conv's backward runs, so it can produce the BN's reduce), else None."""
+        xb = x.bn
+        return xb if (xb is not None and xb.train and self.tape.last_fn() is xb.bwd_fn) else None
+
+    def _fused_descs(self, x: Act, rec):
+        """(ydesc, xdesc or None) of a fused backward launch; the reduce of x's BN goes to fresh scratch, left in its red_done."""
+        ydesc, xdesc = self._bn_desc(rec.ybn, red=rec.yred), None
+        if rec.xbn is not None:
+            rec.xbn.red_done = self.scratch(2 * x.c * STAT_R * x.groups)
+            xdesc = self._bn_desc(rec.xbn, out_red=rec.xbn.red_done, with_params=False)
+        return ydesc, xdesc
+
+    def _flush_addend(self, x: Act, rec):
+        """Deferred residual gradient, conv ended up unfused after all: add it to dx."""
+        if rec.addend is not None:
+            acc = self.grads.claim(x, self)
+            L.check(self.lib.isa_axpy(rec.addend.d(), self.grads.grad_of(x).d(), 1.0, acc, self.st()),
+                    "isa_axpy(res, deferred)")
+
+    def _fused_pw_backward(self, x: Act, wname, rec):
         """BN-apply of the conv's output BN + weight gradient + data gradient (+ reduce of the BN that
         produced x) in one pass: isa_conv1x1_bn_backward."""
-        yb, yred, g = info["ybn"]
-        xb = info["xbn"]
-        ydesc = self._bn_desc(yb, red=yred)
-        xdesc = None
-        if xb is not None:
-            xred = self.scratch(2 * x.c * STAT_R * x.groups)
-            xdesc = self._bn_desc(xb, out_red=xred, with_params=False)
-            xb["red_done"] = xred
+        ydesc, xdesc = self._fused_descs(x, rec)
         acc = self.grads.claim(x, self)
+        g = rec.g
         if self.profile:
             self.next_bytes = x.n * x.h * x.w * (2 * g.c + 2 * x.c) * x.buf.element_size()
         L.check(self.lib.isa_conv1x1_bn_backward(
-            g.d(), yb["raw"].d(), C.byref(ydesc), x.d(), x.p(), C.byref(xdesc) if xdesc is not None else None,
+            g.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(), C.byref(xdesc) if xdesc is not None else None,
             self.params.ptr(wname), self.params.gptr(wname), self.grads.grad_of(x).d(), acc,
-            info["addend"].d() if info["addend"] is not None else None,
+            rec.addend.d() if rec.addend is not None else None,
             L.ptr(self.ws), self.ws.numel(), self.defer_handle(), self.st()), "isa_conv1x1_bn_backward")
 
     def _launch_conv(self, x, reg, bias, out, in_mode, out_mode, st):
@@ -976,47 +1000,33 @@ class Engine:
                                        self.params.ptr(bias) if bias else None, out.d(), L.ptr(st), self.st()),
                 "isa_dwconv3x3")
         if self.record:
-            info = None
+            rec = None
             if self.fuse_dw_bn and self.bn_train and x.c % 8 == 0 and bias is None and x.needs_grad \
                     and (x.pro is None or x.pro.bscale is None):
                 # BN(out)'s backward may leave its "apply" to this conv's backward (see bn()); BN(x)'s
-                # "reduce" can be produced here when that BN was recorded immediately before this conv,
-                # so every other consumer of x has already accumulated its gradient when we run
-                xb = getattr(x, "bn", None)
-                ok_x = xb is not None and xb["train"] and self.tape.last_fn() is xb.get("bwd_fn")
-                info = dict(xbn=xb if ok_x else None, ybn=None, addend=None, done=False)
-                self._dw_out[(out.buf.data_ptr(), out.c0, out.c)] = info
-                if x.pro is None and xb is None:                                  # plain tensor: residual gradients may ride along
-                    self._pw_in.setdefault((x.buf.data_ptr(), x.c0, x.c), info)
+                # "reduce" can be produced here (see _bn_just_recorded)
+                rec = self._dw_out[self._key(out)] = ConvFusion(self._bn_just_recorded(x))
+                if x.pro is None and x.bn is None:                                # plain tensor: residual gradients may ride along
+                    self._pw_in.setdefault(self._key(x), rec)
 
             def bwd():
                 dy = self.grads.grad_of(out)
                 nb = x.n * x.h * x.w * x.c * x.buf.element_size()
-                if info is not None:
-                    info["done"] = True
-                    if info["ybn"] is None and info["addend"] is not None:    # deferred residual gradient, unfused after all
-                        acc0 = self.grads.claim(x, self)
-                        L.check(self.lib.isa_axpy(info["addend"].d(), self.grads.grad_of(x).d(), 1.0, acc0, self.st()),
-                                "isa_axpy(res, deferred)")
-                if info is not None and info["ybn"] is not None:
-                    yb, yred = info["ybn"]
-                    xb = info["xbn"]
-                    ydesc = self._bn_desc(yb, red=yred)
-                    xdesc = None
-                    if xb is not None:
-                        xred = self.scratch(2 * x.c * STAT_R * x.groups)
-                        xdesc = self._bn_desc(xb, out_red=xred, with_params=False)
-                        xb["red_done"] = xred
-                    acc = self.grads.claim(x, self)
-                    if self.profile:
-                        self.next_bytes = 4 * nb
-                    L.check(self.lib.isa_dwconv3x3_bn_backward(
-                        dy.d(), yb["raw"].d(), C.byref(ydesc), x.d(), x.p(),
-                        C.byref(xdesc) if xdesc is not None else None, self.packer.ptr(reg["dgrad"]),
-                        self.params.gptr(wname), self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
-                        info["addend"].d() if info["addend"] is not None else None,
-                        L.ptr(self.ws), self.ws.numel(), self.defer_handle(), self.st()), "isa_dwconv3x3_bn_backward")
-                    return
+                if rec is not None:
+                    rec.done = True
+                    if rec.ybn is not None:
+                        ydesc, xdesc = self._fused_descs(x, rec)
+                        acc = self.grads.claim(x, self)
+                        if self.profile:
+                            self.next_bytes = 4 * nb
+                        L.check(self.lib.isa_dwconv3x3_bn_backward(
+                            dy.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
+                            C.byref(xdesc) if xdesc is not None else None, self.packer.ptr(reg["dgrad"]),
+                            self.params.gptr(wname), self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
+                            rec.addend.d() if rec.addend is not None else None,
+                            L.ptr(self.ws), self.ws.numel(), self.defer_handle(), self.st()), "isa_dwconv3x3_bn_backward")
+                        return
+                    self._flush_addend(x, rec)
                 if self.profile:
                     self.next_bytes = 2 * nb
                 L.check(self.lib.isa_dwconv3x3_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
@@ -1034,54 +1044,42 @@ class Engine:
         return out, st
 
     # ------------------------------------------------------------------ batch norm
+    def _bn_layer(self, raw: Act, stats, pre, act, count):
+        """(BnLayer, pending finalize or None): per-step constants in train mode, eval_bn's cached ones in eval mode."""
+        c, G = raw.c, raw.groups
+        count = float(raw.n // G * raw.h * raw.w) if count is None else float(count)     # per statistic group
+        train = self.bn_train
+        assert train or G == 1, "statistic groups exist in train mode only (eval statistics are shared)"
+        fin = None
+        if train:
+            scale, shift, mean, invstd = (self.f32(G * c) for _ in range(4))
+            fin = self._finalize_train(stats, count, pre, c, scale, shift, mean, invstd, G)
+        else:
+            scale, shift, mean, invstd = self.eval_bn(pre, c)
+        return BnLayer(pre, scale, shift, mean, invstd, act, count, train, raw), fin
+
     def bn(self, raw: Act, stats, pre, act, count=None) -> Act:
         """Lazy BN(+act): returns a view of `raw` whose prologue applies scale/shift/act.
         Gradient w.r.t. the lazy tensor is converted in place to the gradient w.r.t. `raw`."""
-        c = raw.c
-        G = raw.groups
-        count = float(raw.n // G * raw.h * raw.w) if count is None else float(count)     # per statistic group
-        P = self.params
-        train = self.bn_train
-        assert train or G == 1, "statistic groups exist in train mode only (eval statistics are shared)"
-        cached = None if train else self.eval_bn_cache.get(pre)
-        if cached is not None:
-            scale, shift, mean, invstd = cached
-        elif train:
-            scale, shift, mean, invstd = (self.f32(G * c) for _ in range(4))
-        else:       # eval: constants of the running statistics, computed once per weight version
-            scale, shift, mean, invstd = (torch.empty(c, dtype=torch.float32, device=self.device) for _ in range(4))
-            self.eval_bn_cache[pre] = (scale, shift, mean, invstd)
-        fin = None
-        if train:
-            fin = self._finalize_train(stats, count, pre, c, scale, shift, mean, invstd, G)
-        elif cached is None:
-            L.check(self.lib.isa_bn_finalize(None, count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"),
-                                             P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var"),
-                                             self.BN_MOMENTUM, self.BN_EPS, L.ptr(scale), L.ptr(shift), L.ptr(mean),
-                                             L.ptr(invstd), c, 1, 1, self.st()), "isa_bn_finalize")
-            self._eval_bn_filled(pre)
-        else:
-            self._eval_bn_wait(pre)
-        lazy = raw.with_pro(Pro(scale, shift, act, fin=fin))
-        lazy.bn = dict(pre=pre, scale=scale, shift=shift, mean=mean, invstd=invstd, act=act, count=count,
-                       train=train, raw=raw)
+        b, fin = self._bn_layer(raw, stats, pre, act, count)
+        lazy = raw.with_pro(Pro(b.scale, b.shift, act, fin=fin))
+        lazy.bn = b
         if self.record:
-            key = (raw.buf.data_ptr(), raw.c0, raw.c)
-            dw = self._dw_out.get(key) if train else None
-            pw = self._pw_out.get(key) if train else None
+            # raw came from a depthwise conv or from a small 1x1 conv: reduce here, apply inside that conv's backward
+            rec = None
+            if b.train:
+                key = self._key(raw)
+                rec = self._dw_out.get(key)
+                if rec is None:
+                    rec = self._pw_out.get(key)
 
             def bwd():
                 g = self.grads.grad_of(raw)
-                if dw is not None:          # raw came from a depthwise conv: reduce here, apply inside its backward
-                    red = self._bn_backward(lazy, g, g, None, do_apply=False)
-                    dw["ybn"] = (lazy.bn, red)
-                    return
-                if pw is not None:          # ... or from a small 1x1 conv
-                    red = self._bn_backward(lazy, g, g, None, do_apply=False)
-                    pw["ybn"] = (lazy.bn, red, g)
+                if rec is not None:
+                    rec.ybn, rec.yred, rec.g = b, self._bn_backward(lazy, g, g, None, do_apply=False), g
                     return
                 self._bn_backward(lazy, g, g, None)
-            lazy.bn["bwd_fn"] = bwd
+            b.bwd_fn = bwd
             self.tape.append(bwd)
         return lazy
 
@@ -1092,23 +1090,22 @@ class Engine:
         statistics), though the apply does not subtract them from the data gradient."""
         b = lazy.bn
         P = self.params
-        red = b.pop("red_done", None)
+        red, b.red_done = b.red_done, None
         nb = lazy.n * lazy.h * lazy.w * lazy.c * lazy.buf.element_size()
         if red is None:
             red = self.scratch(2 * lazy.c * STAT_R * lazy.groups)
             if self.profile:
                 self.next_bytes = 2 * nb
-            L.check(self.lib.isa_bn_bwd_reduce(dt.d(), b["raw"].d(), L.ptr(b["scale"]), L.ptr(b["shift"]),
-                                               L.ptr(b["mean"]), L.ptr(b["invstd"]), b["act"], L.ptr(bscale),
-                                               L.ptr(red), self.st()), "isa_bn_bwd_reduce")
+            L.check(self.lib.isa_bn_bwd_reduce(dt.d(), b.raw.d(), L.ptr(b.scale), L.ptr(b.shift), L.ptr(b.mean),
+                                               L.ptr(b.invstd), b.act, L.ptr(bscale), L.ptr(red), self.st()),
+                    "isa_bn_bwd_reduce")
         if not do_apply:
             return red
         if self.profile:
             self.next_bytes = 3 * nb
-        L.check(self.lib.isa_bn_bwd_apply(dt.d(), b["raw"].d(), L.ptr(b["scale"]), L.ptr(b["shift"]),
-                                          L.ptr(b["mean"]), L.ptr(b["invstd"]), b["act"], L.ptr(bscale),
-                                          P.ptr(b["pre"] + ".weight"), L.ptr(red), b["count"], 1 if b["train"] else 0,
-                                          dy.d(), P.gptr(b["pre"] + ".weight"), P.gptr(b["pre"] + ".bias"),
+        L.check(self.lib.isa_bn_bwd_apply(dt.d(), b.raw.d(), L.ptr(b.scale), L.ptr(b.shift), L.ptr(b.mean), L.ptr(b.invstd),
+                                          b.act, L.ptr(bscale), P.ptr(b.pre + ".weight"), L.ptr(red), b.count,
+                                          1 if b.train else 0, dy.d(), P.gptr(b.pre + ".weight"), P.gptr(b.pre + ".bias"),
                                           self.st()), "isa_bn_bwd_apply")
         return red
 
@@ -1117,41 +1114,16 @@ class Engine:
         """Materialising BN: out = (act(BN(raw)) * bscale (+ res) (+ res2)) * oscale.
         Broadcast form (train mode): raw / res hold one statistic group, out has G of them with a per-image oscale each
         (isa_affine_act_res); the gradient of the shared value is the oscale-weighted sum over the groups."""
-        c = raw.c
-        G = raw.groups
-        count = float(raw.n // G * raw.h * raw.w) if count is None else float(count)     # per statistic group
-        P = self.params
-        train = self.bn_train
-        assert train or G == 1, "statistic groups exist in train mode only (eval statistics are shared)"
-        cached = None if train else self.eval_bn_cache.get(pre)
-        if cached is not None:
-            scale, shift, mean, invstd = cached
-        elif train:
-            scale, shift, mean, invstd = (self.f32(G * c) for _ in range(4))
-        else:       # eval: constants of the running statistics, computed once per weight version
-            scale, shift, mean, invstd = (torch.empty(c, dtype=torch.float32, device=self.device) for _ in range(4))
-            self.eval_bn_cache[pre] = (scale, shift, mean, invstd)
-        fin = None
-        if train:
-            fin = self._finalize_train(stats, count, pre, c, scale, shift, mean, invstd, G)
-        elif cached is None:
-            L.check(self.lib.isa_bn_finalize(None, count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"),
-                                             P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var"),
-                                             self.BN_MOMENTUM, self.BN_EPS, L.ptr(scale), L.ptr(shift), L.ptr(mean),
-                                             L.ptr(invstd), c, 1, 1, self.st()), "isa_bn_finalize")
-            self._eval_bn_filled(pre)
-        else:
-            self._eval_bn_wait(pre)
-        lazy = raw.with_pro(Pro(scale, shift, act, bscale, fin=fin))
-        lazy.bn = dict(pre=pre, scale=scale, shift=shift, mean=mean, invstd=invstd, act=act, count=count,
-                       train=train, raw=raw)
+        b, fin = self._bn_layer(raw, stats, pre, act, count)
+        lazy = raw.with_pro(Pro(b.scale, b.shift, act, bscale, fin=fin))
+        lazy.bn = b
         if self.profile:
             self.next_bytes = (2 + (res is not None) + (res2 is not None)) * raw.n * raw.h * raw.w * raw.c * raw.buf.element_size()
         L.check(self.lib.isa_affine_act_res(lazy.d(), lazy.p_fin(), res.d() if res is not None else None,
                                             res2.d() if res2 is not None else None, L.ptr(oscale), out.d(),
                                             self.st()), "isa_affine_act_res")
         if self.record:
-            pw = self._pw_out.get((raw.buf.data_ptr(), raw.c0, raw.c)) if (train and bscale is None) else None
+            pw = self._pw_out.get(self._key(raw)) if (b.train and bscale is None) else None
 
             bcast = out.n != raw.n
             assert not bcast or (oscale is not None and res2 is None and out.n == out.groups * raw.n and raw.groups == 1)
@@ -1164,16 +1136,15 @@ class Engine:
                     L.check(self.lib.isa_scale_bc(dout.d(), L.ptr(oscale), dsum.d(), 0, self.st()), "isa_scale_bc")
                 for r in (res, res2):
                     if r is not None and r.needs_grad:
-                        pin = self._pw_in.get((r.buf.data_ptr(), r.c0, r.c))
-                        if pin is not None and not pin["done"] and pin["addend"] is None:
-                            pin["addend"] = dsum          # the consuming 1x1 conv's backward adds it to dx itself
+                        pin = self._pw_in.get(self._key(r))
+                        if pin is not None and not pin.done and pin.addend is None:
+                            pin.addend = dsum             # the consuming conv's backward adds it to dx itself
                             continue
                         acc = self.grads.claim(r, self)
                         L.check(self.lib.isa_axpy(dsum.d(), self.grads.grad_of(r).d(), 1.0, acc, self.st()),
                                 "isa_axpy(res)")
                 if pw is not None:                # the producing 1x1 conv's backward applies this BN on the fly
-                    red = self._bn_backward(lazy, dsum, None, None, do_apply=False)
-                    pw["ybn"] = (lazy.bn, red, dsum)
+                    pw.ybn, pw.yred, pw.g = b, self._bn_backward(lazy, dsum, None, None, do_apply=False), dsum
                     return
                 self.grads.claim(raw, self)       # single consumer: overwrite
                 self._bn_backward(lazy, dsum, self.grads.grad_of(raw), bscale)

@@ -92,10 +92,8 @@ class InstanceHead:
         if E.bn_train:
             L.check(E.lib.isa_scaled_stats(x.d(), L.ptr(beta), L.ptr(stats), E.st()), "isa_scaled_stats")
             P.int_buffers[pre + ".bn.num_batches_tracked"] += 1
-        L.check(E.lib.isa_bn_finalize(L.ptr(stats) if E.bn_train else None, float(n * Lp), P.ptr(pre + ".bn.weight"),
-                                      P.ptr(pre + ".bn.bias"), P.ptr(pre + ".bn.running_mean"),
-                                      P.ptr(pre + ".bn.running_var"), E.BN_MOMENTUM, E.BN_EPS, L.ptr(scale),
-                                      L.ptr(shift), L.ptr(mean), L.ptr(invstd), c, 1, 1, E.st()), "isa_bn_finalize")
+        E.bn_finalize(stats if E.bn_train else None, float(n * Lp), pre + ".bn", E.running_ptrs(pre + ".bn"), scale, shift,
+                      mean, invstd, c, 1, 1, "isa_bn_finalize")
         out = E.new_act(n, x.h, x.w, c)
         L.check(E.lib.isa_sp_apply(x.d(), L.ptr(beta), L.ptr(sem), L.ptr(scale), L.ptr(shift), out.d(), E.st()),
                 "isa_sp_apply")

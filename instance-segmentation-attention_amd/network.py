@@ -157,7 +157,7 @@ class Network:
         gated = x_dec.with_pro(Pro(bscale=gate))
         sem = E.new_act(n, x_dec.h, x_dec.w, self.n_classes)
         E.conv(gated, "sem_seg_output.weight", sem, bias="sem_seg_output.bias", record_bwd=False)
-        reg = E._last_conv["reg"]
+        reg = E.reg_conv("sem_seg_output.weight")
         if E.record:
             def bwd():
                 # sem conv: weight/bias grads see x*gate; its data gradient is w.r.t. x*gate (dxa)

@@ -89,7 +89,7 @@ def test_constants_are_bit_identical_to_the_launch(dtype, consumer, G, rep, monk
             assert "isa_bn_finalize" not in calls, calls
         else:
             assert "isa_bn_finalize" in calls
-        consts = [lazy_bn[k].clone().cpu() for k in ("scale", "shift", "mean", "invstd")] if lazy_bn is not None else []
+        consts = [getattr(lazy_bn, k).clone().cpu() for k in ("scale", "shift", "mean", "invstd")] if lazy_bn is not None else []
         res[mode] = (out.nchw().float().cpu(), consts, eng.params.view("bn.running_mean").clone().cpu(),
                      eng.params.view("bn.running_var").clone().cpu(), eng.params.int_buffers["bn.num_batches_tracked"])
     a, b = res["1"], res["0"]
@@ -197,7 +197,7 @@ def test_entry_points_without_the_kernel_form_launch_the_finalize_themselves(mon
                 L.check(eng.lib.isa_conv_wgrad(lazy.d(), lazy.p_fin(), to_act(Act, dy, dtype).d(), L.ptr(out), None, L.IN_1X1,
                                                L.OUT_PLAIN, None, 0, L.ptr(ws), ws.numel(), None, eng.st()), "isa_conv_wgrad")
             torch.cuda.synchronize()
-            outs += [out.cpu(), lazy.bn["scale"].clone().cpu(), lazy.bn["invstd"].clone().cpu(),
+            outs += [out.cpu(), lazy.bn.scale.clone().cpu(), lazy.bn.invstd.clone().cpu(),
                      eng.params.view("bn.running_var").clone().cpu()]
         res[mode] = outs
     for i, (u, v) in enumerate(zip(res["1"], res["0"])):
