@@ -461,6 +461,30 @@ int isa_sem_loss_k_grad(const isa_tensor* logits, const uint8_t* labels, const f
  * (sem_seg_argmax, reseg.py:118); the first maximum wins, as in torch.argmax.  Either output may be NULL, not both. */
 int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t hw, uint8_t* labels, float* argmax_map,
                            void* stream);
+/* ---- scoring K-class semantic predictions on the device: confusion matrix, IoU, Dice, pixel accuracy ------------------
+ * Both entries check every argument before they launch or clear anything (ISA_EINVAL / ISA_EALIGN / ISA_EDTYPE), are
+ * asynchronous on `stream` and allocate nothing.  2 <= K <= ISA_SEM_MAX_CLASSES, n <= 65535.
+ * isa_sem_confusion: one pass over the logits NHWC [n,h,w,c] (c == K, ld a multiple of 8, bf16 | fp32, 16-byte aligned:
+ *   the layout of isa_sem_loss_k_sums); h*w % 4 == 0.  The prediction of a pixel is the arg-max over channels 0..K-1: the
+ *   first maximum wins, NaN counts as the maximum (so the first NaN channel wins; the rule of isa_chan_argmax and
+ *   torch.argmax), all -inf gives class 0.  Channels K..ld-1 are padding and never take part, whatever they hold.
+ *   class_map (uint8 [n, h*w], 4-byte aligned, or NULL) receives the prediction of every pixel.
+ *   labels (uint8 [n, h*w], 4-byte aligned, or NULL; not both NULL): conf[i][t][p] (int64 [n][K][K], 8-byte aligned)
+ *   counts the pixels of image i with label t and prediction p; a pixel with label >= K is counted in oob[i] (int32 [n])
+ *   instead.  The entry zeroes conf and oob on the stream itself.  With labels == NULL conf and oob are not touched and
+ *   may be NULL.  A row is shared by up to ISA_ROW_CHUNKS workgroups that add their non-zero counters with integer
+ *   atomics: the result does not depend on the order in which they run.
+ * isa_sem_scores: out[i][0 .. 3+2K] (double, 8-byte aligned) from conf[i], one workgroup per image (n = 1 on a summed
+ *   matrix scores a dataset total).  Per class c: tp = conf[c][c], gt = sum of row c, pr = sum of column c.
+ *     0: pixel accuracy trace / total (NaN when total == 0)
+ *     1: mean IoU over the classes with gt + pr - tp > 0, summed in class order (NaN when there is none)
+ *     2: mean Dice over the same classes          3: the number of those classes
+ *     4 .. 4+K-1: IoU[c] = tp / (gt + pr - tp), NaN for a class absent from both maps
+ *     4+K .. 4+2K-1: Dice[c] = 2 tp / (gt + pr), same NaN rule
+ *   Every per-class value is one correctly rounded double division of exact integers (sums below 2^53). */
+int isa_sem_confusion(const isa_tensor* logits, const uint8_t* labels, int32_t K, int64_t* conf, int32_t* oob,
+                      uint8_t* class_map, void* stream);
+int isa_sem_scores(const int64_t* conf, int32_t n, int32_t K, double* out, void* stream);
 int isa_ins_softmax_bwd(const float* alpha, const int64_t* ins, const int32_t* idx, const int32_t* s_t,
                         const float* adv, int32_t n, int32_t nobj, int64_t L, float* dmerge /*[nsrc, L]*/, int32_t nsrc,
                         void* stream);

@@ -165,6 +165,9 @@ SIGNATURES = {
     "isa_labels_from_planes": [VP, I32, I32, I32, I64, VP, VP],
     "isa_label_pair_hist": [VP, VP, I32, I64, I32, I32, VP, VP, I32, VP],
     "isa_instance_scores": [VP, I32, I32, I32, VP, VP, VP, VP],
+    # scoring K-class semantic predictions (ReSeg.class_map, ReSeg.score_semantic)
+    "isa_sem_confusion": [P_T, VP, I32, VP, VP, VP, VP],
+    "isa_sem_scores": [VP, I32, I32, VP, VP],
 }
 
 

@@ -35,6 +35,9 @@ class Model(object):
         self.lr_scheduler = None
         # fit(): also segment and score every validation minibatch (SBD, |DiC|, FG Dice -> validation_scores.log)
         self.val_scores = False
+        # fit(): also score the semantic prediction of every validation minibatch (confusion matrix on the device; mIoU,
+        # pixel accuracy, mean Dice of the epoch total -> validation_sem_scores.log)
+        self.val_sem_scores = False
 
     def __load_weights(self):
         if self.load_model_path != '':
@@ -90,6 +93,9 @@ class Model(object):
                     sem, _ = self.model.net.collate_targets(sem, ins)
                 costs = self.model.sem_costs(sem)         # the reference logs CE / Dice in validation too (model.py:255-269)
                 row.update(self.__sem_row(costs))
+                if self.val_sem_scores:                   # before the next forward: the logits live in this step's arena
+                    _, conf = self.model.score_semantic(sem, check=False)
+                    row['sem_conf'] = (conf.sum(0), self.model.last_sem_oob.sum())
                 if self.val_scores and self.use_instance_segmentation:
                     row['scores'] = self.__score_batch(batch, self.max_n_objects, check=False)
             return row
@@ -139,7 +145,7 @@ class Model(object):
             train_loader, test_loader, model_save_path, debug):
         assert criterion_type in ['CE', 'Dice', 'Multi']                       # model.py:364
         main = self.rank == 0                   # only rank 0 writes logs and checkpoints (parallel.py: policy)
-        tlog = vlog = slog = None
+        tlog = vlog = slog = mlog = None
         scoring = bool(self.val_scores) and self.use_instance_segmentation
         if main:
             os.makedirs(model_save_path, exist_ok=True)
@@ -149,6 +155,9 @@ class Model(object):
             if scoring:
                 slog = open(os.path.join(model_save_path, 'validation_scores.log'), 'w')
                 slog.write('Epoch,SBD,DiC,FG Dice\n')
+            if self.val_sem_scores:
+                mlog = open(os.path.join(model_save_path, 'validation_sem_scores.log'), 'w')
+                mlog.write('Epoch,mIoU,PixelAcc,mDice\n')
         self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
                                 criterion_type, class_weights, optimize_bg, train_cnn)
         best_val_cost = np.inf
@@ -201,10 +210,25 @@ class Model(object):
                 means = [parallel.mean_over_ranks(v, self.world) for v in means]
                 if main:
                     slog.write('{},{},{},{}\n'.format(epoch, *means)); slog.flush()
+            if self.val_sem_scores:
+                # the epoch-total confusion matrix: summed over this rank's minibatches, then over the ranks, then scored
+                K = self.n_classes
+                total = torch.zeros(K * K + 1, dtype=torch.int64, device=self.model.store.device)
+                for r in va:
+                    total[:K * K] += r['sem_conf'][0].reshape(-1)
+                    total[K * K] += r['sem_conf'][1]
+                total = parallel.sum_over_ranks(total, self.world)
+                got = torch.cat([self.model.semantic_scores(total[:K * K].view(K, K))[:3], total[K * K:].double()]).tolist()
+                if int(got[3]):
+                    raise ValueError("%d validation pixels carry a label outside the K = %d classes" % (int(got[3]), K))
+                if main:
+                    mlog.write('{},{},{},{}\n'.format(epoch, got[1], got[0], got[2])); mlog.flush()
         if main:
             tlog.close(); vlog.close()
             if slog is not None:
                 slog.close()
+            if mlog is not None:
+                mlog.close()
 
     # ------------------------------------------------------------------ inference (model.py:466-499)
     def predict(self, images):
@@ -217,6 +241,19 @@ class Model(object):
             raise RuntimeError("predict() needs a model built with use_instance_segmentation=False")
         m(False, images.contiguous())
         return m.net.softmax_nchw(m._last_sem).cpu()                          # softmax over classes (model.py:486)
+
+    def predict_classes(self, images):
+        """Class ids of a semantic-only model: a host uint8 tensor [b,h,w], the arg-max of predict()'s softmax (first
+        maximum wins), taken on the device from the logits (ReSeg.class_map) - one byte per pixel comes down, not the K
+        fp32 probabilities."""
+        assert len(images.size()) == 4  # b, c, h, w
+        self.model.eval()
+        m = self.model
+        if m.use_instance_seg:
+            raise RuntimeError("predict_classes() needs a model built with use_instance_segmentation=False")
+        with torch.no_grad():
+            m(False, images.contiguous())
+            return m.class_map().cpu()
 
     def predict_instances(self, images, max_objects=None):
         """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
@@ -258,3 +295,40 @@ class Model(object):
         per = host[:-5].reshape(-1, 8)
         return {'SBD': float(host[-5]), '|DiC|': float(host[-4]), 'FG Dice': float(host[-3]), 'n_images': per.shape[0],
                 'n_skipped': int(host[-2]), 'per_image': per}
+
+    def evaluate_semantic(self, loader):
+        """Semantic scores over a loader of (images, sem, ins, n_objects) batches, either target form (sem uint8 [B,H,W]
+        or one-hot int64 [B,K,H,W]), for semantic-only models and for the K = 2 semantic head of instance models: per
+        batch the backbone and the semantic head run and the confusion matrices are counted on the device
+        (ReSeg.score_semantic); the matrices are summed on the device; one device-to-host copy at the end.
+        Returns {'mIoU', 'Pixel Acc', 'mDice', 'IoU' [K], 'Dice' [K], 'confusion' int64 [K,K], 'n_images', 'per_image'
+        float64 [N, 4+2K]}.  The headline figures are those of the dataset-total confusion matrix (the usual
+        definition: the mean over the classes present of the IoU of the summed matrix), not means of per-image values;
+        per_image holds the rows of score_semantic.  An empty loader gives NaN and 0.  A label >= K raises ValueError.
+        It scores what the loader yields on THIS rank; reducing over ranks is left to the caller
+        (parallel.sum_over_ranks on 'confusion', then ReSeg.semantic_scores)."""
+        m = self.model
+        m.eval()
+        K = self.n_classes
+        dev = m.store.device
+        total = torch.zeros((K, K), dtype=torch.int64, device=dev)
+        n_oob = torch.zeros((), dtype=torch.int64, device=dev)
+        rows = []
+        for images, sem, _ins, _n in loader:
+            m._semantic_logits(images.to(dev).contiguous())
+            scores, conf = m.score_semantic(sem, check=False)
+            rows.append(scores)
+            total += conf.sum(0)
+            n_oob += m.last_sem_oob.sum()
+        per_image = torch.cat(rows) if rows else torch.zeros((0, 4 + 2 * K), dtype=torch.float64, device=dev)
+        head = m.semantic_scores(total)
+        host = torch.cat([per_image.reshape(-1), head, total.reshape(-1).double(), n_oob.double().view(1)]).cpu().numpy()
+        if int(host[-1]):
+            raise ValueError("%d pixels carry a label outside the K = %d classes 0..%d" % (int(host[-1]), K, K - 1))
+        w = 4 + 2 * K
+        n_img = per_image.shape[0]
+        head_h = host[n_img * w:(n_img + 1) * w]
+        confusion = host[(n_img + 1) * w:-1].astype(np.int64).reshape(K, K)        # counts below 2^53: exact in double
+        return {'mIoU': float(head_h[1]), 'Pixel Acc': float(head_h[0]), 'mDice': float(head_h[2]),
+                'IoU': head_h[4:4 + K].copy(), 'Dice': head_h[4 + K:].copy(), 'confusion': confusion,
+                'n_images': n_img, 'per_image': host[:n_img * w].reshape(n_img, w).copy()}

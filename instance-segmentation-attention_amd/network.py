@@ -243,6 +243,35 @@ class Network:
         L.check(E.lib.isa_chan_argmax(logits.d(), out.d(), E.st()), "isa_chan_argmax")
         return out
 
+    def class_map(self, sem: Act) -> torch.Tensor:
+        """uint8 class ids [n,h,w] of the logits `sem` on the device (isa_sem_confusion without labels): the arg-max over
+        the K channels, first maximum wins, NaN is the maximum.  A new tensor, not arena memory."""
+        E = self.E
+        out = torch.empty((sem.n, sem.h, sem.w), dtype=torch.uint8, device=sem.buf.device)
+        L.check(E.lib.isa_sem_confusion(sem.d(), None, sem.c, None, None, L.ptr(out), E.st()), "isa_sem_confusion")
+        return out
+
+    def sem_confusion(self, sem: Act, labels: torch.Tensor):
+        """(conf int64 [n,K,K], oob int32 [n]) of the logits `sem` against the uint8 label map [n,h,w] in one pass over
+        the logits: conf[i][t][p] pixels of image i with label t and predicted class p; labels >= K go to oob[i]."""
+        E = self.E
+        K = sem.c
+        assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == sem.n * sem.h * sem.w
+        conf = torch.empty((sem.n, K, K), dtype=torch.int64, device=sem.buf.device)
+        oob = torch.empty((sem.n,), dtype=torch.int32, device=sem.buf.device)
+        L.check(E.lib.isa_sem_confusion(sem.d(), L.ptr(labels), K, L.ptr(conf), L.ptr(oob), None, E.st()),
+                "isa_sem_confusion")
+        return conf, oob
+
+    def sem_scores(self, conf: torch.Tensor) -> torch.Tensor:
+        """double [n, 4+2K] from confusion matrices int64 [n,K,K] (isa_sem_scores): pixel accuracy, mean IoU, mean Dice,
+        classes present, IoU[K], Dice[K]."""
+        E = self.E
+        n, K = conf.shape[0], conf.shape[1]
+        out = torch.empty((n, 4 + 2 * K), dtype=torch.float64, device=conf.device)
+        L.check(E.lib.isa_sem_scores(L.ptr(conf), n, K, L.ptr(out), E.st()), "isa_sem_scores")
+        return out
+
     # ------------------------------------------------------------------ boundary
     def to_nhwc(self, x: torch.Tensor, c_pad=None) -> Act:
         """NCHW fp32 (reference layout) -> NHWC activation view."""

@@ -93,6 +93,17 @@ def mean_over_ranks(value: float, world=None, device=None) -> float:
     return float(t.item()) / world
 
 
+def sum_over_ranks(t: torch.Tensor, world=None) -> torch.Tensor:
+    """Sum of a tensor over the ranks (integer counters such as confusion matrices: exact, whatever the order).  A new
+    tensor on every rank; the identity (the tensor itself) at world 1."""
+    world = (dist.get_world_size() if dist.is_initialized() else 1) if world is None else world
+    if world <= 1:
+        return t
+    out = t.clone()
+    dist.all_reduce(out, op=dist.ReduceOp.SUM)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ data sharding
 def shard_batch(global_batch: int, rank: int, world: int):
     """Contiguous image shard of a global batch (weak scaling keeps per-rank batch fixed)."""

@@ -348,6 +348,73 @@ class ReSeg(nn.Module):
                                          % (int(row.sum()), torch.nonzero(row).view(-1).tolist(), limit))
             return out
 
+    # ------------------------------------------------------------------ scoring semantic predictions on the device
+    def _semantic_logits(self, x):
+        """Backbone and semantic head alone, eval mode: leaves the logits of `x` (either input form of forward) in
+        self._last_sem for class_map() / score_semantic().  Works for instance models too (their head is not run)."""
+        assert not self.training, "eval mode only (running BatchNorm statistics)"
+        E, net = self.engine, self.net
+        with torch.no_grad():
+            E.begin(bn_train=False, record=False, key=("semantic", tuple(x.shape), x.dtype))
+            if getattr(self, "_weights_dirty", True) and E.packer.entries:
+                E.packer.pack()
+            self._weights_dirty = False
+            x_dec, _ = net.unet(net.input_view(x))
+            self._last_sem = net.sem_head(x_dec)
+
+    def class_map(self):
+        """uint8 class ids [B,H,W] on the device from the logits of the LAST forward() or segment(): arg-max over the
+        classes, first maximum wins (isa_sem_confusion).  Must be called before the next forward (the logits live in
+        that step's arena), like sem_costs."""
+        sem = getattr(self, "_last_sem", None)
+        assert sem is not None, "class_map() follows a forward()"
+        with torch.no_grad():
+            return self.net.class_map(sem)
+
+    def score_semantic(self, sem_target, *, check=True):
+        """(scores double [B, 4+2K], conf int64 [B,K,K]), both on the device, of the LAST forward's (or segment's) logits
+        against sem_target: uint8 [B,H,W] class ids or one-hot int64 [B,C,H,W].  conf[b][t][p] counts the pixels of image b
+        with label t and predicted class p (the arg-max, never materialised: one pass over the logits); the score columns
+        are 0 pixel accuracy, 1 mean IoU and 2 mean Dice over the classes present in either map, 3 their number,
+        4..4+K-1 IoU per class, 4+K..4+2K-1 Dice per class (NaN for a class absent from both maps).
+        A pixel whose label is >= K is not counted; the per-image counts stay on the device in self.last_sem_oob (int32
+        [B]).  With check=True (one device read, the only host synchronisation of the call) any such pixel raises
+        ValueError.  Same lifetime rule as sem_costs: call it before the next forward."""
+        sem = getattr(self, "_last_sem", None)
+        assert sem is not None, "score_semantic() follows a forward()"
+        dev, K = self.store.device, self.n_classes
+        with torch.no_grad():
+            t = sem_target.to(dev).contiguous()
+            if t.dtype == torch.uint8:
+                assert tuple(t.shape) == (sem.n, sem.h, sem.w), "compact sem_target: uint8 [B,H,W]"
+                labels = t
+            else:
+                assert t.dtype == torch.int64 and t.dim() == 4 and tuple(t.shape[2:]) == (sem.h, sem.w) and \
+                    t.shape[0] == sem.n and 2 <= t.shape[1] <= 256, "sem_target: uint8 [B,H,W] or one-hot int64 [B,C,H,W]"
+                labels = torch.empty((sem.n, sem.h, sem.w), dtype=torch.uint8, device=dev)
+                L.check(self.engine.lib.isa_labels_from_onehot(L.ptr(t), sem.n, t.shape[1], sem.h * sem.w, L.ptr(labels),
+                                                               None, self.engine.st()), "isa_labels_from_onehot")
+            conf, oob = self.net.sem_confusion(sem, labels)
+            scores = self.net.sem_scores(conf)
+            self.last_sem_oob = oob
+            if check:
+                bad = oob.cpu()
+                if int(bad.sum()):
+                    raise ValueError("score_semantic: %d pixels of images %s carry a label outside the K = %d classes 0..%d"
+                                     % (int(bad.sum()), torch.nonzero(bad).view(-1).tolist(), K, K - 1))
+            return scores, conf
+
+    def semantic_scores(self, conf):
+        """The score rows of score_semantic for confusion matrices int64 [K,K] -> [4+2K] or [n,K,K] -> [n, 4+2K], on the
+        device (isa_sem_scores) - for a total summed over images, batches or ranks."""
+        with torch.no_grad():
+            c = conf.to(self.store.device)
+            assert c.dtype == torch.int64 and c.dim() in (2, 3) and c.shape[-1] == c.shape[-2], "int64 [K,K] or [n,K,K]"
+            if not 2 <= c.shape[-1] <= 32:
+                raise ValueError("2..32 classes, got %d" % c.shape[-1])
+            out = self.net.sem_scores(c.reshape(-1, c.shape[-1], c.shape[-1]).contiguous())
+            return out[0] if c.dim() == 2 else out
+
     # ------------------------------------------------------------------ forward
     def forward(self, training, *_input, selected_idx=None, injected_s_t=None, capture=None, _arena_key=None):
         """reseg.py:106-130.  (x) -> (sem_out, sem_argmax);  (x, sem_onehot[B,K,H,W] i64,

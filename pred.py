@@ -7,6 +7,8 @@ softmax(l)[1] > 0.5 is l1 > l0, i.e. the arg-max map the library already returns
 map is materialised.  `--synthetic` predicts one random image when no file is at hand (nothing ships with the repo).
 `--instances` builds the instance model and also writes <name>-ins_mask.png, <name>-ins_mask_color.png and
 <name>-n_objects.npy as pred_list.py --instances does (ReSeg.segment, at most `--max-objects` instances).
+`--n-classes K` (K > 2) loads a K-class semantic-only model and also writes <name>-sem_mask.png and
+<name>-sem_mask_color.png as pred_list.py --n-classes does (ReSeg.class_map); -fg_mask.png is then class != 0.
 The reference's hard-coded checkpoint and image paths (pred.py:25-26,112) are flags here."""
 import argparse
 import os
@@ -19,7 +21,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import isa_amd  # noqa: F401,E402
 from isa_amd.model import Model  # noqa: E402
-from pred_list import H, W, nearest_upsample, write_instances  # noqa: E402
+from pred_list import H, W, nearest_upsample, write_classes, write_instances  # noqa: E402
 
 
 def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
@@ -30,9 +32,13 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
                                                                # BILINEAR resize (prediction.py:37); ImageEx follows there
     net = model.model
     net.eval()
-    labels = None
+    labels = classes = None
     with torch.no_grad():
-        if instances:
+        if net.n_classes > 2:
+            net(False, x)
+            classes = net.class_map()[0].cpu().numpy()         # uint8 [H,W]: the arg-max taken on the device
+            sem_arg = torch.from_numpy((classes != 0).astype(np.float32))[None, None]
+        elif instances:
             _, sem_arg, labels, counts = net.segment(x, max_objects)
         else:
             _, sem_arg = net(False, x)                         # arg-max map == (softmax[:, 1] > 0.5)
@@ -42,6 +48,8 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, name + '-fg_mask.png')
     Image.fromarray(fg_seg_pred_norm).convert('P').save(path)              # pred.py:122-123
+    if classes is not None:
+        write_classes(out_dir, name, classes, image.shape[0], image.shape[1])
     if instances:
         write_instances(out_dir, name, labels[0].cpu().numpy(), int(counts[0]), image.shape[0], image.shape[1])
     return path
@@ -58,7 +66,13 @@ def main():
     parser.add_argument('--synthetic', action='store_true', help='predict one random 530x500 image instead of --image')
     parser.add_argument('--instances', action='store_true', help='also write -ins_mask.png, -ins_mask_color.png, -n_objects.npy')
     parser.add_argument('--max-objects', type=int, default=32, help='most instances with --instances (1..255)')
+    parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
+                        'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     opt = parser.parse_args()
+    if not 2 <= opt.n_classes <= 32:
+        parser.error('--n-classes must be in [2, 32]')
+    if opt.n_classes > 2 and opt.instances:
+        parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     assert opt.dataset in ['CVPPP', ]                          # pred.py:29
     assert opt.image or opt.synthetic, "give --image or --synthetic"
     if opt.synthetic:
@@ -67,8 +81,8 @@ def main():
         from PIL import Image
         assert os.path.isfile(opt.image), 'Image : {} does not exists!'.format(opt.image)
         image, name = np.asarray(Image.open(opt.image).convert('RGB')), os.path.splitext(os.path.basename(opt.image))[0]
-    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=opt.instances, load_model_path=opt.model,
-                  usegpu=True)
+    model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=opt.instances,
+                  load_model_path=opt.model, usegpu=True)
     path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects)
     print('wrote', path)
 

@@ -12,6 +12,9 @@ same nearest-neighbour rule), <name>-ins_mask_color.png (the labels through a fi
 The reference fills them from `Prediction.cluster`, which is dead at HEAD (its GT-free instance path
 raises UnboundLocalError, reseg.py:126); here they come from ReSeg.segment - one glimpse point and one decoder pass per
 object, at most `--max-objects` per image.  Without the flag nothing but the two foreground files is written.
+`--n-classes K` (K > 2) loads a K-class semantic-only model and also writes <name>-sem_mask.png (uint8 class ids at the
+original size, same nearest-neighbour rule) and <name>-sem_mask_color.png (the ids through the palette); -fg_mask.png is
+then (class != 0) * 255.  The class map is taken on the device from the logits (ReSeg.class_map): no softmax comes down.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -55,6 +58,15 @@ def write_instances(d, name, labels, n_objects, out_h, out_w):
     np.save(os.path.join(d, name + '-n_objects.npy'), np.int64(n_objects))
 
 
+def write_classes(d, name, classes, out_h, out_w):
+    """The two class-map files of one image of a K-class model.  classes: uint8 [h,w].  Returns the full-size map."""
+    from PIL import Image
+    full = nearest_upsample(classes, out_h, out_w).astype(np.uint8)
+    Image.fromarray(full).save(os.path.join(d, name + '-sem_mask.png'))
+    Image.fromarray(label_palette()[full]).save(os.path.join(d, name + '-sem_mask_color.png'))
+    return full
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--lst', default='', help='Text file that contains image paths')
@@ -66,7 +78,13 @@ def main():
     parser.add_argument('--synthetic', type=int, default=0, help='predict N random images instead of --lst')
     parser.add_argument('--instances', action='store_true', help='also write -ins_mask.png, -ins_mask_color.png, -n_objects.npy')
     parser.add_argument('--max-objects', type=int, default=32, help='most instances per image with --instances (1..255)')
+    parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
+                        'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     opt = parser.parse_args()
+    if not 2 <= opt.n_classes <= 32:
+        parser.error('--n-classes must be in [2, 32]')
+    if opt.n_classes > 2 and opt.instances:
+        parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     assert opt.dataset in ['CVPPP', ]                    # pred_list.py:26
     assert opt.lst or opt.synthetic, "give --lst or --synthetic N"
 
@@ -87,8 +105,8 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
 
     from PIL import Image
-    model = Model(opt.dataset, 'ReSeg', 2, 32, use_instance_segmentation=opt.instances, load_model_path=opt.model,
-                  usegpu=True)
+    model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=opt.instances,
+                  load_model_path=opt.model, usegpu=True)
     net = model.model
     net.eval()
     done = 0
@@ -96,8 +114,14 @@ def main():
         imgs = [ld() for ld in loaders[s:s + opt.batch]]
         # resize on the device (isa_resize_bilinear_u8, bit-identical to PIL's BILINEAR): one launch per source size
         x = torch.cat([resize_bilinear(torch.from_numpy(im[None]), (H, W)) for im in imgs])   # uint8 [B,H,W,3]; ImageEx follows
-        labels = counts = None
-        if opt.instances:
+        labels = counts = classes = None
+        if opt.n_classes > 2:
+            with torch.no_grad():
+                net(False, x)
+                classes = net.class_map()                # uint8 [B,H,W] on the device: one byte per pixel comes down
+            sem_arg = (classes != 0).to(torch.float32)[:, None]
+            classes = classes.cpu().numpy()
+        elif opt.instances:
             _, sem_arg, labels, counts = net.segment(x, opt.max_objects)
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         else:
@@ -112,6 +136,8 @@ def main():
             Image.fromarray(full.astype(np.uint8)).save(os.path.join(d, name + '-fg_mask.png'))
             if opt.instances:
                 write_instances(d, name, labels[i], counts[i], im.shape[0], im.shape[1])
+            if classes is not None:
+                write_classes(d, name, classes[i], im.shape[0], im.shape[1])
             done += 1
     print('wrote %d predictions under %s' % (done, out_dir))
 

@@ -53,6 +53,9 @@ def build_parser():
     parser.add_argument('--freeze-cnn', action='store_true', help='do not update the backbone (fit\'s train_cnn=False)')
     parser.add_argument('--val-scores', action='store_true', help='also segment and score every validation minibatch: '
                         'per-epoch SBD, |DiC| and FG Dice in <out>/validation_scores.log (Model.val_scores)')
+    parser.add_argument('--val-sem-scores', action='store_true', help='also score the semantic prediction of every validation '
+                        'minibatch: per-epoch mIoU, pixel accuracy and mean Dice of the epoch-total confusion matrix in '
+                        '<out>/validation_sem_scores.log (Model.val_sem_scores)')
     # AlignCollate's five photometric augmentations, which the reference ships disabled (training_settings.py:42-46 COLOR_JITTERING,
     # GAMMA_ADJUSTMENT, CHANNEL_SWAPPING, GRAYSCALING, RESOLUTION_DEGRADING): for the training loader of --data only
     parser.add_argument('--color-jitter', action='store_true', help='random brightness / contrast / saturation / hue')
@@ -109,6 +112,7 @@ def main(argv=None):
     model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=not opt.semantic_only,
                   load_model_path=opt.model, usegpu=True, dtype=torch.bfloat16 if opt.dtype == 'bf16' else torch.float32)
     model.val_scores = opt.val_scores
+    model.val_sem_scores = opt.val_sem_scores
     # every rank draws its own shard of each global batch (weights start identical: the model seed is not per rank)
     train_loader = SyntheticLoader(opt.iters_per_epoch, per_rank, opt.size, opt.size, seed=parallel.rank_seed(SEED, rank),
                                    compact=opt.compact_targets, n_classes=opt.n_classes)
