@@ -445,7 +445,8 @@ int isa_mask_loss_grad(const isa_tensor* pred, const float* target, const int64_
  * isa_mask_loss_sums + isa_sem_loss + isa_mask_loss_grad.  logits NHWC [B,H,W,K] (bf16 | fp32, ld a multiple of 8),
  * labels uint8 [B,H,W] with values < K (a precondition, not checked: the reference raises IndexError there).
  * cfg (device, read at run time so that a captured hipGraph follows in-place changes) [4 + K] floats:
- *   {use_ce, use_dice, optimize_bg, 0, w_0 .. w_{K-1}}; no class weights = all ones.
+ *   {use_ce, use_dice, optimize_bg, only_present (read by isa_lovasz_assemble alone), w_0 .. w_{K-1}}; no class
+ *   weights = all ones.
  * isa_sem_loss_k_sums: sums [B*3K + 2], zeroed by the caller: per image {sum p*g [K], sum p [K], sum g [K]}, then the
  *   batch's {sum w_y * nll, sum w_y}.
  * isa_sem_loss_k_assemble: one workgroup; coef [3*B*K + 1] for the gradient, scal[2] = {CE, Dice} (0 for a term the
@@ -457,6 +458,58 @@ int isa_sem_loss_k_assemble(const float* sums, const float* cfg, int32_t B, int3
                             void* stream);
 int isa_sem_loss_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
                         const isa_tensor* dlogits, int32_t accumulate, void* stream);
+/* ---- stable segmented key-value radix sort ---------------------------------------------------------------------------
+ * isa_segsort_kv_u32 sorts nseg independent segments of seglen keys each (segment s = elements [s*seglen, (s+1)*seglen)):
+ * uint32 keys ascending, compared on their bits [begin_bit, end_bit) only, every key carrying one uint32 value.  The sort
+ * is stable: keys equal on those bits keep their input order.  Input, output and temporaries are six buffers of
+ * nseg*seglen uint32 (4-byte aligned, ISA_EALIGN otherwise); the input is left as it is.  table: uint32 scratch of at
+ * least ISA_SEGSORT_TABLE_ELEMS(nseg, seglen) elements (ISA_ENOMEM when table_elems is smaller).  The seven buffers
+ * must not overlap; any two with the same address are refused.  LSD radix with 8-bit
+ * digits; a pass is tile histograms, an exclusive scan of [segment][digit][tile] (three launches: sums of 2048-entry
+ * chunks, their scan, the chunks; the sums live behind the digit table) and a stable scatter of tiles of ISA_SEGSORT_TILE
+ * keys.  Launch boundaries are the only synchronisation between workgroups, so the launch count
+ * 5 * ceil((end_bit - begin_bit) / 8) is fixed by the arguments and a captured hipGraph replays it.  Integer
+ * counters only: the output is bit-identical from run to run.  ISA_EINVAL, before anything is launched: a NULL or
+ * repeated buffer, nseg < 1, seglen < 1, nseg*seglen >= 2^31, or not 0 <= begin_bit < end_bit <= 32. */
+#define ISA_SEGSORT_TILE 2048
+#define ISA_SEGSORT_TILES(seglen) (((int64_t)(seglen) + ISA_SEGSORT_TILE - 1) / ISA_SEGSORT_TILE)
+#define ISA_SEGSORT_TABLE_ELEMS(nseg, seglen) \
+    ((int64_t)(nseg) * (256 * ISA_SEGSORT_TILES(seglen) + (ISA_SEGSORT_TILES(seglen) + 7) / 8))
+int isa_segsort_kv_u32(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out,
+                       int32_t nseg, int64_t seglen, int32_t begin_bit, int32_t end_bit, uint32_t* tmp_keys,
+                       uint32_t* tmp_vals, uint32_t* table, int64_t table_elems, void* stream);
+/* ---- Lovasz-Softmax semantic criterion (lovasz_softmax, losses/lovasz_losses.py:156-196) on the segmented sort ----------
+ * logits and labels as for isa_sem_loss_k_* (NHWC [B,H,W,K], bf16 | fp32, ld a multiple of 8, 16-byte aligned, groups 1,
+ * B <= 65535, B*H*W*K < 2^31; labels uint8 [B,H,W] with values < K); finite logits are a precondition (NaN gives an
+ * unspecified value, never an access out of range).  A segment is (class, whole batch), or (class, image) when
+ * per_image != 0; either way a range of one array laid out [K][B][H*W]: nimg = per_image ? B : 1 segments per class of
+ * seglen = H*W*B / nimg elements, segment index c*nimg + s.  cfg is the criterion's device buffer: optimize_bg = cfg[2]
+ * and only_present = cfg[3] are read at run time, so a captured hipGraph follows in-place changes; per_image fixes the
+ * launch geometry.  Every entry checks all arguments before it launches (ISA_EINVAL / ISA_EDTYPE / ISA_EALIGN).
+ * isa_lovasz_keys: classes [c0, c0+nc) -> keys / vals [nc][B][H*W]: key = 0x3F800000 - bits(e), e = |[label == c] - p_c|
+ *   clamped to [0,1] with p the fp32 softmax (ascending key = descending error, 30 key bits); value = pixel index inside
+ *   the segment, bit 31 set for a foreground pixel.  G [nc*nimg] int32, zeroed by the caller, receives the foreground
+ *   count of every segment (integer atomics).
+ * isa_lovasz_coef: keys / vals sorted by isa_segsort_kv_u32(.., 0, 30, ..).  Three launches: foreground counts of the
+ *   tiles (tile_counts, uint32 [nseg * ceil(seglen / ISA_SEGSORT_TILE)]), their exclusive scan per segment, then for the
+ *   element at rank r with cf / cb foreground / background elements before it, I = G - cf, U = G + cb:
+ *   g = 1/U (foreground) | I / (U (U+1)) (background) | G == 0: [r == 0], from the integer counts in double.
+ *   partial [nseg][tiles] (double) = the tile's sum of e*g, folded in a fixed order; gpix (float [nseg][seglen], may be
+ *   NULL: forward only) = sign*g in pixel order, sign -1 for a foreground pixel and +1 otherwise.
+ * isa_lovasz_assemble: one workgroup.  Counted classes: optimize_bg ? 0..K-1 : 1..K-1; only_present keeps those with
+ *   G > 0 in the segment.  scal[0] = mean over the kept classes (0 when none is kept), then over the images when
+ *   per_image; scale [K*nimg] = 1 / (kept * nimg) for a kept (class, segment), else 0; segloss [K*nimg] double scratch.
+ *   partial, G: those of all K classes, [K*nimg][tiles] and [K*nimg].
+ * isa_lovasz_grad: d_c = scale * gpix, d logits_k = p_k (d_k - sum_j p_j d_j), written to dlogits (the logits' dtype and
+ *   shape) or added when accumulate != 0; channels >= K of a row untouched. */
+int isa_lovasz_keys(const isa_tensor* logits, const uint8_t* labels, int32_t c0, int32_t nc, int32_t per_image,
+                    uint32_t* keys, uint32_t* vals, int32_t* G, void* stream);
+int isa_lovasz_coef(const uint32_t* keys_sorted, const uint32_t* vals_sorted, const int32_t* G, int32_t nseg,
+                    int64_t seglen, uint32_t* tile_counts, double* partial, float* gpix, void* stream);
+int isa_lovasz_assemble(const double* partial, const int32_t* G, const float* cfg, int32_t B, int32_t K, int32_t per_image,
+                        int64_t hw, double* segloss, float* scale, float* scal, void* stream);
+int isa_lovasz_grad(const isa_tensor* logits, const float* gpix, const float* scale, int32_t per_image,
+                    const isa_tensor* dlogits, int32_t accumulate, void* stream);
 /* reference-format targets: int64 one-hot [n,k,h,w] -> uint8 labels [n,h,w] and / or the fp32 argmax(1) map [n, h*w]
  * (sem_seg_argmax, reseg.py:118); the first maximum wins, as in torch.argmax.  Either output may be NULL, not both. */
 int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t hw, uint8_t* labels, float* argmax_map,

@@ -331,6 +331,9 @@ static inline int tensor_groups(const isa_tensor* t) { return (t && t->groups > 
 // grid of a grouped launch: a multiple of G, at least G
 static inline long group_grid(long gx, int G) { if (G <= 1) return gx < 1 ? 1 : gx; gx = gx / G * G; return gx < G ? G : gx; }
 
+// exclusive scan of n uint32 entries per segment, in place, one workgroup per segment (seg_sort.hip)
+int seg_exclusive_scan_u32(uint32_t* table, int nseg, long n, hipStream_t s);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int grid_cap(long blocks, int cap = 256 * 8) { return (int)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap); }
 

@@ -18,6 +18,15 @@ IN_1X1, IN_3X3, IN_GATHER2 = 0, 1, 2
 OUT_PLAIN, OUT_SHUFFLE2 = 0, 1
 PLANES_U8_NHWK, PLANES_I64_NKHW, PLANES_F32_NKHW = 0, 1, 2
 HIST_AGGREGATE, HIST_NAIVE = 0, 1
+SEGSORT_TILE = 2048           # ISA_SEGSORT_TILE
+
+
+def segsort_table_elems(nseg, seglen):
+    """ISA_SEGSORT_TABLE_ELEMS: uint32 elements of isa_segsort_kv_u32's table (digit table + chunk sums)."""
+    tiles = (seglen + SEGSORT_TILE - 1) // SEGSORT_TILE
+    return nseg * (256 * tiles + (tiles + 7) // 8)
+
+
 PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SATURATION, PHOTO_HUE = 0, 1, 2, 3
 
 _ERR = {-1: "ISA_EINVAL", -2: "ISA_EALIGN", -3: "ISA_EDTYPE", -4: "ISA_ELAUNCH", -5: "ISA_ENOMEM"}
@@ -136,6 +145,12 @@ SIGNATURES = {
     "isa_sem_loss_k_assemble": [VP, VP, I32, I32, VP, VP, VP],
     "isa_sem_loss_k_grad": [P_T, VP, VP, VP, P_T, I32, VP],
     "isa_labels_from_onehot": [VP, I32, I32, I64, VP, VP, VP],
+    # stable segmented radix sort and the Lovasz-Softmax criterion built on it
+    "isa_segsort_kv_u32": [VP, VP, VP, VP, I32, I64, I32, I32, VP, VP, VP, I64, VP],
+    "isa_lovasz_keys": [P_T, VP, I32, I32, I32, VP, VP, VP, VP],
+    "isa_lovasz_coef": [VP, VP, VP, I32, I64, VP, VP, VP, VP],
+    "isa_lovasz_assemble": [VP, VP, VP, I32, I32, I32, I64, VP, VP, VP, VP],
+    "isa_lovasz_grad": [P_T, VP, VP, I32, P_T, I32, VP],
     "isa_ins_softmax_bwd": [VP, VP, VP, VP, VP, I32, I32, I64, VP, I32, VP],
     "isa_maskbn_bwd": [P_T, VP, VP, VP, VP, F, VP, I32, VP, VP, VP, VP, P_T, I32, VP],
     "isa_sp_bwd": [P_T, P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, F, I32, VP, P_T, I32,

@@ -38,6 +38,9 @@ class Model(object):
         # fit(): also score the semantic prediction of every validation minibatch (confusion matrix on the device; mIoU,
         # pixel accuracy, mean Dice of the epoch total -> validation_sem_scores.log)
         self.val_sem_scores = False
+        # fit(): the options of the Lovasz and CELovasz criteria (lovasz_softmax's per_image and only_present)
+        self.lovasz_per_image = False
+        self.lovasz_only_present = False
 
     def __load_weights(self):
         if self.load_model_path != '':
@@ -52,12 +55,13 @@ class Model(object):
     # ------------------------------------------------------------------ training
     def __define_optimizer(self, learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm,
                            optimizer='Adadelta', criterion='Multi', class_weights=None, optimize_bg=False,
-                           train_cnn=True):
+                           train_cnn=True, lovasz_per_image=False, lovasz_only_present=False):
         assert optimizer in ['RMSprop', 'Adam', 'Adadelta', 'SGD']            # model.py:147
         # the criterion of __define_criterion (model.py:102-133): CE(weight) and / or Dice(optimize_bg, weight)
         self.trainer = Trainer(self.model, world_size=self.world, lr=learning_rate, weight_decay=weight_decay,
                                clip_grad_norm=clip_grad_norm, criterion=criterion, class_weights=class_weights,
-                               optimize_bg=optimize_bg, optimizer=optimizer, train_cnn=train_cnn)
+                               optimize_bg=optimize_bg, optimizer=optimizer, train_cnn=train_cnn,
+                               lovasz_per_image=lovasz_per_image, lovasz_only_present=lovasz_only_present)
         self._plateau = dict(best=float('inf'), bad=0, factor=lr_drop_factor, patience=lr_drop_patience)
 
     def __plateau_step(self, val):                   # torch ReduceLROnPlateau(mode='min') semantics, rel 1e-4
@@ -138,12 +142,18 @@ class Model(object):
             row['CE Cost'] = costs[0].clone()
         if crit.dice:
             row['Dice Cost'] = costs[1].clone()
+        if crit.lovasz:
+            row['Lovasz Cost'] = costs[2].clone()
         return row
 
     def fit(self, criterion_type, delta_var, delta_dist, norm, learning_rate, weight_decay, clip_grad_norm,
             lr_drop_factor, lr_drop_patience, optimize_bg, optimizer, train_cnn, n_epochs, class_weights,
-            train_loader, test_loader, model_save_path, debug):
-        assert criterion_type in ['CE', 'Dice', 'Multi']                       # model.py:364
+            train_loader, test_loader, model_save_path, debug, lovasz_per_image=None, lovasz_only_present=None):
+        assert criterion_type in ['CE', 'Dice', 'Multi', 'Lovasz', 'CELovasz']  # model.py:364, and the Lovasz criteria
+        if lovasz_per_image is None:
+            lovasz_per_image = self.lovasz_per_image
+        if lovasz_only_present is None:
+            lovasz_only_present = self.lovasz_only_present
         main = self.rank == 0                   # only rank 0 writes logs and checkpoints (parallel.py: policy)
         tlog = vlog = slog = mlog = None
         scoring = bool(self.val_scores) and self.use_instance_segmentation
@@ -159,7 +169,8 @@ class Model(object):
                 mlog = open(os.path.join(model_save_path, 'validation_sem_scores.log'), 'w')
                 mlog.write('Epoch,mIoU,PixelAcc,mDice\n')
         self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
-                                criterion_type, class_weights, optimize_bg, train_cnn)
+                                criterion_type, class_weights, optimize_bg, train_cnn, lovasz_per_image,
+                                lovasz_only_present)
         best_val_cost = np.inf
         if os.environ.get('ISA_PREFETCH', '1') != '0':      # batch i+1 uploads on a side stream while step i runs
             from .data import DevicePrefetcher
@@ -178,6 +189,8 @@ class Model(object):
             # the cost that drives the plateau scheduler and checkpointing (model.py:425-434)
             if self.use_instance_segmentation:
                 key = 'ins_dice_loss'
+            elif criterion_type in ['Lovasz', 'CELovasz']:
+                key = 'Lovasz Cost'
             elif criterion_type in ['Dice', 'Multi']:
                 key = 'Dice Cost'
             else:

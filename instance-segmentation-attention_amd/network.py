@@ -14,14 +14,29 @@ from . import lib as L
 from .engine import Act, Engine, Pro, rup
 
 
-CRITERIA = ("CE", "Dice", "Multi")
+CRITERIA = ("CE", "Dice", "Multi", "Lovasz", "CELovasz")
+LOVASZ_SCRATCH_BYTES = 256 << 20     # above this the Lovasz criterion sorts its classes in groups
+
+
+def lovasz_class_group(K, pixels, backward):
+    """Classes the Lovasz criterion sorts at once: all K, or as many as keep its scratch under LOVASZ_SCRATCH_BYTES.  Per
+    element of a group: keys and values, in, out and temporary (24 bytes), and at most 0.63 byte of histogram table, tile
+    counts and loss partials (1284 bytes a tile of 2048); per element of all K classes: the 4-byte gradient coefficient
+    when there is a backward.  G, scale and the segment losses (16 bytes a segment) are not counted.
+    Never less than 1: where one class alone, or the gradient coefficients alone, exceed the budget (K * pixels above
+    64 M with a backward, pixels above 10 M without), the criterion still runs, one class at a time, and takes what that
+    needs: 25 bytes a pixel on top of the coefficients."""
+    fixed = 4 * K * pixels if backward else 0
+    return max(1, min(K, (LOVASZ_SCRATCH_BYTES - fixed) // (25 * pixels)))
 
 
 class SemCriterion:
     """The trainer's semantic criterion (Model.__define_criterion, model.py:102-133): criterion type, class weights,
     optimize_bg.  Its settings live in ONE device buffer allocated here, once, and rewritten in place: a captured
     hipGraph reads them at replay time.  Layout (include/isa_kernels.h, isa_sem_loss_k_*): {use_ce, use_dice,
-    optimize_bg, 0, w_0 .. w_{K-1}}; no weights = all ones (the same CE and Dice as unweighted).
+    optimize_bg, lovasz_only_present, w_0 .. w_{K-1}}; no weights = all ones (the same CE and Dice as unweighted).
+    "Lovasz" / "CELovasz": the Lovasz-Softmax loss (lovasz_losses.py:156-196), alone or added to CE; class weights are
+    the CE term's.  lovasz_per_image sets the segment geometry, so it belongs to a captured step's configuration.
     `legacy`: the shipped combination (K = 2, Multi, no weights, fg only) runs the 2-class kernels it always ran."""
 
     def __init__(self, n_classes, device):
@@ -29,9 +44,12 @@ class SemCriterion:
         self.cfg = torch.zeros(4 + n_classes, dtype=torch.float32, device=device)
         self.set("Multi", None, False)
 
-    def set(self, criterion="Multi", class_weights=None, optimize_bg=False):
+    def set(self, criterion="Multi", class_weights=None, optimize_bg=False, lovasz_per_image=False,
+            lovasz_only_present=False):
         assert criterion in CRITERIA, "criterion must be one of %s" % (CRITERIA,)
         K = self.K
+        if criterion == "Lovasz" and class_weights is not None:
+            raise ValueError("class_weights weigh the CE term: the Lovasz criterion has none (use CELovasz)")
         if class_weights is not None:
             class_weights = [float(v) for v in class_weights]
             if len(class_weights) != K:
@@ -39,10 +57,13 @@ class SemCriterion:
             if min(class_weights) < 0 or sum(class_weights[0 if optimize_bg else 1:]) <= 0:
                 raise ValueError("class_weights must be non-negative with a positive sum over the optimised classes")
         self.criterion, self.class_weights, self.optimize_bg = criterion, class_weights, bool(optimize_bg)
-        self.ce, self.dice = criterion in ("CE", "Multi"), criterion in ("Dice", "Multi")
+        self.ce, self.dice = criterion in ("CE", "Multi", "CELovasz"), criterion in ("Dice", "Multi")
+        self.lovasz = criterion in ("Lovasz", "CELovasz")
+        self.lovasz_per_image, self.lovasz_only_present = bool(lovasz_per_image), bool(lovasz_only_present)
         self.legacy = K == 2 and criterion == "Multi" and class_weights is None and not optimize_bg
         w = class_weights if class_weights is not None else [1.0] * K
-        self.cfg.copy_(torch.tensor([float(self.ce), float(self.dice), float(self.optimize_bg), 0.0] + w))
+        self.cfg.copy_(torch.tensor([float(self.ce), float(self.dice), float(self.optimize_bg),
+                                     float(self.lovasz and self.lovasz_only_present)] + w))
 
     @property
     def weights(self):
@@ -182,9 +203,9 @@ class Network:
 
     def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None):
         """Trainer-side semantic criterion on the logits (model.py:255-269), per self.crit: CE (weighted) and / or
-        Dice (time=1, per class, fg or all).  `labels`: the uint8 label map when the caller has it (compact targets),
-        else taken from the one-hot.  Returns device tensor [ce, dice] (0 for a term the criterion lacks); records
-        d(sem)."""
+        Dice (time=1, per class, fg or all), or Lovasz-Softmax with or without CE.  `labels`: the uint8 label map when
+        the caller has it (compact targets), else taken from the one-hot.  Returns device tensor [ce, dice] (0 for a term
+        the criterion lacks), [ce, 0, lovasz] for the Lovasz criteria; records d(sem)."""
         E = self.E
         n = sem.n
         if self.crit.legacy:             # the shipped criterion: its pinned 2-class kernels
@@ -206,6 +227,8 @@ class Network:
             L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, K, sem.h * sem.w, L.ptr(labels), None, E.st()),
                     "isa_labels_from_onehot")
         assert labels.dtype == torch.uint8 and tuple(labels.shape) == (n, sem.h, sem.w)
+        if self.crit.lovasz:
+            return self._lovasz_loss(sem, labels)
         sums = E.scratch(3 * n * K + 2)
         L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
         coef, scal = E.f32(3 * n * K + 1), E.f32(2)
@@ -216,6 +239,64 @@ class Network:
                 acc = E.grads.claim(sem, E)
                 L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef),
                                                   E.grads.grad_of(sem).d(), acc, E.st()), "isa_sem_loss_k_grad")
+            E.tape.append(bwd)
+        return scal
+
+    def _lovasz_loss(self, sem: Act, labels: torch.Tensor):
+        """CELovasz: the CE term from the K-class kernels as they are, then the Lovasz-Softmax launches (keys, segmented
+        sort, coefficients per class group; one assemble); the backward adds both gradients into d(sem).  The launch
+        count depends on (K, B, H*W, per_image) alone and nothing is read back: the step captures."""
+        E, crit = self.E, self.crit
+        n, K, hw, cfg = sem.n, sem.c, sem.h * sem.w, self.crit.cfg
+        T = L.SEGSORT_TILE
+        per_image = int(crit.lovasz_per_image)
+        nimg = n if per_image else 1
+        seglen = n * hw // nimg
+        ntiles = (seglen + T - 1) // T
+        if K * n * hw >= 1 << 31:
+            raise L.IsaError("Lovasz criterion: K*B*H*W = %d elements, the segmented sort takes fewer than 2^31" % (K * n * hw))
+        scal = E.arena.alloc((3,), torch.float32, zero=True)
+        coef = None
+        if crit.ce:
+            sums = E.scratch(3 * n * K + 2)
+            L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+            coef = E.f32(3 * n * K + 1)
+            L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
+                    "isa_sem_loss_k_assemble")
+        record = E.record
+        G = E.scratch(K * nimg).view(torch.int32)                       # zero at step start: the keys kernel adds to it
+        partial = E.arena.alloc((K * nimg * ntiles,), torch.float64)
+        gpix = E.f32(K * n * hw) if record else None
+        kg = lovasz_class_group(K, n * hw, record)
+        u32 = [E.arena.alloc((kg * n * hw,), torch.int32) for _ in range(6)]
+        k_in, v_in, k_out, v_out, k_tmp, v_tmp = u32
+        table = E.arena.alloc((L.segsort_table_elems(kg * nimg, seglen),), torch.int32)
+        tcnt = E.arena.alloc((kg * nimg * ntiles,), torch.int32)
+        for c0 in range(0, K, kg):
+            nc = min(kg, K - c0)
+            s0 = c0 * nimg
+            L.check(E.lib.isa_lovasz_keys(sem.d(), L.ptr(labels), c0, nc, per_image, L.ptr(k_in), L.ptr(v_in),
+                                          L.ptr(G[s0:]), E.st()), "isa_lovasz_keys")
+            L.check(E.lib.isa_segsort_kv_u32(L.ptr(k_in), L.ptr(v_in), L.ptr(k_out), L.ptr(v_out), nc * nimg, seglen, 0, 30,
+                                             L.ptr(k_tmp), L.ptr(v_tmp), L.ptr(table), table.numel(), E.st()),
+                    "isa_segsort_kv_u32")
+            L.check(E.lib.isa_lovasz_coef(L.ptr(k_out), L.ptr(v_out), L.ptr(G[s0:]), nc * nimg, seglen, L.ptr(tcnt),
+                                          L.ptr(partial[s0 * ntiles:]), L.ptr(gpix[s0 * seglen:]) if record else None,
+                                          E.st()), "isa_lovasz_coef")
+        segloss = E.arena.alloc((K * nimg,), torch.float64)
+        scale = E.f32(K * nimg)
+        L.check(E.lib.isa_lovasz_assemble(L.ptr(partial), L.ptr(G), L.ptr(cfg), n, K, per_image, hw, L.ptr(segloss),
+                                          L.ptr(scale), L.ptr(scal[2:]), E.st()), "isa_lovasz_assemble")
+        if record:
+            def bwd():
+                acc = E.grads.claim(sem, E)
+                dsem = E.grads.grad_of(sem).d()
+                if coef is not None:
+                    L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), dsem, acc, E.st()),
+                            "isa_sem_loss_k_grad")
+                    acc = 1
+                L.check(E.lib.isa_lovasz_grad(sem.d(), L.ptr(gpix), L.ptr(scale), per_image, dsem, acc, E.st()),
+                        "isa_lovasz_grad")
             E.tape.append(bwd)
         return scal
 

@@ -186,14 +186,17 @@ class ReSeg(nn.Module):
         slot["graph"].replay()
         return slot["out"]
 
-    def set_criterion(self, criterion="Multi", class_weights=None, optimize_bg=False):
-        """The semantic criterion of training steps and sem_costs (Model.__define_criterion, model.py:102-133)."""
-        self.net.crit.set(criterion, class_weights, optimize_bg)
+    def set_criterion(self, criterion="Multi", class_weights=None, optimize_bg=False, lovasz_per_image=False,
+                      lovasz_only_present=False):
+        """The semantic criterion of training steps and sem_costs (Model.__define_criterion, model.py:102-133); "Lovasz" and
+        "CELovasz" add lovasz_softmax (losses/lovasz_losses.py:156-196) with its per_image / only_present options."""
+        self.net.crit.set(criterion, class_weights, optimize_bg, lovasz_per_image, lovasz_only_present)
 
     def sem_costs(self, sem_seg_target):
         """Semantic criterion (set_criterion; default CE + Dice(time=1)) of the LAST forward's logits against a one-hot
         int64 target [B,K,H,W] (validation branch of model.py:244-270).  Returns a device tensor [ce, dice] (0 for a
-        term the criterion lacks); must be called before the next forward (the logits live in that step's arena)."""
+        term the criterion lacks; [ce, 0, lovasz] for the Lovasz criteria); must be called before the next forward (the
+        logits live in that step's arena)."""
         sem = getattr(self, "_last_sem", None)
         assert sem is not None, "sem_costs() follows a forward()"
         t = sem_seg_target.to(self.store.device).contiguous()

@@ -31,13 +31,14 @@ def frozen_prefix(store):
 
 class Trainer:
     def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6,
-                 criterion='Multi', class_weights=None, optimize_bg=False, optimizer='Adadelta', train_cnn=True):
+                 criterion='Multi', class_weights=None, optimize_bg=False, optimizer='Adadelta', train_cnn=True,
+                 lovasz_per_image=False, lovasz_only_present=False):
         assert optimizer in OPTIMIZERS, optimizer
         self.model = model
         self.optimizer, self.train_cnn = optimizer, bool(train_cnn)
         # semantic criterion (model.py:102-133, 255-269): written once into the model's settings buffer, which was
         # allocated with the model - a captured step keeps reading the same device memory
-        model.set_criterion(criterion, class_weights, optimize_bg)
+        model.set_criterion(criterion, class_weights, optimize_bg, lovasz_per_image, lovasz_only_present)
         self.criterion = criterion
         self.world = world_size
         self.lr, self.wd, self.clip, self.rho, self.eps = lr, weight_decay, clip_grad_norm, rho, eps
@@ -78,8 +79,9 @@ class Trainer:
     def forward_backward(self, x, sem, ins, n_objects, selected_idx=None, injected_s_t=None, capture=None,
                          idx_dev=None, arena_key=None, backward=True):
         """Forward + backward; gradients land in model.store.grad.  Returns device scalars
-        dict(sem=[ce, dice], head=[ins_cost_finite, criterion, ins_ce, ins_dice]).  backward=False: the training-mode
-        forward alone (batch statistics, sampling, Dropout2d, losses; no tape) - the forward-only benchmark line."""
+        dict(sem=[ce, dice] ([ce, 0, lovasz] for the Lovasz criteria), head=[ins_cost_finite, criterion, ins_ce,
+        ins_dice]).  backward=False: the training-mode forward alone (batch statistics, sampling, Dropout2d, losses; no
+        tape) - the forward-only benchmark line."""
         m = self.model
         E, net, st = m.engine, m.net, m.store
         dev = st.device
@@ -197,7 +199,10 @@ class Trainer:
                 random.shuffle(order)
                 selected_idx.append(order)
         key = (tuple(x.shape), tuple(sem.shape), tuple(ins.shape), max_iter, bool(m.training), self.world,
-               m.engine.dtype, injected_s_t is not None, x.dtype == torch.uint8, ins.dtype == torch.uint8, bool(forward_only))
+               m.engine.dtype, injected_s_t is not None, x.dtype == torch.uint8, ins.dtype == torch.uint8, bool(forward_only),
+               # the Lovasz criteria have launches of their own (CELovasz three more than Lovasz), and per_image sets
+               # their segment geometry
+               m.net.crit.criterion if m.net.crit.lovasz else None, m.net.crit.lovasz and m.net.crit.lovasz_per_image)
         slot = self._graphs.get(key)
         akey = ("train_graph",) + key            # the captured configuration owns its arena (frozen after capture)
         self.sync_lr()

@@ -40,7 +40,11 @@ def build_parser():
     parser.add_argument('--out', default=os.path.join(ROOT, 'models', 'CVPPP', 'run'))
     # the semantic criterion (settings/CVPPP/training_settings.py: CRITERION, CLASS_WEIGHTS, OPTIMIZE_BG; data_settings.py:
     # N_CLASSES); the defaults are the shipped settings
-    parser.add_argument('--criterion', default='Multi', choices=['CE', 'Dice', 'Multi'])
+    parser.add_argument('--criterion', default='Multi', choices=['CE', 'Dice', 'Multi', 'Lovasz', 'CELovasz'])
+    parser.add_argument('--lovasz-per-image', action='store_true', help='Lovasz / CELovasz: the loss per image, then the mean '
+                        '(lovasz_softmax per_image; Model.lovasz_per_image)')
+    parser.add_argument('--lovasz-present', action='store_true', help='Lovasz / CELovasz: average only the classes present in '
+                        'the ground truth (lovasz_softmax only_present; Model.lovasz_only_present)')
     parser.add_argument('--class-weights', default=None, help='one weight per class, comma separated (w0,w1,...)')
     parser.add_argument('--optimize-bg', action='store_true', help='Dice over every class, background included')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes, 2..32 (more than 2 needs --semantic-only)')
@@ -113,6 +117,7 @@ def main(argv=None):
                   load_model_path=opt.model, usegpu=True, dtype=torch.bfloat16 if opt.dtype == 'bf16' else torch.float32)
     model.val_scores = opt.val_scores
     model.val_sem_scores = opt.val_sem_scores
+    model.lovasz_per_image, model.lovasz_only_present = opt.lovasz_per_image, opt.lovasz_present
     # every rank draws its own shard of each global batch (weights start identical: the model seed is not per rank)
     train_loader = SyntheticLoader(opt.iters_per_epoch, per_rank, opt.size, opt.size, seed=parallel.rank_seed(SEED, rank),
                                    compact=opt.compact_targets, n_classes=opt.n_classes)
