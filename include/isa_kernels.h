@@ -538,6 +538,44 @@ int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t 
 int isa_sem_confusion(const isa_tensor* logits, const uint8_t* labels, int32_t K, int64_t* conf, int32_t* oob,
                       uint8_t* class_map, void* stream);
 int isa_sem_scores(const int64_t* conf, int32_t n, int32_t K, double* out, void* stream);
+/* ---- connected components of uint8 label maps, and the clean-up of instance maps built on them --------------------------
+ * Both entries check every argument before they launch or clear anything (ISA_EINVAL / ISA_EALIGN / ISA_ENOMEM), are
+ * asynchronous on `stream`, allocate nothing and never read anything back: the launch count depends on the shape and the
+ * mode alone, so a captured hipGraph replays them.  n <= 65535, w % 4 == 0, h * w < 2^30.  Only integer atomics and scans
+ * decide anything: two runs are bit-identical, whatever order workgroups ran in.
+ * isa_cc_label: map uint8 [n,h,w] (4-byte aligned), 0 = background.  Two pixels of one image are neighbours when they share
+ *   an edge (connectivity 4) or an edge or a corner (8) AND hold the same non-zero value; the last column of a row and the
+ *   first of the next are not neighbours, nor are pixels of two images.  comp int32 [n,h,w] (16-byte aligned): 0 for
+ *   background, else 1 + the smallest row-major pixel index (inside its image) of the pixel's component - the canonical
+ *   form.  n_comp int32 [n]: components per image.  scratch: ISA_CC_LABEL_SCRATCH_BYTES(n,h,w) bytes, 16-byte aligned
+ *   (the union-find parents; they need not be cleared).  Three launches (two when the image is one ISA_CC_TILE_H x
+ *   ISA_CC_TILE_W tile): tiles labelled in LDS, unions across tile edges with device-scope atomics on every access,
+ *   flatten.
+ * isa_cc_select: map and the comp isa_cc_label made of it -> out uint8 [n,h,w] (4-byte aligned; it must not overlap map:
+ *   ISA_EINVAL), count int32 [n] (labels given), dropped int32 [n].  The area of a component is its pixel count; it
+ *   qualifies when area >= min_area (min_area <= 1: every component).  1 <= max_objects <= 255.
+ *   ISA_CC_SPLIT: the qualifying components are numbered 1, 2, .. in ascending order of their root pixel (raster order of
+ *     their first pixels); only the first max_objects get a label, the pixels of every other component become 0.
+ *   ISA_CC_LARGEST: per input value v the component of largest area wins (equal areas: the smaller root); it survives when
+ *     it qualifies, every other component of v becomes 0.  The survivors are numbered 1, 2, .. in ascending order of v and
+ *     only the first max_objects of them get a label.
+ *   In both modes dropped = qualifying components - count: components cut by the cap, and in LARGEST the qualifying
+ *   fragments that lost to a larger one ("this instance was really two objects").
+ *   scratch: ISA_CC_SELECT_SCRATCH_BYTES(n,h,w) bytes, 16-byte aligned, cleared by the entry (areas by root pixel, then
+ *   ISA_CC_TAB_BYTES of winner keys, survivor tables and chunk counts per image).  Six launches (SPLIT: clear, areas,
+ *   chunk counts of qualifying roots, one-workgroup fold, ranks, write) or five (LARGEST: clear, areas, winners, fold,
+ *   write). */
+#define ISA_CC_TILE_H 32
+#define ISA_CC_TILE_W 64
+#define ISA_CC_TAB_BYTES 4608
+#define ISA_CC_LABEL_SCRATCH_BYTES(n, h, w) ((int64_t)(n) * (h) * (w) * 4)
+#define ISA_CC_SELECT_SCRATCH_BYTES(n, h, w) ((int64_t)(n) * ((int64_t)(h) * (w) * 4 + ISA_CC_TAB_BYTES))
+enum { ISA_CC_SPLIT = 0, ISA_CC_LARGEST = 1 };
+int isa_cc_label(const uint8_t* map, int32_t n, int32_t h, int32_t w, int32_t connectivity, int32_t* comp, int32_t* n_comp,
+                 void* scratch, int64_t scratch_bytes, void* stream);
+int isa_cc_select(const uint8_t* map, const int32_t* comp, int32_t n, int32_t h, int32_t w, int32_t mode, int32_t min_area,
+                  int32_t max_objects, uint8_t* out, int32_t* count, int32_t* dropped, void* scratch, int64_t scratch_bytes,
+                  void* stream);
 int isa_ins_softmax_bwd(const float* alpha, const int64_t* ins, const int32_t* idx, const int32_t* s_t,
                         const float* adv, int32_t n, int32_t nobj, int64_t L, float* dmerge /*[nsrc, L]*/, int32_t nsrc,
                         void* stream);

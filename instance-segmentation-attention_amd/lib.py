@@ -19,12 +19,24 @@ OUT_PLAIN, OUT_SHUFFLE2 = 0, 1
 PLANES_U8_NHWK, PLANES_I64_NKHW, PLANES_F32_NKHW = 0, 1, 2
 HIST_AGGREGATE, HIST_NAIVE = 0, 1
 SEGSORT_TILE = 2048           # ISA_SEGSORT_TILE
+CC_SPLIT, CC_LARGEST = 0, 1
+CC_TILE_H, CC_TILE_W, CC_TAB_BYTES = 32, 64, 4608       # ISA_CC_TILE_H, ISA_CC_TILE_W, ISA_CC_TAB_BYTES
 
 
 def segsort_table_elems(nseg, seglen):
     """ISA_SEGSORT_TABLE_ELEMS: uint32 elements of isa_segsort_kv_u32's table (digit table + chunk sums)."""
     tiles = (seglen + SEGSORT_TILE - 1) // SEGSORT_TILE
     return nseg * (256 * tiles + (tiles + 7) // 8)
+
+
+def cc_label_scratch_bytes(n, h, w):
+    """ISA_CC_LABEL_SCRATCH_BYTES: the union-find parents of isa_cc_label."""
+    return n * h * w * 4
+
+
+def cc_select_scratch_bytes(n, h, w):
+    """ISA_CC_SELECT_SCRATCH_BYTES: areas by root pixel and the per-image tables of isa_cc_select."""
+    return n * (h * w * 4 + CC_TAB_BYTES)
 
 
 PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SATURATION, PHOTO_HUE = 0, 1, 2, 3
@@ -183,6 +195,9 @@ SIGNATURES = {
     # scoring K-class semantic predictions (ReSeg.class_map, ReSeg.score_semantic)
     "isa_sem_confusion": [P_T, VP, I32, VP, VP, VP, VP],
     "isa_sem_scores": [VP, I32, I32, VP, VP],
+    # connected components and instance clean-up (ReSeg.components, split_components, clean_instances)
+    "isa_cc_label": [VP, I32, I32, I32, I32, VP, VP, VP, I64, VP],
+    "isa_cc_select": [VP, VP, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, I64, VP],
 }
 
 

@@ -110,12 +110,15 @@ class Model(object):
                         'ins_dice_loss': h[3].clone()})
         return row
 
-    def __score_batch(self, batch, max_objects, check):
+    def __score_batch(self, batch, max_objects, check, clean=None):
         """segment() + score_instances() of one loader batch: the device tensor [B,8], and the number of pixels whose
-        label the histograms do not hold (a device scalar: the callers read it with their one copy and raise)."""
+        label the histograms do not hold (a device scalar: the callers read it with their one copy and raise).
+        clean: keyword arguments of ReSeg.clean_instances, applied to the labels before they are scored."""
         images, sem, ins, n_objects = batch
         m = self.model
         _, sem_arg, labels, count = m.segment(images.contiguous(), max_objects)
+        if clean is not None:
+            labels, count, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         out = m.score_instances(labels, count, ins, n_objects, sem_arg, sem, max_objects=max_objects, check=check)
         return out, m.last_score_oob.sum()
 
@@ -268,34 +271,74 @@ class Model(object):
             m(False, images.contiguous())
             return m.class_map().cpu()
 
-    def predict_instances(self, images, max_objects=None):
+    @staticmethod
+    def __clean_arguments(min_area, keep, connectivity):
+        """None when the defaults ask for no clean-up (then nothing of it runs), else ReSeg.clean_instances' keywords.
+        keep=None with a min_area above 1 drops small pieces and keeps everything else apart: 'all'."""
+        if keep not in (None, 'largest', 'all'):
+            raise ValueError("keep must be None, 'largest' or 'all', got %r" % (keep,))
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+        if keep is None and int(min_area) <= 1:
+            return None
+        return {'keep': keep or 'all', 'connectivity': connectivity, 'min_area': int(min_area)}
+
+    def predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8):
         """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
         instance prediction is dead at HEAD).  images: [b,21,h,w] float or raw uint8 RGB [b,h,w,3].  Returns host tensors
         (fg_prob [b,h,w] = softmax probability of the foreground class, labels uint8 [b,h,w] with 0 = no instance,
-        n_objects int32 [b]); at most max_objects (default: the constructor's max_n_objects) instances per image."""
+        n_objects int32 [b]); at most max_objects (default: the constructor's max_n_objects) instances per image.
+        keep='largest' | 'all' and / or min_area > 1 clean the label map on the device before it comes down
+        (ReSeg.clean_instances: the largest connected piece of every instance, or every piece as an instance of its own;
+        pieces under min_area pixels dropped; connectivity 4 or 8).  With the defaults none of that runs."""
         assert len(images.size()) == 4
         m = self.model
         if not m.use_instance_seg:
             raise RuntimeError("predict_instances() needs a model built with use_instance_segmentation=True")
+        clean = self.__clean_arguments(min_area, keep, connectivity)
         m.eval()
-        _, _, labels, n_objects = m.segment(images.contiguous(), self.max_n_objects if max_objects is None else max_objects)
+        max_objects = self.max_n_objects if max_objects is None else max_objects
+        _, _, labels, n_objects = m.segment(images.contiguous(), max_objects)
+        if clean is not None:
+            labels, n_objects, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
 
-    def evaluate(self, loader, max_objects=None):
+    def predict_components(self, images, *, min_area=1, connectivity=8, max_objects=None):
+        """The count-the-blobs baseline, for any model (no instance head is run): the connected components of the predicted
+        class map (class 0 = background; pixels of different classes never join) with at least min_area pixels, numbered in
+        raster order (ReSeg.split_components).  Returns what predict_instances returns: host tensors (fg_prob [b,h,w] = the
+        softmax probability of not being background, labels uint8 [b,h,w], n_objects int32 [b]); at most max_objects
+        (default: the constructor's max_n_objects, 1..255) objects per image."""
+        assert len(images.size()) == 4
+        m = self.model
+        m.eval()
+        max_objects = self.max_n_objects if max_objects is None else max_objects
+        with torch.no_grad():
+            m._semantic_logits(images.to(m.store.device).contiguous())
+            labels, n_objects, _ = m.split_components(m.class_map(), connectivity=connectivity, min_area=min_area,
+                                                      max_objects=max_objects)
+            prob = m.net.softmax_nchw(m._last_sem)
+            fg_prob = prob[:, 1] if prob.shape[1] == 2 else 1.0 - prob[:, 0]
+        return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
+
+    def evaluate(self, loader, max_objects=None, *, min_area=0, keep=None, connectivity=8):
         """Scores of ground-truth-free instance inference over a loader of (images, sem, ins, n_objects) batches, either
         target form: every batch is segmented (ReSeg.segment, at most max_objects instances per image; default: the
         constructor's max_n_objects) and scored on the device (ReSeg.score_instances); one device-to-host copy at the end.
         Returns {'SBD', '|DiC|', 'FG Dice', 'n_images', 'n_skipped', 'per_image'}: per_image is the float64 ndarray
         [N,8] of score_instances, the three means are taken over the images whose value is not NaN (evaluate.py's main
         averages the images it scored), n_skipped counts the images whose SBD is NaN (neither map holds an object).
+        min_area / keep / connectivity: the clean-up of predict_instances, applied to every label map before it is scored
+        (with the defaults none of it runs).
         It scores what the loader yields on THIS rank; reducing over ranks is left to the caller."""
         m = self.model
         if not m.use_instance_seg:
             raise RuntimeError("evaluate() needs a model built with use_instance_segmentation=True")
+        clean = self.__clean_arguments(min_area, keep, connectivity)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
-        rows = [self.__score_batch(b, max_objects, check=False) for b in loader]
+        rows = [self.__score_batch(b, max_objects, check=False, clean=clean) for b in loader]
         if not rows:
             nan = float('nan')
             return {'SBD': nan, '|DiC|': nan, 'FG Dice': nan, 'n_images': 0, 'n_skipped': 0,

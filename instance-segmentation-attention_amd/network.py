@@ -353,6 +353,34 @@ class Network:
         L.check(E.lib.isa_sem_scores(L.ptr(conf), n, K, L.ptr(out), E.st()), "isa_sem_scores")
         return out
 
+    def cc_label(self, maps: torch.Tensor, connectivity=8):
+        """(comp int32 [n,h,w], n_comp int32 [n]) of the uint8 map [n,h,w] on the device (isa_cc_label): 0 for background,
+        else 1 + the smallest row-major pixel index of the pixel's component inside its image.  New tensors."""
+        E = self.E
+        assert maps.dtype == torch.uint8 and maps.dim() == 3 and maps.is_contiguous(), "maps: contiguous uint8 [n,h,w]"
+        n, h, w = maps.shape
+        comp = torch.empty((n, h, w), dtype=torch.int32, device=maps.device)
+        n_comp = torch.empty((n,), dtype=torch.int32, device=maps.device)
+        scratch = torch.empty((L.cc_label_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
+        L.check(E.lib.isa_cc_label(L.ptr(maps), n, h, w, int(connectivity), L.ptr(comp), L.ptr(n_comp), L.ptr(scratch),
+                                   scratch.numel(), E.st()), "isa_cc_label")
+        return comp, n_comp
+
+    def cc_select(self, maps: torch.Tensor, comp: torch.Tensor, mode, min_area=1, max_objects=255):
+        """(labels uint8 [n,h,w], count int32 [n], dropped int32 [n]) from a uint8 map and its cc_label components
+        (isa_cc_select), mode L.CC_SPLIT or L.CC_LARGEST.  New tensors."""
+        E = self.E
+        assert maps.dtype == torch.uint8 and maps.dim() == 3 and maps.is_contiguous(), "maps: contiguous uint8 [n,h,w]"
+        assert comp.dtype == torch.int32 and comp.shape == maps.shape and comp.is_contiguous()
+        n, h, w = maps.shape
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=maps.device)
+        count = torch.empty((n,), dtype=torch.int32, device=maps.device)
+        dropped = torch.empty((n,), dtype=torch.int32, device=maps.device)
+        scratch = torch.empty((L.cc_select_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
+        L.check(E.lib.isa_cc_select(L.ptr(maps), L.ptr(comp), n, h, w, int(mode), int(min_area), int(max_objects), L.ptr(out),
+                                    L.ptr(count), L.ptr(dropped), L.ptr(scratch), scratch.numel(), E.st()), "isa_cc_select")
+        return out, count, dropped
+
     # ------------------------------------------------------------------ boundary
     def to_nhwc(self, x: torch.Tensor, c_pad=None) -> Act:
         """NCHW fp32 (reference layout) -> NHWC activation view."""

@@ -351,6 +351,51 @@ class ReSeg(nn.Module):
                                          % (int(row.sum()), torch.nonzero(row).view(-1).tolist(), limit))
             return out
 
+    # ------------------------------------------------------------------ connected components, cleaning instance maps
+    def _cc_map(self, maps, connectivity, min_area=1, max_objects=255):
+        t = maps.to(self.store.device).contiguous()
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise TypeError("expects a uint8 map [B,H,W], got %s %s" % (t.dtype, tuple(t.shape)))
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+        if not 1 <= int(max_objects) <= 255:
+            raise ValueError("max_objects must be in 1..255 (labels are uint8), got %d" % max_objects)
+        if t.shape[2] % 4 or t.shape[1] * t.shape[2] >= 1 << 30 or not 1 <= t.shape[0] <= 65535:
+            raise ValueError("maps [B,H,W]: W a multiple of 4, H*W < 2^30, 1 <= B <= 65535; got %s" % (tuple(t.shape),))
+        return t
+
+    def components(self, maps, *, connectivity=8):
+        """(comp int32 [B,H,W], n_components int32 [B]), on the device, of a uint8 map [B,H,W] whose value 0 is background:
+        two pixels belong together when they are neighbours (connectivity 4: edges, 8: edges and corners) and hold the same
+        non-zero value.  comp is 0 on the background and elsewhere 1 + the smallest row-major pixel index of the pixel's
+        component inside its image - the same tensor bit for bit on every run (isa_cc_label)."""
+        with torch.no_grad():
+            return self.net.cc_label(self._cc_map(maps, connectivity), connectivity)
+
+    def split_components(self, maps, *, connectivity=8, min_area=1, max_objects=255):
+        """(labels uint8 [B,H,W], n_objects int32 [B], dropped int32 [B]), on the device: every connected component of `maps`
+        (see components()) with at least min_area pixels becomes an instance, numbered 1, 2, .. in raster order of the
+        components' first pixels; past max_objects (1..255) a component gets no label and is counted in dropped.  Fed with
+        class_map() or a foreground map this is the count-the-blobs baseline of a semantic-only model; the result goes
+        straight into score_instances."""
+        with torch.no_grad():
+            t = self._cc_map(maps, connectivity, min_area, max_objects)
+            comp, _ = self.net.cc_label(t, connectivity)
+            return self.net.cc_select(t, comp, L.CC_SPLIT, min_area, max_objects)
+
+    def clean_instances(self, labels, *, keep='largest', connectivity=8, min_area=1, max_objects=255):
+        """Cleans a label map such as segment()'s (uint8 [B,H,W]), on the device; returns (labels, n_objects, dropped) as
+        split_components does.  keep='largest': of every instance only its largest connected piece survives (equal areas:
+        the one whose first pixel comes first), and only if it has min_area pixels; the survivors are renumbered 1, 2, .. in
+        the order of their old labels (segment's order of discovery).  keep='all': every piece of min_area pixels becomes an
+        instance of its own, in raster order.  dropped counts the pieces of min_area pixels that ended without a label."""
+        if keep not in ('largest', 'all'):
+            raise ValueError("keep must be 'largest' or 'all', got %r" % (keep,))
+        with torch.no_grad():
+            t = self._cc_map(labels, connectivity, min_area, max_objects)
+            comp, _ = self.net.cc_label(t, connectivity)
+            return self.net.cc_select(t, comp, L.CC_LARGEST if keep == 'largest' else L.CC_SPLIT, min_area, max_objects)
+
     # ------------------------------------------------------------------ scoring semantic predictions on the device
     def _semantic_logits(self, x):
         """Backbone and semantic head alone, eval mode: leaves the logits of `x` (either input form of forward) in

@@ -9,6 +9,8 @@ map is materialised.  `--synthetic` predicts one random image when no file is at
 <name>-n_objects.npy as pred_list.py --instances does (ReSeg.segment, at most `--max-objects` instances).
 `--n-classes K` (K > 2) loads a K-class semantic-only model and also writes <name>-sem_mask.png and
 <name>-sem_mask_color.png as pred_list.py --n-classes does (ReSeg.class_map); -fg_mask.png is then class != 0.
+`--min-area`, `--keep`, `--connectivity` and `--components` are pred_list.py's: the clean-up of the `--instances` label
+map on the device, and the instance files from the connected components of the class map without an instance head.
 The reference's hard-coded checkpoint and image paths (pred.py:25-26,112) are flags here."""
 import argparse
 import os
@@ -21,11 +23,13 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import isa_amd  # noqa: F401,E402
 from isa_amd.model import Model  # noqa: E402
-from pred_list import H, W, nearest_upsample, write_classes, write_instances  # noqa: E402
+from pred_list import (H, W, add_cleanup_arguments, check_cleanup_arguments, cleanup_arguments, nearest_upsample,  # noqa: E402
+                       write_classes, write_instances)
 
 
-def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
-    """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask."""
+def predict_file(model, image, out_dir, name, instances=False, max_objects=32, clean=None, components=None):
+    """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask.  clean: ReSeg.clean_instances' keywords for the
+    instance map; components: ReSeg.split_components' keywords - the instance files come from the class map's components."""
     from PIL import Image
     from isa_amd.data import resize_bilinear
     x = resize_bilinear(torch.from_numpy(image[None]), (H, W))  # uint8 [1,H,W,3] on the device, bit-identical to PIL's
@@ -36,12 +40,19 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
     with torch.no_grad():
         if net.n_classes > 2:
             net(False, x)
-            classes = net.class_map()[0].cpu().numpy()         # uint8 [H,W]: the arg-max taken on the device
+            classes = net.class_map()
+            if components is not None:
+                labels, counts, _ = net.split_components(classes, **components)
+            classes = classes[0].cpu().numpy()                 # uint8 [H,W]: the arg-max taken on the device
             sem_arg = torch.from_numpy((classes != 0).astype(np.float32))[None, None]
         elif instances:
             _, sem_arg, labels, counts = net.segment(x, max_objects)
+            if clean is not None:                              # at model resolution, before the nearest up-sampling
+                labels, counts, _ = net.clean_instances(labels, **clean)
         else:
             _, sem_arg = net(False, x)                         # arg-max map == (softmax[:, 1] > 0.5)
+            if components is not None:
+                labels, counts, _ = net.split_components(net.class_map(), **components)
     fg = sem_arg[0, 0].cpu().numpy() > 0.5
     full = nearest_upsample(fg, image.shape[0], image.shape[1])            # prediction.py:47-50
     fg_seg_pred_norm = (full * 255).astype(np.float32)                     # pred.py:117
@@ -50,12 +61,12 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32):
     Image.fromarray(fg_seg_pred_norm).convert('P').save(path)              # pred.py:122-123
     if classes is not None:
         write_classes(out_dir, name, classes, image.shape[0], image.shape[1])
-    if instances:
+    if labels is not None:
         write_instances(out_dir, name, labels[0].cpu().numpy(), int(counts[0]), image.shape[0], image.shape[1])
     return path
 
 
-def main():
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--image', default='', help='Path of the image')
     parser.add_argument('--model', default='', help='Path of the model (state_dict .pth)')
@@ -68,11 +79,18 @@ def main():
     parser.add_argument('--max-objects', type=int, default=32, help='most instances with --instances (1..255)')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
-    opt = parser.parse_args()
+    add_cleanup_arguments(parser)
+    opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
     if opt.n_classes > 2 and opt.instances:
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
+    check_cleanup_arguments(parser, opt)
+    return opt
+
+
+def main():
+    opt = parse_args()
     assert opt.dataset in ['CVPPP', ]                          # pred.py:29
     assert opt.image or opt.synthetic, "give --image or --synthetic"
     if opt.synthetic:
@@ -83,7 +101,9 @@ def main():
         image, name = np.asarray(Image.open(opt.image).convert('RGB')), os.path.splitext(os.path.basename(opt.image))[0]
     model = Model(opt.dataset, 'ReSeg', opt.n_classes, 32, use_instance_segmentation=opt.instances,
                   load_model_path=opt.model, usegpu=True)
-    path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects)
+    components = {'connectivity': opt.connectivity, 'min_area': opt.min_area, 'max_objects': opt.max_objects} \
+        if opt.components else None
+    path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects, cleanup_arguments(opt), components)
     print('wrote', path)
 
 

@@ -15,6 +15,11 @@ object, at most `--max-objects` per image.  Without the flag nothing but the two
 `--n-classes K` (K > 2) loads a K-class semantic-only model and also writes <name>-sem_mask.png (uint8 class ids at the
 original size, same nearest-neighbour rule) and <name>-sem_mask_color.png (the ids through the palette); -fg_mask.png is
 then (class != 0) * 255.  The class map is taken on the device from the logits (ReSeg.class_map): no softmax comes down.
+`--min-area N`, `--keep largest|all` and `--connectivity 4|8` clean the `--instances` label maps on the device, at model
+resolution and before the up-sampling (ReSeg.clean_instances: the largest connected piece of every instance, or every
+piece as an object of its own; pieces under N pixels dropped).  `--components` needs no instance head: the connected
+components of the predicted class map (ReSeg.split_components; `--min-area`, `--connectivity`, `--max-objects` apply) are
+written as <name>-ins_mask.png, <name>-ins_mask_color.png and <name>-n_objects.npy - the count-the-blobs baseline.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -67,7 +72,7 @@ def write_classes(d, name, classes, out_h, out_w):
     return full
 
 
-def main():
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--lst', default='', help='Text file that contains image paths')
     parser.add_argument('--model', default='', help='Path of the model (state_dict .pth)')
@@ -80,11 +85,45 @@ def main():
     parser.add_argument('--max-objects', type=int, default=32, help='most instances per image with --instances (1..255)')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
-    opt = parser.parse_args()
+    add_cleanup_arguments(parser)
+    opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
     if opt.n_classes > 2 and opt.instances:
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
+    check_cleanup_arguments(parser, opt)
+    return opt
+
+
+def add_cleanup_arguments(parser):
+    parser.add_argument('--min-area', type=int, default=0, help='with --instances or --components: drop connected pieces '
+                        'under N pixels (at model resolution)')
+    parser.add_argument('--keep', choices=['largest', 'all'], default=None, help='with --instances: keep the largest '
+                        'connected piece of every instance, or make every piece an instance of its own')
+    parser.add_argument('--connectivity', type=int, choices=[4, 8], default=8, help='neighbourhood of the connected pieces')
+    parser.add_argument('--components', action='store_true', help='write -ins_mask.png, -ins_mask_color.png and '
+                        '-n_objects.npy from the connected components of the predicted class map (no instance head)')
+
+
+def check_cleanup_arguments(parser, opt):
+    if opt.components and opt.instances:
+        parser.error('--components and --instances both write the -ins_mask files: give one of them')
+    if opt.keep is not None and not opt.instances:
+        parser.error('--keep cleans the instances of --instances')
+    if opt.min_area > 1 and not (opt.instances or opt.components):
+        parser.error('--min-area needs --instances or --components')
+
+
+def cleanup_arguments(opt):
+    """ReSeg.clean_instances' keywords for the --instances label maps, or None when the flags ask for no clean-up."""
+    if opt.keep is None and opt.min_area <= 1:
+        return None
+    return {'keep': opt.keep or 'all', 'connectivity': opt.connectivity, 'min_area': opt.min_area,
+            'max_objects': opt.max_objects}
+
+
+def main():
+    opt = parse_args()
     assert opt.dataset in ['CVPPP', ]                    # pred_list.py:26
     assert opt.lst or opt.synthetic, "give --lst or --synthetic N"
 
@@ -120,9 +159,22 @@ def main():
                 net(False, x)
                 classes = net.class_map()                # uint8 [B,H,W] on the device: one byte per pixel comes down
             sem_arg = (classes != 0).to(torch.float32)[:, None]
+            if opt.components:
+                labels, counts, _ = net.split_components(classes, connectivity=opt.connectivity, min_area=opt.min_area,
+                                                         max_objects=opt.max_objects)
+                labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
             classes = classes.cpu().numpy()
         elif opt.instances:
             _, sem_arg, labels, counts = net.segment(x, opt.max_objects)
+            clean = cleanup_arguments(opt)
+            if clean is not None:                        # at model resolution, before the nearest up-sampling
+                labels, counts, _ = net.clean_instances(labels, **clean)
+            labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
+        elif opt.components:
+            with torch.no_grad():
+                _, sem_arg = net(False, x)
+                labels, counts, _ = net.split_components(net.class_map(), connectivity=opt.connectivity,
+                                                         min_area=opt.min_area, max_objects=opt.max_objects)
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         else:
             _, sem_arg = net.infer_graphed(x) if len(imgs) == opt.batch else net(False, x)
@@ -134,7 +186,7 @@ def main():
             full = nearest_upsample(m, im.shape[0], im.shape[1]) * 255
             Image.fromarray(im).save(os.path.join(d, name + '.png'))
             Image.fromarray(full.astype(np.uint8)).save(os.path.join(d, name + '-fg_mask.png'))
-            if opt.instances:
+            if labels is not None:
                 write_instances(d, name, labels[i], counts[i], im.shape[0], im.shape[1])
             if classes is not None:
                 write_classes(d, name, classes[i], im.shape[0], im.shape[1])
