@@ -510,6 +510,68 @@ int isa_lovasz_assemble(const double* partial, const int32_t* G, const float* cf
                         int64_t hw, double* segloss, float* scale, float* scal, void* stream);
 int isa_lovasz_grad(const isa_tensor* logits, const float* gpix, const float* scale, int32_t per_image,
                     const isa_tensor* dlogits, int32_t accumulate, void* stream);
+/* ---- discriminative embedding loss (losses/discriminative.py: calculate_means 7-62, calculate_variance_term 65-95 (its
+ * hinge branch), calculate_distance_term 98-132, calculate_regularization_term 135-147, calculate_q_regularization_term
+ * 149-160, discriminative_loss 162-188) and its hand-derived backward ----------------------------------------------------
+ * emb x: NHWC [B,H,W,C] (bf16 | fp32, 1 <= C <= 32, ld >= C and a multiple of 8, 16-byte aligned, groups 1, B <= 65535,
+ * L = H*W < 2^31).  labels: uint8 [B, L] as isa_labels_from_planes makes them of k planes (1 <= k <= ISA_DISC_MAX_K; the
+ * first plane wins, so the instances are disjoint): 0 background, i + 1 = instance i; a label above k counts as
+ * background.  n_objects int32 [B], clamped to [0, 32]: planes at index >= n_objects[b] are ignored for the means and the
+ * var / dist / reg terms but stay foreground for qreg, as in the reference.  Instance i of image b is PRESENT when
+ * i < n_objects[b] and N_i > 0 (N_i its pixel count); np_b = present instances, F_b = sum of their N_i.
+ *   m_i = sum_{p in i} x_p / N_i;  mu_i = unit_means ? m_i / |m_i|_2 : m_i                       (both 0 when not present)
+ *   var  = 1/B sum_b 1/F_b sum_{i present} sum_{p in i} max(|x_p - mu_i| - delta_v, 0)^2   (the divisor is the image's
+ *          counted foreground, not the cluster's size: the reference, not the paper)
+ *   dist = 1/B sum_{b: np_b >= 2} sum_{i != j present} max(2 delta_d - |mu_i - mu_j|, 0)^2 / (np_b (np_b - 1))
+ *   reg  = 1/B sum_{b: np_b >= 1} 1/np_b sum_{i present} |mu_i|
+ *   qreg = sum_{b,p} ([label_p != 0] |x_p|_2 - 1)^2 / num, num = foreground pixels of the batch: a background pixel adds the
+ *          constant 1 (kept from the reference); always the L2 norm
+ *   loss = weight (alpha var + beta dist + gamma reg + gamma_q qreg)
+ * |.| is the L1 (norm == 1) or L2 (norm == 2) norm; delta_v, delta_d >= 0.  Where the reference divides 0 by 0 these rules
+ * hold instead: a counted instance with N_i = 0 adds nothing and is not counted in np_b; F_b = 0, np_b < 2 (dist),
+ * np_b = 0 (reg), num = 0 (qreg) give 0; d/|d|_2 is 0 at d = 0; the L1 derivative is sign with sign(0) = 0; m_i = 0 with
+ * unit_means gives mu_i = 0 and no gradient through it.
+ * cfg (device, ISA_DISC_CFG_FLOATS floats, read at run time so that a captured hipGraph follows in-place changes):
+ *   {delta_v, delta_d, norm (informative: the kernels take the call argument), unit_means, alpha, beta, gamma, gamma_q,
+ *    weight, 0, 0, 0}.
+ * Every entry checks all its arguments before it launches or writes anything (ISA_EINVAL / ISA_EALIGN / ISA_EDTYPE),
+ * allocates nothing, never syncs and works on `stream`.  A row is shared by ISA_DISC_CHUNKS(L) <= ISA_ROW_CHUNKS workgroups
+ * that each write a slab of their own; every fold has a fixed order and there are no float atomics: loss, means and
+ * gradient are bit-reproducible.  Scratch is the caller's; none of it has to be cleared.
+ * isa_disc_sums: slab (float, ISA_DISC_SLAB_FLOATS(B, L)) [B][chunks][32][32] = per chunk sum_{p in i} x_p[j], as
+ *   one-hot[32 x P] . x[P x 32] on the f32-input MFMA (exact f32, a fixed fmaf chain; channels C..31 are zero operands);
+ *   cslab (int32, ISA_DISC_CSLAB_INTS(B, L)) [B][chunks][32] = per chunk N_i.
+ * isa_disc_means: one workgroup per image folds the chunks in order.  mu, m (may be NULL) float [B][32][32]; mnorm float
+ *   [B][32] = |m_i|_2; cnt int32 [B][ISA_DISC_CNT_STRIDE] = {N_0 .. N_31 (every plane), F_b, np_b, foreground pixels, 0}.
+ * isa_disc_hinge: hslab (as slab) = per chunk sum_{p in i} h_p d|d|/dd (x_p - mu_i), h_p the hinge of var; partial (double,
+ *   ISA_DISC_PARTIAL_DOUBLES(B, L)) [B][chunks][2] = {sum h_p^2, sum of the qreg summand}.
+ * isa_disc_assemble: two launches.  Per image: the folds, dist and reg over the <= 32 means and their gradients, d loss / d mu
+ *   back through the normalisation (g_m = (g_mu - mu (mu . g_mu)) / |m|_2 when unit_means), gconst float [B][32][32] =
+ *   weight g_m / N_i; coef float [B + 1]: coef[b] = weight 2 alpha / (B F_b), coef[B] = weight 2 gamma_q / num; img double
+ *   [B][8] scratch.  Then one workgroup folds the images in order: scal[8] = {loss, var, dist, reg, qreg, sum_b np_b,
+ *   sum_b F_b, 0} (the loss carries the weight, the four terms do not).
+ * isa_disc_grad: dx_p = coef[b] h_p d|d|/dd + gconst[label_p] + coef[B] (|x_p|_2 - 1) x_p / |x_p|_2 (the last two on
+ *   foreground pixels), recomputed from x, mu and the labels; written to demb (the dtype and shape of emb) or added when
+ *   accumulate != 0; channels >= C of a row untouched. */
+#define ISA_DISC_MAX_K 32
+#define ISA_DISC_CFG_FLOATS 12
+#define ISA_DISC_CNT_STRIDE 36
+#define ISA_DISC_CHUNKS(L) \
+    ((((int64_t)(L) + 1023) / 1024) < ISA_ROW_CHUNKS ? (((int64_t)(L) + 1023) / 1024) : (int64_t)ISA_ROW_CHUNKS)
+#define ISA_DISC_SLAB_FLOATS(n, L) ((int64_t)(n) * ISA_DISC_CHUNKS(L) * 1024)
+#define ISA_DISC_CSLAB_INTS(n, L) ((int64_t)(n) * ISA_DISC_CHUNKS(L) * 32)
+#define ISA_DISC_PARTIAL_DOUBLES(n, L) ((int64_t)(n) * ISA_DISC_CHUNKS(L) * 2)
+int isa_disc_sums(const isa_tensor* emb, const uint8_t* labels, int32_t k, float* slab, int32_t* cslab, void* stream);
+int isa_disc_means(const float* slab, const int32_t* cslab, const int32_t* n_objects, const float* cfg, int32_t n, int64_t L,
+                   float* mu, float* m, float* mnorm, int32_t* cnt, void* stream);
+int isa_disc_hinge(const isa_tensor* emb, const uint8_t* labels, int32_t k, const int32_t* n_objects, const float* mu,
+                   const float* cfg, int32_t norm, float* hslab, double* partial, void* stream);
+int isa_disc_assemble(const float* hslab, const double* partial, const float* mu, const float* mnorm, const int32_t* cnt,
+                      const int32_t* n_objects, const float* cfg, int32_t norm, int32_t n, int64_t L, float* gconst,
+                      float* coef, double* img, float* scal, void* stream);
+int isa_disc_grad(const isa_tensor* emb, const uint8_t* labels, int32_t k, const int32_t* n_objects, const float* mu,
+                  const float* gconst, const float* coef, const float* cfg, int32_t norm, const isa_tensor* demb,
+                  int32_t accumulate, void* stream);
 /* reference-format targets: int64 one-hot [n,k,h,w] -> uint8 labels [n,h,w] and / or the fp32 argmax(1) map [n, h*w]
  * (sem_seg_argmax, reseg.py:118); the first maximum wins, as in torch.argmax.  Either output may be NULL, not both. */
 int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t hw, uint8_t* labels, float* argmax_map,

@@ -326,17 +326,40 @@ class InstanceHead:
         return E.bn_out(y3, s3, pre + ".conv.7", L.ACT_NONE, out, res=x if x.c == cout else None,
                         res2=res2, oscale=oscale)
 
+    # ------------------------------------------------------------------ discriminative loss on the embedding
+    def disc_loss(self, x_enc: Act, ins: torch.Tensor, n_obj: torch.Tensor) -> torch.Tensor:
+        """The discriminative embedding loss (Network.disc_loss; settings in net.disc) on the instance embedding x_enc
+        against the step's instance planes: the label map once, the four forward launches, and one tape closure that adds
+        the loss's gradient into d(x_enc).  Returns scal [8]."""
+        E, net = self.E, self.net
+        n, k, Lp = ins.shape[0], ins.shape[1], x_enc.h * x_enc.w
+        assert ins.dtype == torch.int64 and 1 <= k <= L.DISC_MAX_K, "instance planes: int64 [n,K,h,w], K <= 32"
+        labels = E.arena.alloc((n, Lp), torch.uint8)
+        L.check(E.lib.isa_labels_from_planes(L.ptr(ins), L.PLANES_I64_NKHW, n, k, Lp, L.ptr(labels), E.st()),
+                "isa_labels_from_planes")
+        scal, _, grad = net.disc_loss(x_enc, labels, k, n_obj, net.disc.cfg, net.disc.norm)
+        if E.record:
+            def bwd_disc():
+                acc = E.grads.claim(x_enc, E)
+                grad(E.grads.grad_of(x_enc), acc)
+            E.tape.append(bwd_disc)
+        return scal
+
     # ------------------------------------------------------------------ driver (attenet2.py:357-407)
     def forward(self, x_dec: Act, feats, sem_map: torch.Tensor, ins: torch.Tensor, n_ins, training: bool,
-                selected_idx, injected_s_t=None, capture=None, idx_dev=None):
+                selected_idx, injected_s_t=None, capture=None, idx_dev=None, disc=None):
         """sem_map: fp32 [n, h*w] {0,1}; ins: int64 [n,32,h,w] on device; n_ins: host ints;
         selected_idx[b]: instance order; injected_s_t: optional list of int32 device vectors (train
-        sampling is injected, SURVEY §7 'RNG parity').  Returns dict of per-iteration records."""
+        sampling is injected, SURVEY §7 'RNG parity').  disc (the trainer's, when the discriminative embedding loss is on):
+        dict(n_obj = the object counts, int32 [n] on the device); it receives `scal`, the loss's eight scalars.
+        Returns dict of per-iteration records."""
         E = self.E
         n, H, W = x_dec.n, x_dec.h, x_dec.w
         Lp = H * W
         nobj = ins.shape[1]
         x_enc = self.stems(x_dec)
+        if disc is not None:
+            disc["scal"] = self.disc_loss(x_enc, ins, disc["n_obj"])
         s = self.spatial_attention(x_enc, sem_map)
         merge = self.hard_attention_scores(s, sem_map)
         nmin = int(min(int(v) for v in n_ins))

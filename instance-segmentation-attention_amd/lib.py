@@ -39,6 +39,14 @@ def cc_select_scratch_bytes(n, h, w):
     return n * (h * w * 4 + CC_TAB_BYTES)
 
 
+DISC_MAX_K, DISC_CFG_FLOATS, DISC_CNT_STRIDE, ROW_CHUNKS = 32, 12, 36, 64     # ISA_DISC_*, ISA_ROW_CHUNKS
+
+
+def disc_chunks(L):
+    """ISA_DISC_CHUNKS: workgroups that share one image's pixels in the discriminative-loss passes."""
+    return min((L + 1023) // 1024, ROW_CHUNKS)
+
+
 PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SATURATION, PHOTO_HUE = 0, 1, 2, 3
 
 _ERR = {-1: "ISA_EINVAL", -2: "ISA_EALIGN", -3: "ISA_EDTYPE", -4: "ISA_ELAUNCH", -5: "ISA_ENOMEM"}
@@ -163,6 +171,12 @@ SIGNATURES = {
     "isa_lovasz_coef": [VP, VP, VP, I32, I64, VP, VP, VP, VP],
     "isa_lovasz_assemble": [VP, VP, VP, I32, I32, I32, I64, VP, VP, VP, VP],
     "isa_lovasz_grad": [P_T, VP, VP, I32, P_T, I32, VP],
+    # discriminative embedding loss (ReSeg.discriminative_loss, Trainer(disc_weight=...))
+    "isa_disc_sums": [P_T, VP, I32, VP, VP, VP],
+    "isa_disc_means": [VP, VP, VP, VP, I32, I64, VP, VP, VP, VP, VP],
+    "isa_disc_hinge": [P_T, VP, I32, VP, VP, VP, I32, VP, VP, VP],
+    "isa_disc_assemble": [VP, VP, VP, VP, VP, VP, VP, I32, I32, I64, VP, VP, VP, VP, VP],
+    "isa_disc_grad": [P_T, VP, I32, VP, VP, VP, VP, VP, I32, P_T, I32, VP],
     "isa_ins_softmax_bwd": [VP, VP, VP, VP, VP, I32, I32, I64, VP, I32, VP],
     "isa_maskbn_bwd": [P_T, VP, VP, VP, VP, F, VP, I32, VP, VP, VP, VP, P_T, I32, VP],
     "isa_sp_bwd": [P_T, P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, F, I32, VP, P_T, I32,

@@ -55,13 +55,13 @@ class Model(object):
     # ------------------------------------------------------------------ training
     def __define_optimizer(self, learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm,
                            optimizer='Adadelta', criterion='Multi', class_weights=None, optimize_bg=False,
-                           train_cnn=True, lovasz_per_image=False, lovasz_only_present=False):
+                           train_cnn=True, lovasz_per_image=False, lovasz_only_present=False, disc=None):
         assert optimizer in ['RMSprop', 'Adam', 'Adadelta', 'SGD']            # model.py:147
         # the criterion of __define_criterion (model.py:102-133): CE(weight) and / or Dice(optimize_bg, weight)
         self.trainer = Trainer(self.model, world_size=self.world, lr=learning_rate, weight_decay=weight_decay,
                                clip_grad_norm=clip_grad_norm, criterion=criterion, class_weights=class_weights,
                                optimize_bg=optimize_bg, optimizer=optimizer, train_cnn=train_cnn,
-                               lovasz_per_image=lovasz_per_image, lovasz_only_present=lovasz_only_present)
+                               lovasz_per_image=lovasz_per_image, lovasz_only_present=lovasz_only_present, **(disc or {}))
         self._plateau = dict(best=float('inf'), bad=0, factor=lr_drop_factor, patience=lr_drop_patience)
 
     def __plateau_step(self, val):                   # torch ReduceLROnPlateau(mode='min') semantics, rel 1e-4
@@ -108,6 +108,8 @@ class Model(object):
         if h is not None:                                 # semantic-only models have no instance head (model.py:244)
             row.update({'INS Cost': h[0] + float('nan'), 'Criterion': h[1].clone(), 'ins_ce_loss': h[2].clone(),
                         'ins_dice_loss': h[3].clone()})
+        if 'disc' in out:                                 # the discriminative embedding loss, weight included
+            row['Disc Cost'] = out['disc'][0].clone()
         return row
 
     def __score_batch(self, batch, max_objects, check, clean=None):
@@ -151,7 +153,11 @@ class Model(object):
 
     def fit(self, criterion_type, delta_var, delta_dist, norm, learning_rate, weight_decay, clip_grad_norm,
             lr_drop_factor, lr_drop_patience, optimize_bg, optimizer, train_cnn, n_epochs, class_weights,
-            train_loader, test_loader, model_save_path, debug, lovasz_per_image=None, lovasz_only_present=None):
+            train_loader, test_loader, model_save_path, debug, lovasz_per_image=None, lovasz_only_present=None,
+            disc_weight=0.0, disc_form='reference'):
+        """model.py:359-460.  delta_var, delta_dist, norm: the parameters of the reference's DiscriminativeLoss
+        (model.py:109-115, which it builds and never calls); here the loss trains the instance embedding when
+        disc_weight > 0, in the form disc_form ('reference' | 'full', ReSeg.discriminative_loss)."""
         assert criterion_type in ['CE', 'Dice', 'Multi', 'Lovasz', 'CELovasz']  # model.py:364, and the Lovasz criteria
         if lovasz_per_image is None:
             lovasz_per_image = self.lovasz_per_image
@@ -173,7 +179,9 @@ class Model(object):
                 mlog.write('Epoch,mIoU,PixelAcc,mDice\n')
         self.__define_optimizer(learning_rate, weight_decay, lr_drop_factor, lr_drop_patience, clip_grad_norm, optimizer,
                                 criterion_type, class_weights, optimize_bg, train_cnn, lovasz_per_image,
-                                lovasz_only_present)
+                                lovasz_only_present,
+                                dict(disc_weight=disc_weight, delta_var=delta_var, delta_dist=delta_dist, disc_norm=norm,
+                                     disc_form=disc_form))
         best_val_cost = np.inf
         if os.environ.get('ISA_PREFETCH', '1') != '0':      # batch i+1 uploads on a side stream while step i runs
             from .data import DevicePrefetcher

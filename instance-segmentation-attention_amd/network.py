@@ -71,12 +71,56 @@ class SemCriterion:
         return self.cfg[4:]
 
 
+DISC_FORMS = {"reference": (True, (1.0, 0.0, 0.0, 0.005)), "full": (False, (1.0, 1.0, 0.001, 0.0))}
+
+
+class DiscCriterion:
+    """Settings of the discriminative embedding loss (DiscriminativeLoss, losses/discriminative.py:162-213) in ONE device
+    buffer, allocated once and rewritten in place so that a captured hipGraph reads them at replay time.  Layout
+    (include/isa_kernels.h, isa_disc_*): {delta_v, delta_d, norm, unit_means, alpha, beta, gamma, gamma_q, weight, 0, 0, 0}.
+    form 'reference': what discriminative_loss() computes (unit means, var + 0.005 qreg); 'full': var + dist + 0.001 reg on
+    plain means; `weights` = (alpha, beta, gamma, gamma_q) and `unit_means` override the form's.  The loss runs when
+    weight > 0; on / off, the form and the norm belong to a captured step's configuration (key()), the rest does not."""
+
+    def __init__(self, device):
+        self.cfg = torch.zeros(L.DISC_CFG_FLOATS, dtype=torch.float32, device=device)
+        self.set(0.0)
+
+    def set(self, weight, delta_var=0.5, delta_dist=1.5, norm=2, form="reference", weights=None, unit_means=None):
+        if form not in DISC_FORMS:
+            raise ValueError("form must be one of %s, got %r" % (tuple(DISC_FORMS), form))
+        if int(norm) not in (1, 2):
+            raise ValueError("norm must be 1 or 2, got %r" % (norm,))
+        if float(delta_var) < 0 or float(delta_dist) < 0 or float(weight) < 0:
+            raise ValueError("delta_var, delta_dist and the weight must not be negative")
+        unit, w = DISC_FORMS[form]
+        if weights is not None:
+            w = tuple(float(v) for v in weights)
+            if len(w) != 4:
+                raise ValueError("weights: (alpha, beta, gamma, gamma_q)")
+        if unit_means is not None:
+            unit = bool(unit_means)
+        self.weight, self.norm, self.form, self.on = float(weight), int(norm), form, float(weight) > 0
+        self.cfg.copy_(torch.tensor([float(delta_var), float(delta_dist), float(norm), float(unit)] + list(w) +
+                                    [float(weight), 0.0, 0.0, 0.0]))
+
+    def set_weight(self, weight):
+        """In place: a captured step follows it (on / off is part of the step's configuration and stays)."""
+        assert float(weight) > 0 and self.on, "the weight of a running loss; switch it on or off with set()"
+        self.weight = float(weight)
+        self.cfg[8:9].fill_(float(weight))
+
+    def key(self):
+        return (True, self.form, self.norm) if self.on else (False, None, None)
+
+
 class Network:
     def __init__(self, eng: Engine, use_instance_seg=True, n_classes=2):
         self.E = eng
         self.use_instance_seg = use_instance_seg
         self.n_classes = n_classes
         self.crit = SemCriterion(n_classes, eng.device)
+        self.disc = DiscCriterion(eng.device)
 
     # ------------------------------------------------------------------ blocks
     def block_v1(self, x: Act, pre: str, out: Act):
@@ -299,6 +343,37 @@ class Network:
                         "isa_lovasz_grad")
             E.tape.append(bwd)
         return scal
+
+    def disc_loss(self, emb: Act, labels: torch.Tensor, k, n_obj: torch.Tensor, cfg: torch.Tensor, norm, alloc=None):
+        """The forward launches of the discriminative embedding loss on `emb` (isa_disc_sums, _means, _hinge, _assemble):
+        labels uint8 [n, h*w] of k planes, n_obj int32 [n], cfg the settings buffer.  Returns (scal [8] = {loss, var, dist,
+        reg, qreg, present instances, their pixels, 0}, mu [n,32,32], grad) where grad(demb: Act, accumulate) launches
+        isa_disc_grad.  alloc(shape, dtype): where the scratch comes from (default: the step's arena)."""
+        E = self.E
+        alloc = alloc or E.arena.alloc
+        n, hw = emb.n, emb.h * emb.w
+        ch = L.disc_chunks(hw)
+        f32, i32 = torch.float32, torch.int32
+        slab, hslab = alloc((n * ch * 1024,), f32), alloc((n * ch * 1024,), f32)
+        cslab = alloc((n * ch * 32,), i32)
+        mu, m, gconst = alloc((n, 32, 32), f32), alloc((n, 32, 32), f32), alloc((n, 32, 32), f32)
+        mnorm, cnt = alloc((n * 32,), f32), alloc((n * L.DISC_CNT_STRIDE,), i32)
+        partial, img = alloc((n * ch * 2,), torch.float64), alloc((n * 8,), torch.float64)
+        coef, scal = alloc((n + 1,), f32), alloc((8,), f32)
+        lp, np_, cp = L.ptr(labels), L.ptr(n_obj), L.ptr(cfg)
+        L.check(E.lib.isa_disc_sums(emb.d(), lp, k, L.ptr(slab), L.ptr(cslab), E.st()), "isa_disc_sums")
+        L.check(E.lib.isa_disc_means(L.ptr(slab), L.ptr(cslab), np_, cp, n, hw, L.ptr(mu), L.ptr(m), L.ptr(mnorm), L.ptr(cnt),
+                                     E.st()), "isa_disc_means")
+        L.check(E.lib.isa_disc_hinge(emb.d(), lp, k, np_, L.ptr(mu), cp, norm, L.ptr(hslab), L.ptr(partial), E.st()),
+                "isa_disc_hinge")
+        L.check(E.lib.isa_disc_assemble(L.ptr(hslab), L.ptr(partial), L.ptr(mu), L.ptr(mnorm), L.ptr(cnt), np_, cp, norm, n, hw,
+                                        L.ptr(gconst), L.ptr(coef), L.ptr(img), L.ptr(scal), E.st()), "isa_disc_assemble")
+
+        def grad(demb: Act, accumulate):
+            L.check(E.lib.isa_disc_grad(emb.d(), lp, k, np_, L.ptr(mu), L.ptr(gconst), L.ptr(coef), cp, norm, demb.d(),
+                                        int(accumulate), E.st()), "isa_disc_grad")
+        grad.keep = (labels, n_obj, cfg)
+        return scal, mu, grad
 
     def onehot_map(self, sem_onehot: torch.Tensor) -> torch.Tensor:
         """int64 one-hot [n,K,h,w] -> fp32 argmax(1) map [n, h*w] (sem_seg_argmax of reseg.py:118, on the device)."""

@@ -351,6 +351,57 @@ class ReSeg(nn.Module):
                                          % (int(row.sum()), torch.nonzero(row).view(-1).tolist(), limit))
             return out
 
+    # ------------------------------------------------------------------ discriminative embedding loss
+    def discriminative_loss(self, emb, ins, n_objects, delta_var=0.5, delta_dist=1.5, norm=2, form='reference',
+                            weights=None, unit_means=None, grad=False):
+        """The discriminative (pull / push) loss of an instance embedding, on the device (DiscriminativeLoss,
+        losses/discriminative.py:162-213; isa_disc_*).  emb: float [B,C,H,W] (fp32 or bf16, C <= 32)
+        or an engine Act; ins: the instance planes in any form isa_labels_from_planes takes (uint8 [B,H,W,K], int64 or fp32
+        [B,K,H,W], K <= 32; overlapping planes: the first one gets the pixel) or a ready uint8 label map [B,H,W] (0 =
+        background, i + 1 = plane i); n_objects [B] or [B,1]: planes past it are ignored by the means and the var / dist /
+        reg terms and stay foreground for qreg.  form 'reference' = var + 0.005 qreg on unit-length means (what the
+        reference's discriminative_loss computes), 'full' = var + dist + 0.001 reg on plain means; weights = (alpha, beta,
+        gamma, gamma_q) and unit_means override the form's.  Returns a dict of device tensors: loss, var, dist, reg, qreg
+        (scalars) and means [B,K,C]; with grad=True also grad = d loss / d emb, shaped like emb (an Act for an Act).  Nothing
+        is read back: the call does not synchronise."""
+        from .engine import Act, rup
+        from .network import DiscCriterion
+        dev = self.store.device
+        with torch.no_grad():
+            if isinstance(emb, Act):
+                a, as_act = emb, True
+            else:
+                as_act = False
+                t = emb.to(dev)
+                if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError("emb: fp32 or bf16 [B,C,H,W] or an engine Act, got %s %s" % (t.dtype, tuple(t.shape)))
+                B, C, H, W = t.shape
+                buf = torch.zeros((B, H, W, rup(C, 8)), dtype=t.dtype, device=dev)
+                buf[..., :C].copy_(t.permute(0, 2, 3, 1))
+                a = Act(buf, 0, C)
+            if not 1 <= a.c <= 32:
+                raise ValueError("emb: 1..32 channels, got %d" % a.c)
+            lab = ins.to(dev).contiguous()
+            if lab.dtype == torch.uint8 and lab.dim() == 3:
+                labels, k = lab.view(lab.shape[0], -1), L.DISC_MAX_K
+            else:
+                labels, k = self._label_map(lab, "ins")
+            if not 1 <= k <= L.DISC_MAX_K:
+                raise ValueError("ins: 1..32 planes, got %d" % k)
+            assert tuple(labels.shape) == (a.n, a.h * a.w), "ins and emb differ in size"
+            n_obj = n_objects.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            assert n_obj.numel() == a.n
+            crit = DiscCriterion(dev)
+            crit.set(1.0, delta_var, delta_dist, norm, form, weights, unit_means)
+            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+            scal, mu, gfn = self.net.disc_loss(a, labels, k, n_obj, crit.cfg, crit.norm, alloc)
+            out = dict(loss=scal[0], var=scal[1], dist=scal[2], reg=scal[3], qreg=scal[4], means=mu[:, :k, :a.c])
+            if grad:
+                g = Act(torch.empty_like(a.buf), a.c0, a.c)
+                gfn(g, 0)
+                out["grad"] = g if as_act else g.buf[..., :a.c].permute(0, 3, 1, 2)
+            return out
+
     # ------------------------------------------------------------------ connected components, cleaning instance maps
     def _cc_map(self, maps, connectivity, min_area=1, max_objects=255):
         t = maps.to(self.store.device).contiguous()

@@ -32,7 +32,8 @@ def frozen_prefix(store):
 class Trainer:
     def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6,
                  criterion='Multi', class_weights=None, optimize_bg=False, optimizer='Adadelta', train_cnn=True,
-                 lovasz_per_image=False, lovasz_only_present=False):
+                 lovasz_per_image=False, lovasz_only_present=False, disc_weight=0.0, delta_var=0.5, delta_dist=1.5,
+                 disc_norm=2, disc_form='reference'):
         assert optimizer in OPTIMIZERS, optimizer
         self.model = model
         self.optimizer, self.train_cnn = optimizer, bool(train_cnn)
@@ -40,6 +41,9 @@ class Trainer:
         # allocated with the model - a captured step keeps reading the same device memory
         model.set_criterion(criterion, class_weights, optimize_bg, lovasz_per_image, lovasz_only_present)
         self.criterion = criterion
+        # the discriminative loss on the instance embedding (DiscriminativeLoss(delta_var, delta_dist, norm), model.py:109-115):
+        # runs when disc_weight > 0 and the model has an instance head; its settings live in a device buffer of the model
+        model.net.disc.set(disc_weight, delta_var, delta_dist, disc_norm, disc_form)
         self.world = world_size
         self.lr, self.wd, self.clip, self.rho, self.eps = lr, weight_decay, clip_grad_norm, rho, eps
         st = model.store
@@ -77,10 +81,12 @@ class Trainer:
         self._graphs = {}
 
     def forward_backward(self, x, sem, ins, n_objects, selected_idx=None, injected_s_t=None, capture=None,
-                         idx_dev=None, arena_key=None, backward=True):
+                         idx_dev=None, arena_key=None, backward=True, n_obj_dev=None):
         """Forward + backward; gradients land in model.store.grad.  Returns device scalars
         dict(sem=[ce, dice] ([ce, 0, lovasz] for the Lovasz criteria), head=[ins_cost_finite, criterion, ins_ce,
-        ins_dice]).  backward=False: the training-mode forward alone (batch statistics, sampling, Dropout2d, losses; no
+        ins_dice]) and, when the discriminative embedding loss is on, disc=[weighted loss, var, dist, reg, qreg, present
+        instances, their pixels, 0].  n_obj_dev: the object counts as int32 [B] on the device (the captured step stages
+        them).  backward=False: the training-mode forward alone (batch statistics, sampling, Dropout2d, losses; no
         tape) - the forward-only benchmark line."""
         m = self.model
         E, net, st = m.engine, m.net, m.store
@@ -117,14 +123,25 @@ class Trainer:
                     random.shuffle(order)
                     selected_idx.append(order)
             sem_map = net.onehot_map(sem)                    # GT.argmax(1) (reseg.py:118) as the fp32 map the head reads
+            disc = None
+            if net.disc.on:
+                disc = dict(n_obj=n_obj_dev if n_obj_dev is not None else
+                            torch.tensor(n_ins, dtype=torch.int32, device=dev))
             rec = m.head.forward(x_dec, feats, sem_map, ins, n_ins, True, selected_idx, injected_s_t, capture,
-                                 idx_dev=idx_dev)
+                                 idx_dev=idx_dev, disc=disc)
             m.last_record = rec
             head_scal = rec["scal"]
         if backward:
             E.backward()
         self.last = dict(sem=sem_scal, head=head_scal)
+        if m.use_instance_seg and net.disc.on:
+            self.last["disc"] = disc["scal"]
         return self.last
+
+    def set_disc_weight(self, weight):
+        """A new weight (> 0) of the running discriminative loss, written in place into its device settings: a captured
+        step follows without re-capture.  Switching the loss on or off is a new Trainer."""
+        self.model.net.disc.set_weight(weight)
 
     @property
     def class_weights(self):
@@ -202,7 +219,10 @@ class Trainer:
                m.engine.dtype, injected_s_t is not None, x.dtype == torch.uint8, ins.dtype == torch.uint8, bool(forward_only),
                # the Lovasz criteria have launches of their own (CELovasz three more than Lovasz), and per_image sets
                # their segment geometry
-               m.net.crit.criterion if m.net.crit.lovasz else None, m.net.crit.lovasz and m.net.crit.lovasz_per_image)
+               m.net.crit.criterion if m.net.crit.lovasz else None, m.net.crit.lovasz and m.net.crit.lovasz_per_image,
+               # the discriminative loss: on / off adds launches, form and norm pick kernels; weight and deltas do not
+               m.net.disc.key() if m.use_instance_seg else None)
+        disc_on = m.use_instance_seg and m.net.disc.on
         slot = self._graphs.get(key)
         akey = ("train_graph",) + key            # the captured configuration owns its arena (frozen after capture)
         self.sync_lr()
@@ -225,14 +245,18 @@ class Trainer:
             slot["idx"] = torch.zeros((max(max_iter, 1), x.shape[0]), dtype=torch.int32, device=dev)
             slot["idx_pin"] = torch.zeros((max(max_iter, 1), x.shape[0]), dtype=torch.int32).pin_memory()
             slot["inj"] = None if injected_s_t is None else [torch.zeros_like(t) for t in injected_s_t[:max_iter]]
-            self._stage(slot, x, sem, ins, selected_idx, max_iter, injected_s_t)
+            if disc_on:                          # the object counts the discriminative loss reads on the device
+                slot["nobj"] = torch.zeros(x.shape[0], dtype=torch.int32, device=dev)
+                slot["nobj_pin"] = torch.zeros(x.shape[0], dtype=torch.int32).pin_memory()
+            self._stage(slot, x, sem, ins, selected_idx, max_iter, injected_s_t, n_ins)
             before = dict(st.int_buffers)
             g = torch.cuda.CUDAGraph()
             try:
                 # thread_local: the RCCL watchdog thread may query events while this thread captures
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     out = self.forward_backward(slot["x"], slot["sem"], slot["ins"], n_ins, idx_dev=slot["idx"],
-                                                injected_s_t=slot["inj"], arena_key=akey, backward=not forward_only)
+                                                injected_s_t=slot["inj"], arena_key=akey, backward=not forward_only,
+                                                n_obj_dev=slot.get("nobj"))
                     if self.world == 1 and not forward_only:
                         self.apply_update()
                 m.engine.freeze_arena()
@@ -249,7 +273,7 @@ class Trainer:
             st.int_buffers.update(before)
             slot.update(state="ready", graph=g, out=out)
         else:
-            self._stage(slot, x, sem, ins, selected_idx, max_iter, injected_s_t)
+            self._stage(slot, x, sem, ins, selected_idx, max_iter, injected_s_t, n_ins)
         slot["graph"].replay()
         for k, v in slot["bumps"].items():
             st.int_buffers[k] += v
@@ -266,7 +290,10 @@ class Trainer:
         train_step_graphed, which then replays without any staging copy."""
         return [(s["x"], s["sem"], s["ins"]) for s in reversed(list(self._graphs.values())) if s.get("state") == "ready"]
 
-    def _stage(self, slot, x, sem, ins, selected_idx, max_iter, injected_s_t=None):
+    def _stage(self, slot, x, sem, ins, selected_idx, max_iter, injected_s_t=None, n_ins=None):
+        if slot.get("nobj") is not None:
+            slot["nobj_pin"].copy_(torch.tensor(n_ins, dtype=torch.int32))
+            slot["nobj"].copy_(slot["nobj_pin"], non_blocking=True)
         if slot.get("inj") is not None:          # parity runs: glimpse points fixed from outside
             for dst, src in zip(slot["inj"], injected_s_t):
                 dst.copy_(src, non_blocking=True)

@@ -45,6 +45,13 @@ def build_parser():
                         '(lovasz_softmax per_image; Model.lovasz_per_image)')
     parser.add_argument('--lovasz-present', action='store_true', help='Lovasz / CELovasz: average only the classes present in '
                         'the ground truth (lovasz_softmax only_present; Model.lovasz_only_present)')
+    # the discriminative loss on the instance embedding (training_settings.py: DELTA_VAR, DELTA_DIST, NORM); off at weight 0
+    parser.add_argument('--disc-weight', type=float, default=0.0, help='weight of the discriminative embedding loss (0: off)')
+    parser.add_argument('--delta-var', type=float, default=0.5, help='pull margin of the discriminative loss')
+    parser.add_argument('--delta-dist', type=float, default=1.5, help='push margin of the discriminative loss')
+    parser.add_argument('--disc-norm', type=int, default=2, choices=[1, 2], help='norm of the discriminative loss')
+    parser.add_argument('--disc-form', default='reference', choices=['reference', 'full'],
+                        help="'reference': var + 0.005 qreg on unit means; 'full': var + dist + 0.001 reg")
     parser.add_argument('--class-weights', default=None, help='one weight per class, comma separated (w0,w1,...)')
     parser.add_argument('--optimize-bg', action='store_true', help='Dice over every class, background included')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes, 2..32 (more than 2 needs --semantic-only)')
@@ -91,7 +98,7 @@ def parse_args(argv=None):
 
 def fit_arguments(opt):
     """Model.fit's arguments ahead of the loaders, as the reference's train.py passes them (training_settings.py)."""
-    return (opt.criterion, 0.5, 1.5, 2, opt.lr, opt.weight_decay, 10.0, 0.5, 25, opt.optimize_bg, opt.optimizer,
+    return (opt.criterion, opt.delta_var, opt.delta_dist, opt.disc_norm, opt.lr, opt.weight_decay, 10.0, 0.5, 25, opt.optimize_bg, opt.optimizer,
             not opt.freeze_cnn, opt.nepochs, opt.class_weights)
 
 
@@ -130,7 +137,8 @@ def main(argv=None):
                                     mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt))
         test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
                                    mode='test', seed=SEED, rank=rank, world=world)
-    model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug)
+    model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug, disc_weight=opt.disc_weight,
+              disc_form=opt.disc_form)
     if world > 1:
         torch.distributed.destroy_process_group()
 
