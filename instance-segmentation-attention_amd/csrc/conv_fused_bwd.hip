@@ -8,7 +8,8 @@
 // Built on the bf16 weight-gradient kernel's structure (conv_wgrad.hip): every WAVE owns 32-pixel chunks,
 // staged row-major in a wave-private LDS slab; no __syncthreads in the main loop; the next chunk's raw
 // 16-byte loads are in flight while the current chunk's MFMAs run (the BN/ReLU6 arithmetic is done when the
-// registers are stashed to LDS, not when they are fetched).
+// registers are stashed to LDS, not when they are fetched).  The first chunk's loads leave before the weights and the
+// constants are staged, and the four waves' weight-gradient fragments are folded in one parallel pass (tr_lds.hpp).
 //   wgrad:  dW[n][k] += sum_px dy[px][n] x[px][k]   A/B fragments by ds_read_b64_tr_b16 (pixel-contraction)
 //   dgrad:  dx[px][k] = sum_n  dy[px][n] W[n][k]    A = ds_read_b128 rows of the SAME dy slab,
 //                                                    B = W fragments held in registers for the whole kernel
@@ -31,10 +32,17 @@ struct PwParams {
     int G;                               // statistic groups: M is per group (common.hpp)
 };
 
+#ifdef ISA_PHASE_TRACE
+__device__ unsigned long long phase_buf[10];
+#endif
+
 // XMODE 0: plain x; 1: x = relu6(scale*x+shift) with BN(x) sums produced; 2: runtime prologue, sums if p.xred
-template <int TN, int TK, int YACT, int XMODE>
+// EPI: the store epilogue adds the old dx and / or the residual addend (p.accumulate, p.addend); without it their
+// loads and the waits that go with them are compiled out
+template <int TN, int TK, int YACT, int XMODE, bool EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pw_bn_bwd_kernel(PwParams p) {
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
+    PHASE_DECL(); PHASE(0);
     constexpr int PMB = 32;
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     constexpr int SLAB = PMB * (SN + SK);
@@ -62,14 +70,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int cgn = lane % VN, rown = lane / VN, cgk = lane % VK, rowk = lane / VK;
     const int cn0 = cgn * 8, ck0 = cgk * 8;
     const bool nok = cn0 < p.N, kok = ck0 < p.K;
+    const int cnl = nok ? cn0 : 0, ckl = kok ? ck0 : 0;           // clamped: a 16-byte piece that exists in every row
+
+    bf16x8 rg[LOADS_N], ry[LOADS_N], rx[LOADS_K], rxc[LOADS_K];
+    const long nchunks = (p.M + PMB - 1) / PMB;
+    // raw 16-byte loads only, for EVERY lane at a clamped address and with no branch in front: nothing here waits on
+    // memory, and the number of loads in flight is the same on every path.  stash() zeroes what lies past M, N or K.
+    auto fetch = [&](long chunk) {
+        const long mbase = chunk * PMB;
+#pragma unroll
+        for (int v = 0; v < LOADS_N; ++v) {
+            const long m = min(mbase + v * RPN + rown, p.M - 1);
+            rg[v] = *reinterpret_cast<const bf16x8*>(p.g + m * p.ldg + cnl);
+            ry[v] = *reinterpret_cast<const bf16x8*>(p.y + m * p.ldy + cnl);
+        }
+#pragma unroll
+        for (int v = 0; v < LOADS_K; ++v) {
+            const long m = min(mbase + v * RPK + rowk, p.M - 1);
+            rx[v] = *reinterpret_cast<const bf16x8*>(p.x + m * p.ldx + ckl);
+        }
+    };
+    // the first chunk's loads leave before anything else: they are HBM-cold, and the W staging, the constants and the
+    // two barriers of the prologue below used to stand in front of them in every workgroup
+    const long stride = (long)gs.nbx * 4;
+    long chunk = (long)gs.bx * 4 + wave;
+    if (chunk < nchunks) fetch(chunk);
+
     // per-channel constants live in LDS (shared by the four waves) and are re-read at each stash: holding the
     // 9 x 8 floats per lane in registers costs a whole occupancy step
     float* cst = reinterpret_cast<float*>(ldsb + 4 * SLAB);       // [9][64]
-    // W (N x K fp32, <= 16 KB) is staged through the still-unused slab area with coalesced loads: building the MFMA
-    // fragments straight from global memory was 8 * NS * TK dependent scalar loads per lane - a phase trace of a small
-    // launch showed 38 k of its 85 k cycles (64 -> 64 channels) in that prologue
-    float* wl = reinterpret_cast<float*>(ldsb);
-    for (int i = tid; i < p.N * p.K; i += 256) wl[i] = p.w[i];
+    // W (N x K fp32, <= 16 KB) is staged through the still-unused slab area with coalesced loads (building the MFMA
+    // fragments straight from global memory was 8 * NS * TK dependent scalar loads per lane).  It is staged as the
+    // fragments want it: rounded to bf16 (the one rounding of each fp32 weight), transposed to [k][n] and zero-padded
+    // to the TN*32 x TK*32 tile, so that a fragment is ONE unconditional 16-byte LDS read; the predicated form was
+    // 8 * NS * TK single reads, each in an exec-mask region of its own.
+    constexpr int WP = TN * 32 + 8;                               // row pitch (bf16): rows stay 16-byte aligned
+    bf16_t* wl = reinterpret_cast<bf16_t*>(ldsb);
+    float wv[TN * TK * 4];                                        // requested here, written to LDS after the constants:
+#pragma unroll                                                    // both sets of loads are in flight together
+    for (int it = 0; it < TN * TK * 4; ++it) {                    // clamped address, select after: loads back to back
+        const int i = it * 256 + tid, n = i / (TK * 32), k = i % (TK * 32);
+        wv[it] = p.w[min(n, p.N - 1) * p.K + min(k, p.K - 1)];
+    }
     if (tid < 64) {
         const int cn = min(tid, p.N - 1), ck = min(tid, p.K - 1);
         cst[0 * 64 + tid] = p.ysc[cn]; cst[1 * 64 + tid] = p.ysh[cn]; cst[2 * 64 + tid] = p.ymu[cn];
@@ -85,24 +127,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         cst[5 * 64 + tid] = (XMODE && p.xsc) ? p.xsc[ck] : 1.f; cst[6 * 64 + tid] = (XMODE && p.xsh) ? p.xsh[ck] : 0.f;
         cst[7 * 64 + tid] = (XMODE && p.xmu) ? p.xmu[ck] : 0.f; cst[8 * 64 + tid] = (XMODE && p.xis) ? p.xis[ck] : 1.f;
     }
+#pragma unroll
+    for (int it = 0; it < TN * TK * 4; ++it) {
+        const int i = it * 256 + tid, n = i / (TK * 32), k = i % (TK * 32);
+        wl[k * WP + n] = (bf16_t)((n < p.N && k < p.K) ? wv[it] : 0.f);
+    }
     __syncthreads();
+    PHASE(1);
     auto ldc = [&](int which, int c0, float (&v)[8]) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(cst + which * 64 + c0), b = *reinterpret_cast<const f32x4*>(cst + which * 64 + c0 + 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
     };
-    // ---- W fragments for the data gradient: B[n = 16 s + 8 hh + jj][k = 32 j + r], rounded to bf16 once
+    // ---- W fragments for the data gradient: B[n = 16 s + 8 hh + jj][k = 32 j + r]
     bf16x8 wb[NS][TK];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
         for (int j = 0; j < TK; ++j)
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                const int n = 16 * s + 8 * hh + jj, k = 32 * j + r;
-                wb[s][j][jj] = (bf16_t)((n < p.N && k < p.K) ? wl[n * p.K + k] : 0.f);
-            }
+            wb[s][j] = *reinterpret_cast<const bf16x8*>(wl + (32 * j + r) * WP + 16 * s + 8 * hh);
     __syncthreads();                                              // the slabs reuse W's staging area
+    PHASE(2);
 
     f32x16 acc[TN][TK];
 #pragma unroll
@@ -113,26 +158,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
 
-    bf16x8 rg[LOADS_N], ry[LOADS_N], rx[LOADS_K], rxc[LOADS_K];
-    const long nchunks = (p.M + PMB - 1) / PMB;
-    auto fetch = [&](long chunk) {                               // raw loads only: nothing here waits on memory
-        const long mbase = chunk * PMB;
-#pragma unroll
-        for (int v = 0; v < LOADS_N; ++v) {
-            const long m = mbase + v * RPN + rown;
-            rg[v] = bf16x8{0}; ry[v] = bf16x8{0};
-            if (m < p.M && nok) {
-                rg[v] = *reinterpret_cast<const bf16x8*>(p.g + m * p.ldg + cn0);
-                ry[v] = *reinterpret_cast<const bf16x8*>(p.y + m * p.ldy + cn0);
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < LOADS_K; ++v) {
-            const long m = mbase + v * RPK + rowk;
-            rx[v] = bf16x8{0};
-            if (m < p.M && kok) rx[v] = *reinterpret_cast<const bf16x8*>(p.x + m * p.ldx + ck0);
-        }
-    };
     auto stash = [&](long chunk) {                               // BN-backward / prologue arithmetic, then LDS
         const long mbase = chunk * PMB;
         {
@@ -169,30 +194,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
 
-    const long stride = (long)gs.nbx * 4;
-    long chunk = (long)gs.bx * 4 + wave;
-    if (chunk < nchunks) fetch(chunk);
     for (; chunk < nchunks; chunk += stride) {
         stash(chunk);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (chunk + stride < nchunks) fetch(chunk + stride);
-        // operands of this chunk's store epilogue (old dx / residual-branch gradient): requested now, consumed after
-        // the MFMAs, so their latency is not exposed at the end of the trip
-        constexpr bool EPI_PREFETCH = TK == 1;                    // wider x tiles have no registers to spare
+        PHASE_ONCE(3);
+        // operands of this chunk's store epilogue (old dx / residual-branch gradient): requested now, BEFORE the next
+        // chunk's loads, and consumed after the MFMAs: their latency is not exposed at the end of the trip, and waiting
+        // for them does not wait for the prefetch behind them
+        constexpr bool EPI_PREFETCH = EPI && TK == 1;             // wider x tiles have no registers to spare
         bf16x8 repi_old[EPI_PREFETCH ? LOADS_K : 1], repi_add[EPI_PREFETCH ? LOADS_K : 1];
         if constexpr (EPI_PREFETCH) {
             const long mb = chunk * PMB;
 #pragma unroll
             for (int v = 0; v < LOADS_K; ++v) {
-                const long m = mb + v * RPK + rowk;
+                const long m = min(mb + v * RPK + rowk, p.M - 1);
                 repi_old[v] = bf16x8{0}; repi_add[v] = bf16x8{0};
-                if (m < p.M && kok) {
-                    if (p.accumulate) repi_old[v] = *reinterpret_cast<const bf16x8*>(p.dx + m * p.lddx + ck0);
-                    if (p.addend) repi_add[v] = *reinterpret_cast<const bf16x8*>(p.addend + m * p.lda + ck0);
-                }
+                if (p.accumulate) repi_old[v] = *reinterpret_cast<const bf16x8*>(p.dx + m * p.lddx + ckl);
+                if (p.addend) repi_add[v] = *reinterpret_cast<const bf16x8*>(p.addend + m * p.lda + ckl);
             }
         }
+        if (chunk + stride < nchunks) fetch(chunk + stride);
         // ---- weight gradient
 #pragma unroll
         for (int s = 0; s < PMB / 16; ++s) {
@@ -238,17 +260,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (m < p.M && kok) {
                 bf16x8 o = *reinterpret_cast<const bf16x8*>(sX + (v * RPK + rowk) * SK + cgk * 16);
                 bf16_t* dst = p.dx + m * p.lddx + ck0;
-                if (p.accumulate) {
-                    bf16x8 old;
-                    if constexpr (EPI_PREFETCH) old = repi_old[v]; else old = *reinterpret_cast<const bf16x8*>(dst);
+                if constexpr (EPI) {
+                    if (p.accumulate) {
+                        bf16x8 old;
+                        if constexpr (EPI_PREFETCH) old = repi_old[v]; else old = *reinterpret_cast<const bf16x8*>(dst);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)((float)o[j] + (float)old[j]);
-                }
-                if (p.addend) {
-                    bf16x8 ad;
-                    if constexpr (EPI_PREFETCH) ad = repi_add[v]; else ad = *reinterpret_cast<const bf16x8*>(p.addend + m * p.lda + ck0);
+                        for (int j = 0; j < 8; ++j) o[j] = (bf16_t)((float)o[j] + (float)old[j]);
+                    }
+                    if (p.addend) {
+                        bf16x8 ad;
+                        if constexpr (EPI_PREFETCH) ad = repi_add[v]; else ad = *reinterpret_cast<const bf16x8*>(p.addend + m * p.lda + ck0);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)((float)o[j] + (float)ad[j]);
+                        for (int j = 0; j < 8; ++j) o[j] = (bf16_t)((float)o[j] + (float)ad[j]);
+                    }
                 }
                 *reinterpret_cast<bf16x8*>(dst) = o;
                 if (want_xred) {
@@ -265,55 +289,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_wave_barrier();                          // sX is rewritten by the next stash
     }
 
-    // ---- fold the four waves' weight-gradient fragments, one slab per workgroup (conv_wgrad.hip layout)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(ldsb);
-    constexpr int ACC_FLOATS = TN * TK * 16 * 64;
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TK; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        float* q = red + ((i * TK + j) * 16 + e) * 64 + lane;
-                        *q = (w == 0 ? 0.f : *q) + acc[i][j][e];
-                    }
-        }
-        __syncthreads();
-    }
-    constexpr int SLABF = TN * TK * 1024 + TN * 32;
-    float* slab = p.ws + (long)blockIdx.x * SLABF;
-    if (wave == 0) {
-#pragma unroll
-        for (int e = 0; e < TN * TK * 16; ++e) slab[e * 64 + lane] = red[e * 64 + lane];
-        for (int i = lane; i < TN * 32; i += 64) slab[TN * TK * 1024 + i] = 0.f;     // no conv bias on this path
-    }
+    // ---- cross-wave fold (tr_lds.hpp): one slab per workgroup in the conv_wgrad.hip layout.  The BN(x) sums ride on
+    // the same two barriers: every 16-lane row of every wave parks its row_fold partials in a slot of its own, and one
+    // thread per channel adds the 16 slots in a fixed order - no same-address LDS atomics, no barriers of their own.
+    PHASE(4);
+    __syncthreads();                                              // the parked partials reuse the tile slabs and cst
+    PHASE(5);
+    float* part = reinterpret_cast<float*>(ldsb);
+    float* xs = part + fold_part_floats<TN, TK>();                // [4 waves][4 rows][2][TK*32]
+    fold_park<TN, TK>(part, acc, wave, lane);
     if (want_xred) {
-        __syncthreads();
-        float* xr = red;                                          // [2][TK*32]
-        for (int i = tid; i < 2 * TK * 32; i += 256) xr[i] = 0.f;
-        __syncthreads();
+        float* slot = xs + (wave * 4 + (lane >> 4)) * (2 * TK * 32);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float v0 = row_fold<VK>(s0[j]), v1 = row_fold<VK>(s1[j]);      // lanes with equal lane % VK share channels
-            if ((lane & 15) < VK) { atomicAdd(&xr[ck0 + j], v0); atomicAdd(&xr[TK * 32 + ck0 + j], v1); }
-        }
-        __syncthreads();
-        for (int i = tid; i < 2 * TK * 32; i += 256) {
-            const int which = i / (TK * 32), c = i - which * TK * 32;
-            if (c < p.K && xr[i] != 0.f)
-                atomicAdd(p.xred + (blockIdx.x & (ISA_STAT_R - 1)) * 2 * p.K + which * p.K + c, xr[i]);
+            if ((lane & 15) < VK) { slot[ck0 + j] = v0; slot[TK * 32 + ck0 + j] = v1; }
         }
     }
+    __syncthreads();
+    PHASE(6);
+    constexpr int SLABF = TN * TK * 1024 + TN * 32;
+    float* slab = p.ws + (long)blockIdx.x * SLABF;
+    fold_store<TN, TK>(part, slab, tid);
+    PHASE(7);
+    if (tid < TN * 32) slab[TN * TK * 1024 + tid] = 0.f;         // no conv bias on this path
+    if (want_xred && tid < 2 * TK * 32) {
+        float v = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < 16; ++sl) v += xs[sl * (2 * TK * 32) + tid];
+        const int which = tid / (TK * 32), c = tid - which * TK * 32;
+        if (c < p.K && v != 0.f)
+            atomicAdd(p.xred + (blockIdx.x & (ISA_STAT_R - 1)) * 2 * p.K + which * p.K + c, v);
+    }
+    PHASE(8);
+    PHASE_FLUSH(phase_buf);
 }
 
 template <int TN, int TK, int YACT, int XMODE>
 int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     constexpr size_t slab = (size_t)32 * (SN + SK) * 4 + 9 * 64 * 4;
-    constexpr size_t redb = ((size_t)TN * TK * 16 * 64 + TN * 32) * 4;
+    constexpr size_t redb = ((size_t)fold_part_floats<TN, TK>() + 16 * 2 * TK * 32) * 4;   // parked partials + BN(x) sum slots
     constexpr size_t lds = slab > redb ? slab : redb;
     const long nchunks = (p.M + 31) / 32;
     const long slabf = (long)TN * TK * 1024 + TN * 32;
@@ -325,7 +341,8 @@ int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* 
     if (gx > ws_cap) gx = ws_cap;
     gx = group_grid(gx, p.G);
     if (int rc = fin_standalone(xfin, p.K, xfin_groups, s)) return rc;      // every check has passed
-    hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE>), dim3((unsigned)gx), dim3(256), lds, s, p);
+    if (p.accumulate || p.addend) hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, true>), dim3((unsigned)gx), dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, false>), dim3((unsigned)gx), dim3(256), lds, s, p);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
     return wgrad_slab_reduce_launch(p.ws, p.dw, nullptr, (int)gx, TN, TK, p.N, p.K, 1, sa, s);
 }
@@ -343,6 +360,10 @@ int launch_tile(PwParams& p, int xmode, long ws_floats, isa_slab_arena* sa, cons
 }
 
 }  // namespace
+
+#ifdef ISA_PHASE_TRACE
+extern "C" int isa_phase_trace_pw(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(phase_buf), sizeof(phase_buf)) == hipSuccess ? ISA_OK : ISA_ELAUNCH; }
+#endif
 
 extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
                                        const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,

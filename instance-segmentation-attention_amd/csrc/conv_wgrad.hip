@@ -10,8 +10,9 @@
 //     lazy BN/ReLU6 prologue is applied in registers, once per element), then feeds TN x TK output
 //     tiles from conflict-free ds_read_b32 rows.  No __syncthreads in the main loop, the next
 //     chunk's global loads are issued before the current chunk's MFMAs.
-//   * at the end the four waves of a workgroup add their accumulators in LDS and ONE wave issues the
-//     float atomics: 4x fewer atomics on the (small, hot) dW addresses.
+//   * at the end the four waves of a workgroup add their accumulators in LDS and the workgroup writes ONE partial
+//     slab; wgrad_reduce_kernel / wgrad_fold_kernel add the slabs into dW.  (bf16 kernel: the four waves park their
+//     fragments side by side and all threads add and store them, fold_park / fold_store in tr_lds.hpp.)
 //   * blockIdx.x strides over chunks (split-M), blockIdx.y = (n-group, k-group) of <= 2x2 tiles,
 //     blockIdx.z = tap (3x3 dense / transposed-conv quadrant).
 // bf16 storage converts to fp32 while staging; exact-fp32 MFMA keeps weight gradients at fp32 accuracy
@@ -341,15 +342,21 @@ static int launch_reduce(const WgParams& p, int gx, int gy, int tn, int tk, hipS
 // bf16 storage: the same contraction on v_mfma_f32_32x32x16_bf16 (16x the fp32-MFMA rate, which
 // otherwise bounds this kernel: 2*M*N*K flops at 157 TF/s ~ the HBM time of the two operands).
 // Operands A[i=n][k=pixel 8h+j] / B[k=pixel 8h+j][j=k-channel] need 8 consecutive PIXELS of one
-// channel per lane: the tiles are staged row-major [pixel][channel] in LDS (coalesced 16-byte loads,
-// prologue applied in fp32 then rounded once, exactly like conv_gemm's forward operand) and fetched
+// channel per lane: the tiles are staged row-major [pixel][channel] in LDS (coalesced 16-byte loads that
+// carry no arithmetic; the prologue is applied in fp32 when the registers are stashed, then rounded once,
+// exactly like conv_gemm's forward operand) and fetched
 // with ds_read_b64_tr_b16, the hardware transpose read (lane (r,h) element j <- tile[8h+j][r];
 // verified by scripts/probes/tr_probe.hip).  Row stride is kept == 64 (mod 256) bytes so the four
 // 64-byte row pieces a half-wave touches land on disjoint banks.
 // ---------------------------------------------------------------------------------------------
+#ifdef ISA_PHASE_TRACE
+__device__ unsigned long long phase_buf[10];
+#endif
+
 template <int TN, int TK, int ACT>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
+    PHASE_DECL(); PHASE(0);
     constexpr int PMB = 32;                                   // pixels per wave-chunk = 2 MFMA k-steps
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     constexpr int SLAB = PMB * (SN + SK);
@@ -390,6 +397,58 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
     const int cn0 = n0 + cgn * 8, ck0 = k0 + cgk * 8;
     const bool has_aff = p.pro.scale || p.pro.shift;
     const bool has_pro = has_aff || p.pro.bscale || p.pro.act != ISA_ACT_NONE;
+    const bool nok = cn0 < p.N, kok = ck0 < p.cin;
+    const int cnl = nok ? cn0 : 0, ckl = kok ? ck0 : 0;       // clamped: a 16-byte piece that exists in every row
+    const bool xdiv = !plain || p.pro.bscale;
+
+    // global -> registers: raw 16-byte loads only, issued for EVERY lane at a clamped address, with no branch in front
+    // (the whole vector of a channel-tail group lies inside the row, see load8raw in common.hpp).  Nothing here waits on
+    // memory; what a lane must not use (pixels past M, channels past N / cin, 3x3 taps outside the image) is recorded
+    // in okd / okx and zeroed when the registers are stashed.
+    unsigned okd = 0, okx = 0;
+    int pbv[LOADS_K];                                         // image of each x vector (per-image multiplier only)
+#pragma unroll
+    for (int v = 0; v < LOADS_K; ++v) pbv[v] = 0;
+    auto fetch = [&](long chunk) {
+        const long mbase = chunk * PMB;
+        okd = 0; okx = 0;
+#pragma unroll
+        for (int v = 0; v < LOADS_N; ++v) {
+            const long m = mbase + v * RPN + rown;
+            if (m < p.M && nok) okd |= 1u << v;
+            long row = m < p.M ? m : p.M - 1;
+            if (p.out_mode == ISA_OUT_SHUFFLE2) {
+                const unsigned mu = (unsigned)row, q = mu / (unsigned)p.mw;
+                const int px = (int)(mu - q * (unsigned)p.mw);
+                const unsigned pb = q / (unsigned)p.mh; const int py = (int)(q - pb * (unsigned)p.mh);
+                row = ((long)pb * p.dh + 2 * py + (tap >> 1)) * p.dw_ + 2 * px + (tap & 1);
+            }
+            rd[v] = *reinterpret_cast<const bf16x8*>(din + row * p.ldd + cnl);
+        }
+#pragma unroll
+        for (int v = 0; v < LOADS_K; ++v) {
+            const long m = mbase + v * RPK + rowk;
+            long row = m < p.M ? m : p.M - 1;
+            bool ok = m < p.M && kok;
+            if (xdiv) {
+                const unsigned mu = (unsigned)row, q = mu / (unsigned)p.mw;
+                const int px = (int)(mu - q * (unsigned)p.mw);
+                const long pb = q / (unsigned)p.mh; const int py = (int)(q - (unsigned)pb * (unsigned)p.mh);
+                pbv[v] = (int)pb;
+                if (p.in_mode == ISA_IN_3X3) {
+                    const int sy = py + tap / 3 - 1, sx = px + tap % 3 - 1;
+                    ok = ok && sy >= 0 && sy < p.xh && sx >= 0 && sx < p.xw;
+                    row = (pb * p.xh + min(max(sy, 0), p.xh - 1)) * p.xw + min(max(sx, 0), p.xw - 1);
+                }
+            }
+            if (ok) okx |= 1u << v;
+            rx[v] = *reinterpret_cast<const bf16x8*>(xin + row * p.ldx + ckl);
+        }
+    };
+
+    const long stride = (long)gs.nbx * 4;
+    long chunk = (long)gs.bx * 4 + wave;
+    if (chunk < nchunks) fetch(chunk);                        // the first chunk is in flight while the constants load
     float psc[8], psh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -397,91 +456,61 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
         psc[j] = p.pro.scale ? p.pro.scale[c] : 1.f;
         psh[j] = p.pro.shift ? p.pro.shift[c] : 0.f;
     }
+    float bsr[8];                                             // the per-image multiplier row of image bsi
+    int bsi = -1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bsr[j] = 1.f;
 
-    auto fetch = [&](long chunk) {
-        const long mbase = chunk * PMB;
+    // registers -> wave-private LDS slab; the lazy prologue (fp32, rounded once) and all zeroing happen here, after
+    // the wait, so that the loads of fetch() stay in flight while the previous chunk's MFMAs run
+    auto stash = [&]() {
 #pragma unroll
         for (int v = 0; v < LOADS_N; ++v) {
-            const long m = mbase + v * RPN + rown;
-            rd[v] = bf16x8{0};
-            if (m < p.M && cn0 < p.N) {
-                long row = m;
-                if (p.out_mode == ISA_OUT_SHUFFLE2) {
-                    const unsigned mu = (unsigned)m, q = mu / (unsigned)p.mw;
-                    const int px = (int)(mu - q * (unsigned)p.mw);
-                    const unsigned pb = q / (unsigned)p.mh; const int py = (int)(q - pb * (unsigned)p.mh);
-                    row = ((long)pb * p.dh + 2 * py + (tap >> 1)) * p.dw_ + 2 * px + (tap & 1);
-                }
-                const bf16_t* src = din + row * p.ldd + cn0;
-                if (cn0 + 8 <= p.N) rd[v] = *reinterpret_cast<const bf16x8*>(src);
-                else {
+            bf16x8 o = rd[v];
+            if (!((okd >> v) & 1)) o = bf16x8{0};
+            else if (cn0 + 8 > p.N) {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) rd[v][j] = (cn0 + j < p.N) ? src[j] : (bf16_t)0.f;
-                }
+                for (int j = 0; j < 8; ++j) if (cn0 + j >= p.N) o[j] = (bf16_t)0.f;
             }
+            *reinterpret_cast<bf16x8*>(sD + (v * RPN + rown) * SN + cgn * 16) = o;
         }
 #pragma unroll
         for (int v = 0; v < LOADS_K; ++v) {
-            const long m = mbase + v * RPK + rowk;
-            rx[v] = bf16x8{0};
-            if (m < p.M && ck0 < p.cin) {
-                long row = m; bool ok = true; long pb = 0;
-                if (!plain || p.pro.bscale) {
-                    const unsigned mu = (unsigned)m, q = mu / (unsigned)p.mw;
-                    const int px = (int)(mu - q * (unsigned)p.mw);
-                    pb = q / (unsigned)p.mh; const int py = (int)(q - (unsigned)pb * (unsigned)p.mh);
-                    if (p.in_mode == ISA_IN_3X3) {
-                        const int sy = py + tap / 3 - 1, sx = px + tap % 3 - 1;
-                        ok = sy >= 0 && sy < p.xh && sx >= 0 && sx < p.xw;
-                        row = (pb * p.xh + sy) * p.xw + sx;
+            bf16x8 raw = rx[v];
+            const bool ok = (okx >> v) & 1;
+            if (has_pro) {
+                // wave-uniform tests hoisted out of the element loop (the per-image multiplier and the channel
+                // tail were a branch and a select per element)
+                float z[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) z[j] = act_t<ACT>(fmaf((float)raw[j], psc[j], psh[j]), p.pro.act);
+                if (p.pro.bscale) {
+                    if (ok && pbv[v] != bsi) {                // one row fetch per image change
+                        bsi = pbv[v];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bsr[j] = p.pro.bscale[(long)bsi * p.cin + min(ck0 + j, p.cin - 1)];
                     }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) z[j] *= bsr[j];
                 }
-                if (ok) {
-                    const bf16_t* src = xin + row * p.ldx + ck0;
-                    bf16x8 raw;
-                    if (ck0 + 8 <= p.cin) raw = *reinterpret_cast<const bf16x8*>(src);
-                    else {
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) raw[j] = (ck0 + j < p.cin) ? src[j] : (bf16_t)0.f;
-                    }
-                    if (has_pro) {
-                        // wave-uniform tests hoisted out of the element loop (the per-image multiplier and the channel
-                        // tail were a branch and a select per element)
-                        float z[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) z[j] = act_t<ACT>(fmaf((float)raw[j], psc[j], psh[j]), p.pro.act);
-                        if (p.pro.bscale) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) z[j] *= p.pro.bscale[pb * p.cin + min(ck0 + j, p.cin - 1)];
-                        }
-                        if (ck0 + 8 > p.cin) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) if (ck0 + j >= p.cin) z[j] = 0.f;
-                        }
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) raw[j] = (bf16_t)z[j];
-                    }
-                    rx[v] = raw;
-                }
+                for (int j = 0; j < 8; ++j) raw[j] = (bf16_t)z[j];
             }
+            if (!ok) raw = bf16x8{0};
+            else if (ck0 + 8 > p.cin) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) if (ck0 + j >= p.cin) raw[j] = (bf16_t)0.f;
+            }
+            *reinterpret_cast<bf16x8*>(sX + (v * RPK + rowk) * SK + cgk * 16) = raw;
         }
     };
-    auto stash = [&]() {
-#pragma unroll
-        for (int v = 0; v < LOADS_N; ++v)
-            *reinterpret_cast<bf16x8*>(sD + (v * RPN + rown) * SN + cgn * 16) = rd[v];
-#pragma unroll
-        for (int v = 0; v < LOADS_K; ++v)
-            *reinterpret_cast<bf16x8*>(sX + (v * RPK + rowk) * SK + cgk * 16) = rx[v];
-    };
 
-    const long stride = (long)gs.nbx * 4;
-    long chunk = (long)gs.bx * 4 + wave;
-    if (chunk < nchunks) fetch(chunk);
+    PHASE(1);
     for (; chunk < nchunks; chunk += stride) {
         stash();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        PHASE_ONCE(3);
         if (chunk + stride < nchunks) fetch(chunk + stride);
 #pragma unroll
         for (int s = 0; s < PMB / 16; ++s) {
@@ -504,44 +533,35 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
         __builtin_amdgcn_wave_barrier();
     }
 
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(ldsb);
-    constexpr int ACC_FLOATS = TN * TK * 16 * 64;
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
+    // ---- cross-wave fold (tr_lds.hpp): one partial slab per workgroup, raw fragment layout; wgrad_reduce_kernel sums
+    // the gridDim.x slabs of each (group, tap) in a fixed order and adds into dW: bitwise-reproducible weight gradients
+    PHASE(4);
+    __syncthreads();                                          // the parked partials reuse the tile slabs
+    PHASE(5);
+    float* part = reinterpret_cast<float*>(ldsb);
+    float* dbp = part + fold_part_floats<TN, TK>();           // [4 waves][TN*32] column sums of dy
+    fold_park<TN, TK>(part, acc, wave, lane);
 #pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TK; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        float* q = red + ((i * TK + j) * 16 + e) * 64 + lane;
-                        *q = (w == 0 ? 0.f : *q) + acc[i][j][e];
-                    }
-#pragma unroll
-            for (int i = 0; i < TN; ++i) {
-                const float sv = dbs[i] + __shfl_xor(dbs[i], 32, 64);
-                if (hh == 0) { float* q = red + ACC_FLOATS + i * 32 + r; *q = (w == 0 ? 0.f : *q) + sv; }
-            }
-        }
-        __syncthreads();
+    for (int i = 0; i < TN; ++i) {
+        const float sv = dbs[i] + __shfl_xor(dbs[i], 32, 64);
+        if (hh == 0) dbp[wave * TN * 32 + i * 32 + r] = sv;
     }
-    if (wave != 0) return;
-    // one partial slab per workgroup, raw fragment layout (256-byte coalesced stores); wgrad_reduce_kernel
-    // sums the gridDim.x slabs of each (group, tap) in a fixed order and adds into dW: no atomics, so no
-    // same-line serialisation at the memory side, and bitwise-reproducible weight gradients.
+    __syncthreads();
+    PHASE(6);
     constexpr int SLABF = TN * TK * 1024 + TN * 32;
     float* slab = p.ws + (((long)blockIdx.x * gridDim.y + blockIdx.y) * gridDim.z + blockIdx.z) * SLABF;
-#pragma unroll
-    for (int e = 0; e < TN * TK * 16; ++e) slab[e * 64 + lane] = red[e * 64 + lane];
-    for (int i = lane; i < TN * 32; i += 64) slab[TN * TK * 1024 + i] = red[ACC_FLOATS + i];
+    fold_store<TN, TK>(part, slab, tid);
+    if (tid < TN * 32)
+        slab[TN * TK * 1024 + tid] = 0.f + dbp[tid] + dbp[TN * 32 + tid] + dbp[2 * TN * 32 + tid] + dbp[3 * TN * 32 + tid];
+    PHASE(7);
+    PHASE_FLUSH(phase_buf);
 }
 
 template <int TN, int TK>
 int launch_wg_bf16(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     const size_t slab = (size_t)32 * (SN + SK) * 4;
-    const size_t redb = ((size_t)TN * TK * 16 * 64 + TN * 32) * 4;
+    const size_t redb = ((size_t)fold_part_floats<TN, TK>() + 4 * TN * 32) * 4;     // four parked partials + dy column sums
     const size_t lds = slab > redb ? slab : redb;
     const int gy = groups_n * p.groups_k;
     const long nchunks = (p.M + 31) / 32;
@@ -618,6 +638,10 @@ int dispatch_wg(WgParams& p, const isa_pro* fin, hipStream_t s) {
 }
 
 }  // namespace
+
+#ifdef ISA_PHASE_TRACE
+extern "C" int isa_phase_trace_wg(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(phase_buf), sizeof(phase_buf)) == hipSuccess ? ISA_OK : ISA_ELAUNCH; }
+#endif
 
 extern "C" int isa_conv_wgrad(const isa_tensor* x, const isa_pro* pro, const isa_tensor* dy,
                               float* dw, float* dbias, int32_t in_mode, int32_t out_mode,
