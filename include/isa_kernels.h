@@ -572,6 +572,53 @@ int isa_disc_assemble(const float* hslab, const double* partial, const float* mu
 int isa_disc_grad(const isa_tensor* emb, const uint8_t* labels, int32_t k, const int32_t* n_objects, const float* mu,
                   const float* gconst, const float* coef, const float* cfg, int32_t norm, const isa_tensor* demb,
                   int32_t accumulate, void* stream);
+/* ---- clustering the instance embedding into instances (the reference's Prediction.cluster, prediction.py:52-85, runs sklearn
+ * KMeans on the host and fills the map pixel by pixel; here both methods run on the device, per image) -------------------
+ * emb x: as for isa_disc_* (NHWC bf16 | fp32, 1 <= C <= 32, ld >= C and a multiple of 8, 16-byte aligned, groups 1,
+ * B <= 65535, L = H*W < 2^31); channels C..ld-1 of a row are never read as data.  fg: uint8 [B, L], non-zero = foreground.
+ * d(p, c) = sum_j (x_p[j] - c[j])^2, always in this direct form: the difference first, then one fp32 fmaf chain over the
+ * channels in order; never |x|^2 - 2 x.c + |c|^2.  NaN embeddings are not supported (every comparison with a NaN distance
+ * is false: such a pixel joins no ball and goes to centre 0).
+ * Outputs of both entries: labels uint8 [B, L] (0 = background, 1..n = instances), n_objects int32 [B], centres float
+ * [B][32][32] (row i = centre of label i + 1, zero past n_objects[b] and past C), sizes int32 [B][32], moved int32 [B].
+ * isa_cluster_meanshift: the greedy flat-kernel mean-shift.  free = foreground pixels without label that are not noise;
+ *   while k < max_objects and free is not empty and fewer than max_rounds rounds have run: s = the smallest index in free,
+ *   c = x_s; `shifts` times c = mean of
+ *   {p in free: d(p, c) <= bandwidth^2} (an empty set keeps c); S = that set for the last c, united with {s}; |S| >=
+ *   min_pixels: k += 1, S takes label k, centre[k] = c, sizes[k] = |S|; else S is noise.  With assign_rest != 0 and k > 0
+ *   every foreground pixel still without label (noise, or left when max_objects was reached) takes the label of its nearest
+ *   centre (ties: the lowest label; sizes stay |S|); else it keeps 0.  n_objects[b] = k, moved[b] = 0.
+ *   bandwidth > 0, 0 <= shifts <= ISA_CLUSTER_MAX_SHIFTS, 1 <= max_objects <= 32, max_objects <= max_rounds <=
+ *   ISA_CLUSTER_MAX_ROUNDS, min_pixels >= 1.  The round budget is what keeps the launch count free of the data: a round
+ *   ends with an object or with a ball refused as noise, and BOTH use up one of the max_rounds rounds.  With min_pixels == 1
+ *   no ball is refused, rounds == k, and max_rounds == max_objects never binds; with min_pixels > 1 every refused ball
+ *   before the last object needs a round of its own, and what the budget leaves unvisited is treated like what max_objects
+ *   leaves (assign_rest, or 0).  1 + max_rounds (shifts + 1) + 1 launches whatever the data holds.
+ * isa_cluster_kmeans: K_b = min(n_objects_in[b], foreground pixels, kmax), 1 <= kmax <= 32.  init == NULL: deterministic
+ *   maximin - centre 0 is the foreground pixel of smallest index, centre j the foreground pixel farthest from its nearest
+ *   chosen centre (ties: the smallest index) - in kmax launches; else init float [B][32][32] holds the first centres (rows
+ *   past K_b and channels past C are ignored).  Then `iters` (0..ISA_CLUSTER_MAX_ITERS) Lloyd iterations over the foreground:
+ *   every pixel goes to its nearest centre (ties: the lowest index), every centre becomes the mean of its pixels, an empty
+ *   cluster keeps its centre; a last assignment makes the labels.  centres = the centres of that assignment, sizes = its
+ *   counts, moved[b] = pixels whose label differs from the assignment before (0 when iters == 0), n_objects[b] = K_b.
+ *   1 + (init ? 0 : kmax) + iters + 2 launches.
+ * scratch: ISA_CLUSTER_SCRATCH_BYTES(B, L) bytes, 16-byte aligned, never has to be cleared: per-chunk slabs (ISA_DISC_CHUNKS
+ * workgroups share an image), the per-image loop state and the moving centres, all double-buffered by launch parity.  Every
+ * workgroup folds the slabs of the pass before in chunk order itself; there are no float atomics, no waits between
+ * workgroups and nothing is read back, so a call is bit-reproducible and can be captured into a hipGraph on one stream.
+ * Both entries check every argument before they launch or write anything (ISA_EINVAL / ISA_EALIGN / ISA_EDTYPE). */
+#define ISA_CLUSTER_MAX_SHIFTS 8
+#define ISA_CLUSTER_MAX_ITERS 64
+#define ISA_CLUSTER_MAX_ROUNDS 256
+#define ISA_CLUSTER_STATE_INTS 16
+#define ISA_CLUSTER_CSLAB_STRIDE 36
+#define ISA_CLUSTER_SCRATCH_BYTES(n, L) ((int64_t)(n) * (8320 + ISA_DISC_CHUNKS(L) * 8488))
+int isa_cluster_meanshift(const isa_tensor* emb, const uint8_t* fg, float bandwidth, int32_t shifts, int32_t max_objects,
+                          int32_t max_rounds, int32_t min_pixels, int32_t assign_rest, uint8_t* labels, int32_t* n_objects,
+                          float* centres, int32_t* sizes, int32_t* moved, void* scratch, void* stream);
+int isa_cluster_kmeans(const isa_tensor* emb, const uint8_t* fg, const int32_t* n_objects_in, const float* init, int32_t kmax,
+                       int32_t iters, uint8_t* labels, int32_t* n_objects, float* centres, int32_t* sizes, int32_t* moved,
+                       void* scratch, void* stream);
 /* reference-format targets: int64 one-hot [n,k,h,w] -> uint8 labels [n,h,w] and / or the fp32 argmax(1) map [n, h*w]
  * (sem_seg_argmax, reseg.py:118); the first maximum wins, as in torch.argmax.  Either output may be NULL, not both. */
 int isa_labels_from_onehot(const int64_t* onehot, int32_t n, int32_t k, int64_t hw, uint8_t* labels, float* argmax_map,

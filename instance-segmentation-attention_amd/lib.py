@@ -47,6 +47,15 @@ def disc_chunks(L):
     return min((L + 1023) // 1024, ROW_CHUNKS)
 
 
+CLUSTER_MAX_SHIFTS, CLUSTER_MAX_ITERS, CLUSTER_STATE_INTS, CLUSTER_CSLAB_STRIDE = 8, 64, 16, 36      # ISA_CLUSTER_*
+CLUSTER_MAX_ROUNDS = 256
+
+
+def cluster_scratch_bytes(n, L):
+    """ISA_CLUSTER_SCRATCH_BYTES: slabs, loop state and moving centres of isa_cluster_meanshift / isa_cluster_kmeans."""
+    return n * (8320 + disc_chunks(L) * 8488)
+
+
 PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SATURATION, PHOTO_HUE = 0, 1, 2, 3
 
 _ERR = {-1: "ISA_EINVAL", -2: "ISA_EALIGN", -3: "ISA_EDTYPE", -4: "ISA_ELAUNCH", -5: "ISA_ENOMEM"}
@@ -177,6 +186,9 @@ SIGNATURES = {
     "isa_disc_hinge": [P_T, VP, I32, VP, VP, VP, I32, VP, VP, VP],
     "isa_disc_assemble": [VP, VP, VP, VP, VP, VP, VP, I32, I32, I64, VP, VP, VP, VP, VP],
     "isa_disc_grad": [P_T, VP, I32, VP, VP, VP, VP, VP, I32, P_T, I32, VP],
+    # clustering the instance embedding (ReSeg.cluster_embedding, ReSeg.segment_embedding)
+    "isa_cluster_meanshift": [P_T, VP, F, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP, VP],
+    "isa_cluster_kmeans": [P_T, VP, VP, VP, I32, I32, VP, VP, VP, VP, VP, VP, VP],
     "isa_ins_softmax_bwd": [VP, VP, VP, VP, VP, I32, I32, I64, VP, I32, VP],
     "isa_maskbn_bwd": [P_T, VP, VP, VP, VP, F, VP, I32, VP, VP, VP, VP, P_T, I32, VP],
     "isa_sp_bwd": [P_T, P_T, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, F, I32, VP, P_T, I32,

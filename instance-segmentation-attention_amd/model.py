@@ -112,13 +112,28 @@ class Model(object):
             row['Disc Cost'] = out['disc'][0].clone()
         return row
 
-    def __score_batch(self, batch, max_objects, check, clean=None):
+    def __instances(self, images, max_objects, method, bandwidth, n_objects):
+        """(sem_argmax, labels, n_objects) of one batch by `method`: 'attention' (ReSeg.segment), or 'meanshift' / 'kmeans'
+        on the instance embedding (ReSeg.segment_embedding; at most 32 instances)."""
+        m = self.model
+        if method == 'attention':
+            _, sem_arg, labels, count = m.segment(images.contiguous(), max_objects)
+        elif method in ('meanshift', 'kmeans'):
+            if method == 'kmeans' and n_objects is None:
+                raise ValueError("method 'kmeans' needs n_objects")
+            _, sem_arg, labels, count = m.segment_embedding(images.contiguous(), method=method, bandwidth=bandwidth,
+                                                            max_objects=min(int(max_objects), 32), n_objects=n_objects)
+        else:
+            raise ValueError("method must be 'attention', 'meanshift' or 'kmeans', got %r" % (method,))
+        return sem_arg, labels, count
+
+    def __score_batch(self, batch, max_objects, check, clean=None, method='attention', bandwidth=None):
         """segment() + score_instances() of one loader batch: the device tensor [B,8], and the number of pixels whose
         label the histograms do not hold (a device scalar: the callers read it with their one copy and raise).
         clean: keyword arguments of ReSeg.clean_instances, applied to the labels before they are scored."""
         images, sem, ins, n_objects = batch
         m = self.model
-        _, sem_arg, labels, count = m.segment(images.contiguous(), max_objects)
+        sem_arg, labels, count = self.__instances(images, max_objects, method, bandwidth, n_objects)
         if clean is not None:
             labels, count, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         out = m.score_instances(labels, count, ins, n_objects, sem_arg, sem, max_objects=max_objects, check=check)
@@ -291,14 +306,18 @@ class Model(object):
             return None
         return {'keep': keep or 'all', 'connectivity': connectivity, 'min_area': int(min_area)}
 
-    def predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8):
+    def predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
+                          bandwidth=None, n_objects=None):
         """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
         instance prediction is dead at HEAD).  images: [b,21,h,w] float or raw uint8 RGB [b,h,w,3].  Returns host tensors
         (fg_prob [b,h,w] = softmax probability of the foreground class, labels uint8 [b,h,w] with 0 = no instance,
         n_objects int32 [b]); at most max_objects (default: the constructor's max_n_objects) instances per image.
         keep='largest' | 'all' and / or min_area > 1 clean the label map on the device before it comes down
         (ReSeg.clean_instances: the largest connected piece of every instance, or every piece as an instance of its own;
-        pieces under min_area pixels dropped; connectivity 4 or 8).  With the defaults none of that runs."""
+        pieces under min_area pixels dropped; connectivity 4 or 8).  With the defaults none of that runs.
+        method='meanshift' | 'kmeans' takes the instances from clusters of the instance embedding instead of the attention
+        decoder (ReSeg.segment_embedding, at most 32 per image): mean-shift of radius bandwidth (default 1.5 = delta_dist),
+        or k-means with the object counts n_objects [b]."""
         assert len(images.size()) == 4
         m = self.model
         if not m.use_instance_seg:
@@ -306,7 +325,7 @@ class Model(object):
         clean = self.__clean_arguments(min_area, keep, connectivity)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
-        _, _, labels, n_objects = m.segment(images.contiguous(), max_objects)
+        _, labels, n_objects = self.__instances(images, max_objects, method, bandwidth, n_objects)
         if clean is not None:
             labels, n_objects, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
@@ -330,7 +349,8 @@ class Model(object):
             fg_prob = prob[:, 1] if prob.shape[1] == 2 else 1.0 - prob[:, 0]
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
 
-    def evaluate(self, loader, max_objects=None, *, min_area=0, keep=None, connectivity=8):
+    def evaluate(self, loader, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
+                 bandwidth=None):
         """Scores of ground-truth-free instance inference over a loader of (images, sem, ins, n_objects) batches, either
         target form: every batch is segmented (ReSeg.segment, at most max_objects instances per image; default: the
         constructor's max_n_objects) and scored on the device (ReSeg.score_instances); one device-to-host copy at the end.
@@ -339,6 +359,8 @@ class Model(object):
         averages the images it scored), n_skipped counts the images whose SBD is NaN (neither map holds an object).
         min_area / keep / connectivity: the clean-up of predict_instances, applied to every label map before it is scored
         (with the defaults none of it runs).
+        method='meanshift' | 'kmeans': the instances come from clusters of the instance embedding (predict_instances);
+        'kmeans' is given every batch's ground-truth object counts - the reference's protocol, a count supplied.
         It scores what the loader yields on THIS rank; reducing over ranks is left to the caller."""
         m = self.model
         if not m.use_instance_seg:
@@ -346,7 +368,8 @@ class Model(object):
         clean = self.__clean_arguments(min_area, keep, connectivity)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
-        rows = [self.__score_batch(b, max_objects, check=False, clean=clean) for b in loader]
+        rows = [self.__score_batch(b, max_objects, check=False, clean=clean, method=method, bandwidth=bandwidth)
+                for b in loader]
         if not rows:
             nan = float('nan')
             return {'SBD': nan, '|DiC|': nan, 'FG Dice': nan, 'n_images': 0, 'n_skipped': 0,

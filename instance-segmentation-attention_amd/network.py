@@ -375,6 +375,35 @@ class Network:
         grad.keep = (labels, n_obj, cfg)
         return scal, mu, grad
 
+    def cluster(self, emb: Act, fg: torch.Tensor, method, *, bandwidth=1.5, shifts=3, max_objects=32, max_rounds=None,
+                min_pixels=1, assign_rest=True, refine=0, n_objects=None, iters=10, init=None):
+        """Clusters the embedding `emb` over the foreground fg (uint8 [n, h*w], non-zero = foreground) per image:
+        isa_cluster_meanshift, or isa_cluster_kmeans from the counts n_objects (int32 [n]) and init (None: farthest-point, or
+        float [n,32,32]).  max_rounds (default max_objects): the mean-shift's round budget, refused balls included.
+        refine > 0 runs that many Lloyd iterations from the mean-shift's centres over the whole foreground.  Returns (labels uint8 [n, h*w], n_objects int32 [n], centres float [n,32,32], sizes int32 [n,32], moved
+        int32 [n]); everything stays on the device and nothing is read back."""
+        E = self.E
+        dev = emb.buf.device
+        n, hw = emb.n, emb.h * emb.w
+        labels = torch.empty((n, hw), dtype=torch.uint8, device=dev)
+        n_out, moved = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        centres = torch.empty((n, 32, 32), dtype=torch.float32, device=dev)
+        sizes = torch.empty((n, 32), dtype=torch.int32, device=dev)
+        scratch = torch.empty((L.cluster_scratch_bytes(n, hw),), dtype=torch.uint8, device=dev)
+        outs = (L.ptr(labels), L.ptr(n_out), L.ptr(centres), L.ptr(sizes), L.ptr(moved), L.ptr(scratch), E.st())
+        if method == 'meanshift':
+            rounds = int(max_objects if max_rounds is None else max_rounds)
+            L.check(E.lib.isa_cluster_meanshift(emb.d(), L.ptr(fg), float(bandwidth), int(shifts), int(max_objects), rounds,
+                                                int(min_pixels), int(bool(assign_rest)), *outs), "isa_cluster_meanshift")
+            if refine > 0:
+                n_in, init = n_out.clone(), centres.clone()
+                L.check(E.lib.isa_cluster_kmeans(emb.d(), L.ptr(fg), L.ptr(n_in), L.ptr(init), 32, int(refine), *outs),
+                        "isa_cluster_kmeans")
+        else:
+            L.check(E.lib.isa_cluster_kmeans(emb.d(), L.ptr(fg), L.ptr(n_objects), L.ptr(init), int(max_objects), int(iters),
+                                             *outs), "isa_cluster_kmeans")
+        return labels, n_out, centres, sizes, moved
+
     def onehot_map(self, sem_onehot: torch.Tensor) -> torch.Tensor:
         """int64 one-hot [n,K,h,w] -> fp32 argmax(1) map [n, h*w] (sem_seg_argmax of reseg.py:118, on the device)."""
         E = self.E

@@ -226,21 +226,10 @@ class ReSeg(nn.Module):
         max_objects = int(max_objects)
         if not 1 <= max_objects <= 255:
             raise ValueError("max_objects must be in 1..255 (labels are uint8), got %d" % max_objects)
-        E, net = self.engine, self.net
-        if x.dtype == torch.uint8:
-            assert x.dim() == 4 and x.shape[3] == 3, "uint8 input must be RGB [B,H,W,3]"
-            B, H, W = x.shape[0], x.shape[1], x.shape[2]
-        else:
-            assert x.dim() == 4 and x.shape[1] == 21, "expects [B,21,H,W] (ImageEx tensor, utils.py:109)"
-            B, H, W = x.shape[0], x.shape[2], x.shape[3]
-        assert H % 16 == 0 and W % 16 == 0
+        net = self.net
         dev = self.store.device
         with torch.no_grad():
-            E.begin(bn_train=False, record=False, key=("segment", tuple(x.shape), x.dtype))
-            if getattr(self, "_weights_dirty", True) and E.packer.entries:
-                E.packer.pack()
-            self._weights_dirty = False
-            x_dec, feats = net.unet(net.input_view(x))
+            x_dec, feats, B, H, W = self._backbone(x, "segment")
             sem = net.sem_head(x_dec)
             self._last_sem = sem
             sem_out = net.to_nchw(sem)
@@ -401,6 +390,136 @@ class ReSeg(nn.Module):
                 gfn(g, 0)
                 out["grad"] = g if as_act else g.buf[..., :a.c].permute(0, 3, 1, 2)
             return out
+
+    # ------------------------------------------------------------------ clustering the instance embedding into instances
+    def _backbone(self, x, key):
+        """Eval-mode backbone on `x` (either input form of forward): (x_dec, feats, B, H, W)."""
+        assert not self.training, "eval mode only (running BatchNorm statistics)"
+        if not self.use_instance_seg:
+            raise RuntimeError("the instance embedding needs a model built with use_instance_seg=True")
+        if x.dtype == torch.uint8:
+            assert x.dim() == 4 and x.shape[3] == 3, "uint8 input must be RGB [B,H,W,3]"
+            B, H, W = x.shape[0], x.shape[1], x.shape[2]
+        else:
+            assert x.dim() == 4 and x.shape[1] == 21, "expects [B,21,H,W] (ImageEx tensor, utils.py:109)"
+            B, H, W = x.shape[0], x.shape[2], x.shape[3]
+        assert H % 16 == 0 and W % 16 == 0
+        E, net = self.engine, self.net
+        E.begin(bn_train=False, record=False, key=(key, tuple(x.shape), x.dtype))
+        if getattr(self, "_weights_dirty", True) and E.packer.entries:
+            E.packer.pack()
+        self._weights_dirty = False
+        x_dec, feats = net.unet(net.input_view(x))
+        return x_dec, feats, B, H, W
+
+    def embedding(self, x):
+        """The instance embedding x_enc float32 [B,24,H,W] of images `x` (either input form of forward) from the eval-mode
+        network: backbone, then ins_seg_output_1 / ins_seg_output_2 (reseg.py:78-102) - what the discriminative loss is
+        trained on and what cluster_embedding clusters.  Needs no ground truth."""
+        with torch.no_grad():
+            x_dec, _, _, _, _ = self._backbone(x, "embedding")
+            return self.net.to_nchw(self.head.stems(x_dec))
+
+    def cluster_embedding(self, emb, fg, *, method='meanshift', bandwidth=None, delta_var=0.5, delta_dist=1.5, shifts=3,
+                          max_objects=32, min_pixels=1, assign_rest=True, refine=0, n_objects=None, iters=10,
+                          init='farthest', max_rounds=None):
+        """Clusters an instance embedding into instances, per image, on the device (isa_cluster_*).
+        emb: float [B,C,H,W] (fp32 or bf16, C <= 32) or an engine Act; fg: [B,H,W] or [B,H*W] of any dtype, non-zero =
+        foreground.  Distances are squared Euclidean, evaluated as sum_j (x[j] - c[j])^2 in fp32.
+        method 'meanshift' (no object count needed): greedy flat-kernel mean-shift.  The first free foreground pixel seeds a
+        centre, `shifts` (0..8) times the centre moves to the mean of the free pixels within `bandwidth`, those pixels become
+        an instance if they are at least min_pixels (else noise), until nothing is free or max_objects (1..32) instances
+        exist; with assign_rest what is left takes the label of its nearest centre.  The launch sequence is fixed, so the
+        loop also ends after max_rounds rounds (default max_objects, at most 256), and a ball refused as noise uses up a
+        round like an object does: with min_pixels = 1 nothing is refused and the budget never binds; with min_pixels > 1
+        pass max_rounds = max_objects + the refused balls to allow for.  bandwidth=None: delta_dist, the middle
+        of the admissible interval [2 delta_var, 2 delta_dist - 2 delta_var) of an embedding at zero var and dist loss.
+        refine=r then runs r Lloyd iterations from the centres found, over the whole foreground.
+        method 'kmeans': n_objects [B] clusters per image (at most the foreground pixels and max_objects), `iters` (0..64)
+        Lloyd iterations from init='farthest' (deterministic maximin from the first foreground pixel) or a tensor [B,K,C].
+        Returns a dict of device tensors: labels uint8 [B,H,W] (0 background, 1..n in the order of the centres), n_objects
+        int32 [B], centres float32 [B,32,C], sizes int32 [B,32], moved int32 [B] (k-means: pixels whose label changed in the
+        last iteration).  Bit-reproducible; nothing is read back: the call does not synchronise and can be captured."""
+        from .engine import Act, rup
+        if method not in ('meanshift', 'kmeans'):
+            raise ValueError("method must be 'meanshift' or 'kmeans', got %r" % (method,))
+        max_objects, shifts, iters, refine, min_pixels = int(max_objects), int(shifts), int(iters), int(refine), int(min_pixels)
+        if not 1 <= max_objects <= L.DISC_MAX_K:
+            raise ValueError("max_objects must be in 1..32, got %d" % max_objects)
+        if not 0 <= shifts <= L.CLUSTER_MAX_SHIFTS:
+            raise ValueError("shifts must be in 0..8, got %d" % shifts)
+        if not 0 <= iters <= L.CLUSTER_MAX_ITERS or not 0 <= refine <= L.CLUSTER_MAX_ITERS:
+            raise ValueError("iters and refine must be in 0..64, got %d and %d" % (iters, refine))
+        if min_pixels < 1:
+            raise ValueError("min_pixels must be at least 1, got %d" % min_pixels)
+        max_rounds = max_objects if max_rounds is None else int(max_rounds)
+        if not max_objects <= max_rounds <= L.CLUSTER_MAX_ROUNDS:
+            raise ValueError("max_rounds must be in max_objects..256, got %d" % max_rounds)
+        if delta_var < 0 or delta_dist < 0:
+            raise ValueError("delta_var and delta_dist must not be negative")
+        bandwidth = float(delta_dist if bandwidth is None else bandwidth)
+        if not (bandwidth > 0.0 and bandwidth != float("inf")):
+            raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
+        dev = self.store.device
+        with torch.no_grad():
+            if isinstance(emb, Act):
+                a = emb
+            else:
+                t = emb.to(dev)
+                if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError("emb: fp32 or bf16 [B,C,H,W] or an engine Act, got %s %s" % (t.dtype, tuple(t.shape)))
+                B, C, H, W = t.shape
+                buf = torch.zeros((B, H, W, rup(C, 8)), dtype=t.dtype, device=dev)
+                buf[..., :C].copy_(t.permute(0, 2, 3, 1))
+                a = Act(buf, 0, C)
+            if not 1 <= a.c <= 32:
+                raise ValueError("emb: 1..32 channels, got %d" % a.c)
+            f = fg.to(dev)
+            if f.dtype != torch.uint8:
+                f = (f != 0).to(torch.uint8)
+            f = f.reshape(a.n, -1).contiguous()
+            assert f.shape[1] == a.h * a.w, "fg and emb differ in size"
+            n_in = c0 = None
+            if method == 'kmeans':
+                if n_objects is None:
+                    raise ValueError("method 'kmeans' needs n_objects [B]")
+                n_in = n_objects.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+                assert n_in.numel() == a.n
+                if not isinstance(init, str):
+                    ini = init.to(device=dev, dtype=torch.float32)
+                    if ini.dim() != 3 or ini.shape[0] != a.n or not 1 <= ini.shape[1] <= 32 or ini.shape[2] != a.c:
+                        raise ValueError("init: 'farthest' or a tensor [B,K,C] with K <= 32, got %s" % (tuple(ini.shape),))
+                    c0 = torch.zeros((a.n, 32, 32), dtype=torch.float32, device=dev)
+                    c0[:, :ini.shape[1], :a.c].copy_(ini)
+                    max_objects = min(max_objects, ini.shape[1])
+                elif init != 'farthest':
+                    raise ValueError("init: 'farthest' or a tensor [B,K,C], got %r" % (init,))
+            labels, n_out, centres, sizes, moved = self.net.cluster(
+                a, f, method, bandwidth=bandwidth, shifts=shifts, max_objects=max_objects, max_rounds=max_rounds,
+                min_pixels=min_pixels, assign_rest=assign_rest, refine=refine, n_objects=n_in, iters=iters, init=c0)
+            return dict(labels=labels.view(a.n, a.h, a.w), n_objects=n_out, centres=centres[:, :, :a.c], sizes=sizes,
+                        moved=moved)
+
+    def segment_embedding(self, x, *, sem_map=None, n_objects=None, **kw):
+        """(sem_out, sem_argmax, labels, n_objects), the tuple segment() returns, with the instances taken from the
+        embedding instead of the attention decoder: backbone, semantic head and the two embedding stems, then
+        cluster_embedding(**kw) over the predicted foreground (or sem_map, fp32 {0,1} [B,H*W], in its place).  No decoder
+        pass and no glimpse point; method='kmeans' needs n_objects [B].  Eval mode only.  The labels go into
+        score_instances and clean_instances as segment's do."""
+        with torch.no_grad():
+            x_dec, _, B, H, W = self._backbone(x, "segment_embedding")
+            net = self.net
+            sem = net.sem_head(x_dec)
+            self._last_sem = sem
+            sem_out = net.to_nchw(sem)
+            sem_argmax = net.to_nchw(net.argmax_map(sem))
+            if sem_map is None:
+                fg = net.class_map(sem).view(B, -1)
+            else:
+                fg = sem_map.to(self.store.device).reshape(B, -1)
+                assert fg.shape[1] == H * W, "sem_map must be [B, H*W]"
+            out = self.cluster_embedding(self.head.stems(x_dec), fg, n_objects=n_objects, **kw)
+            return sem_out, sem_argmax, out["labels"], out["n_objects"]
 
     # ------------------------------------------------------------------ connected components, cleaning instance maps
     def _cc_map(self, maps, connectivity, min_area=1, max_objects=255):

@@ -23,13 +23,15 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import isa_amd  # noqa: F401,E402
 from isa_amd.model import Model  # noqa: E402
-from pred_list import (H, W, add_cleanup_arguments, check_cleanup_arguments, cleanup_arguments, nearest_upsample,  # noqa: E402
-                       write_classes, write_instances)
+from pred_list import (H, W, add_cleanup_arguments, add_embedding_arguments, check_cleanup_arguments,  # noqa: E402
+                       check_embedding_arguments, cleanup_arguments, nearest_upsample, write_classes, write_instances)
 
 
-def predict_file(model, image, out_dir, name, instances=False, max_objects=32, clean=None, components=None):
+def predict_file(model, image, out_dir, name, instances=False, max_objects=32, clean=None, components=None,
+                 instances_from='attention', bandwidth=None):
     """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask.  clean: ReSeg.clean_instances' keywords for the
-    instance map; components: ReSeg.split_components' keywords - the instance files come from the class map's components."""
+    instance map; components: ReSeg.split_components' keywords - the instance files come from the class map's components;
+    instances_from='embedding': the instances are mean-shift clusters of the embedding (ReSeg.segment_embedding)."""
     from PIL import Image
     from isa_amd.data import resize_bilinear
     x = resize_bilinear(torch.from_numpy(image[None]), (H, W))  # uint8 [1,H,W,3] on the device, bit-identical to PIL's
@@ -46,7 +48,10 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32, c
             classes = classes[0].cpu().numpy()                 # uint8 [H,W]: the arg-max taken on the device
             sem_arg = torch.from_numpy((classes != 0).astype(np.float32))[None, None]
         elif instances:
-            _, sem_arg, labels, counts = net.segment(x, max_objects)
+            if instances_from == 'embedding':
+                _, sem_arg, labels, counts = net.segment_embedding(x, max_objects=min(max_objects, 32), bandwidth=bandwidth)
+            else:
+                _, sem_arg, labels, counts = net.segment(x, max_objects)
             if clean is not None:                              # at model resolution, before the nearest up-sampling
                 labels, counts, _ = net.clean_instances(labels, **clean)
         else:
@@ -80,12 +85,14 @@ def parse_args(argv=None):
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     add_cleanup_arguments(parser)
+    add_embedding_arguments(parser)
     opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
     if opt.n_classes > 2 and opt.instances:
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     check_cleanup_arguments(parser, opt)
+    check_embedding_arguments(parser, opt)
     return opt
 
 
@@ -103,7 +110,8 @@ def main():
                   load_model_path=opt.model, usegpu=True)
     components = {'connectivity': opt.connectivity, 'min_area': opt.min_area, 'max_objects': opt.max_objects} \
         if opt.components else None
-    path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects, cleanup_arguments(opt), components)
+    path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects, cleanup_arguments(opt), components,
+                        opt.instances_from, opt.bandwidth)
     print('wrote', path)
 
 

@@ -15,6 +15,8 @@ object, at most `--max-objects` per image.  Without the flag nothing but the two
 `--n-classes K` (K > 2) loads a K-class semantic-only model and also writes <name>-sem_mask.png (uint8 class ids at the
 original size, same nearest-neighbour rule) and <name>-sem_mask_color.png (the ids through the palette); -fg_mask.png is
 then (class != 0) * 255.  The class map is taken on the device from the logits (ReSeg.class_map): no softmax comes down.
+`--instances-from embedding` takes the `--instances` label maps from mean-shift clustering of the instance embedding
+(ReSeg.segment_embedding; `--bandwidth` sets the ball's radius) instead of the attention decoder; the files are the same.
 `--min-area N`, `--keep largest|all` and `--connectivity 4|8` clean the `--instances` label maps on the device, at model
 resolution and before the up-sampling (ReSeg.clean_instances: the largest connected piece of every instance, or every
 piece as an object of its own; pieces under N pixels dropped).  `--components` needs no instance head: the connected
@@ -86,13 +88,42 @@ def parse_args(argv=None):
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes of the model, 2..32; more than 2: a '
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     add_cleanup_arguments(parser)
+    add_embedding_arguments(parser)
     opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
     if opt.n_classes > 2 and opt.instances:
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     check_cleanup_arguments(parser, opt)
+    check_embedding_arguments(parser, opt)
     return opt
+
+
+def add_embedding_arguments(parser):
+    parser.add_argument('--instances-from', choices=['attention', 'embedding'], default='attention', help='with '
+                        '--instances: the attention decoder (ReSeg.segment) or mean-shift clustering of the instance '
+                        'embedding (ReSeg.segment_embedding: no decoder pass, at most 32 instances)')
+    parser.add_argument('--bandwidth', type=float, default=None, help='with --instances-from embedding: the radius of the '
+                        'mean-shift ball (default: delta_dist = 1.5)')
+
+
+def check_embedding_arguments(parser, opt):
+    if opt.instances_from != 'attention' and not opt.instances:
+        parser.error('--instances-from chooses where the instances of --instances come from')
+    if opt.bandwidth is not None and opt.instances_from != 'embedding':
+        parser.error('--bandwidth needs --instances-from embedding')
+    if opt.bandwidth is not None and not opt.bandwidth > 0:
+        parser.error('--bandwidth must be positive')
+
+
+def segment_instances(net, x, opt):
+    """(sem_argmax, labels, n_objects) of the --instances label maps: ReSeg.segment, or ReSeg.segment_embedding."""
+    if opt.instances_from == 'embedding':
+        _, sem_arg, labels, counts = net.segment_embedding(x, max_objects=min(opt.max_objects, 32),
+                                                           bandwidth=opt.bandwidth)
+    else:
+        _, sem_arg, labels, counts = net.segment(x, opt.max_objects)
+    return sem_arg, labels, counts
 
 
 def add_cleanup_arguments(parser):
@@ -165,7 +196,7 @@ def main():
                 labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
             classes = classes.cpu().numpy()
         elif opt.instances:
-            _, sem_arg, labels, counts = net.segment(x, opt.max_objects)
+            sem_arg, labels, counts = segment_instances(net, x, opt)
             clean = cleanup_arguments(opt)
             if clean is not None:                        # at model resolution, before the nearest up-sampling
                 labels, counts, _ = net.clean_instances(labels, **clean)
