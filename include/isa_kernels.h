@@ -458,6 +458,15 @@ int isa_sem_loss_k_assemble(const float* sums, const float* cfg, int32_t B, int3
                             void* stream);
 int isa_sem_loss_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
                         const isa_tensor* dlogits, int32_t accumulate, void* stream);
+/* The same two entries with a weight per pixel, pixw fp32 [B,H,W] (4-byte aligned, m_i > 0 expected): the batch sums
+ * become {sum m w_y nll, sum m w_y}, so CE = sum m_i w_{y_i} nll_i / sum m_i w_{y_i} after isa_sem_loss_k_assemble (which
+ * is unchanged), and the CE term of pixel i's gradient is scaled by m_i.  The Dice sums and terms do not see pixw.  The two
+ * gradient entries run one kernel body (the unweighted one reads a 1.0 in place of pixw): with pixw = 1 and the same coef
+ * isa_sem_loss_k_grad_pw writes isa_sem_loss_k_grad's bits. */
+int isa_sem_loss_k_sums_pw(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* pixw,
+                           float* sums, void* stream);
+int isa_sem_loss_k_grad_pw(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
+                           const float* pixw, const isa_tensor* dlogits, int32_t accumulate, void* stream);
 /* ---- stable segmented key-value radix sort ---------------------------------------------------------------------------
  * isa_segsort_kv_u32 sorts nseg independent segments of seglen keys each (segment s = elements [s*seglen, (s+1)*seglen)):
  * uint32 keys ascending, compared on their bits [begin_bit, end_bit) only, every key carrying one uint32 value.  The sort
@@ -685,6 +694,39 @@ int isa_cc_label(const uint8_t* map, int32_t n, int32_t h, int32_t w, int32_t co
 int isa_cc_select(const uint8_t* map, const int32_t* comp, int32_t n, int32_t h, int32_t w, int32_t mode, int32_t min_area,
                   int32_t max_objects, uint8_t* out, int32_t* count, int32_t* dropped, void* scratch, int64_t scratch_bytes,
                   void* stream);
+/* ---- exact Euclidean distance transform to the two nearest instances; border weights and instance fill -----------------
+ * Every entry checks all its arguments before it launches or writes anything (ISA_EINVAL / ISA_EALIGN / ISA_ENOMEM), is
+ * asynchronous on `stream`, allocates nothing and never reads anything back: the launch count depends on the shape alone,
+ * so a captured hipGraph replays them.  Only integers decide anything in the transform and the fill: the results are
+ * unique, and two runs are bit-identical.
+ * isa_edt2_u8: labels uint8 [n,h,w] (4-byte aligned), 0 = no instance; n <= 65535, h and w <= ISA_EDT_MAX_SIDE, w % 4 == 0.
+ *   With D_k(p) the squared Euclidean distance (an integer) from pixel p to the nearest pixel of its image that holds label
+ *   k, over the labels present in that image (D_k = 0 on a pixel of label k):
+ *     d1sq int32 [n,h,w] (16-byte aligned): the smallest D_k; INT32_MAX when the image holds no label.
+ *     d2sq int32 [n,h,w] (16-byte aligned): the second smallest D_k as a multiset (= d1sq when two labels tie); INT32_MAX
+ *       when the image holds fewer than two labels.
+ *     nearest uint8 [n,h,w] (4-byte aligned): the smallest label k with D_k = d1sq; 0 when the image holds no label.
+ *   Any of the three may be NULL.  scratch: ISA_EDT_SCRATCH_BYTES(n,h,w) bytes, 16-byte aligned, need not be cleared (two
+ *   packed (vertical distance, label) entries per pixel).  Two launches: one lane per column (ISA_EDT_COL_LANES columns
+ *   per workgroup) sweeps it down and up; one workgroup of min(ISA_EDT_ROW_LANES, w rounded up to 64) lanes per row walks
+ *   outwards from every pixel over the row's entries in LDS (8 w + 16 bytes) until nothing farther can matter.
+ * isa_border_weights: out fp32 [n,hw] (16-byte aligned) = 1 where labels != 0 or d2sq is INT32_MAX, else
+ *   1 + w0 * expf(-(sqrtf(d1sq) + sqrtf(d2sq))^2 / (2 sigma^2)).  cfg: device float[2] = {w0, sigma}, read at run time, so a
+ *   captured hipGraph follows in-place changes.  hw % 4 == 0, hw < 2^30; one launch.
+ * isa_fill_labels: out uint8 [n,hw] (4-byte aligned; it must not overlap labels: ISA_EINVAL) = labels where that is
+ *   non-zero; else nearest where fg != 0 and d1sq <= max_dist_sq (max_dist_sq < 0: no limit); else 0.  filled int32 [n]:
+ *   pixels filled per image (cleared by the entry, integer adds).  labels, fg, nearest 4-byte aligned, d1sq 16-byte
+ *   aligned, hw % 4 == 0, n <= 65535; two launches. */
+#define ISA_EDT_MAX_SIDE 4096
+#define ISA_EDT_COL_LANES 64
+#define ISA_EDT_ROW_LANES 256
+#define ISA_EDT_SCRATCH_BYTES(n, h, w) ((int64_t)(n) * (h) * (w) * 8)
+int isa_edt2_u8(const uint8_t* labels, int32_t n, int32_t h, int32_t w, int32_t* d1sq, int32_t* d2sq, uint8_t* nearest,
+                void* scratch, int64_t scratch_bytes, void* stream);
+int isa_border_weights(const uint8_t* labels, const int32_t* d1sq, const int32_t* d2sq, const float* cfg, int32_t n,
+                       int64_t hw, float* out, void* stream);
+int isa_fill_labels(const uint8_t* labels, const uint8_t* fg, const uint8_t* nearest, const int32_t* d1sq,
+                    int32_t max_dist_sq, int32_t n, int64_t hw, uint8_t* out, int32_t* filled, void* stream);
 int isa_ins_softmax_bwd(const float* alpha, const int64_t* ins, const int32_t* idx, const int32_t* s_t,
                         const float* adv, int32_t n, int32_t nobj, int64_t L, float* dmerge /*[nsrc, L]*/, int32_t nsrc,
                         void* stream);

@@ -52,8 +52,10 @@ __device__ __forceinline__ float softmax_row(float (&l)[KT], float (&p)[KT]) {
 // sums[b][3K] = {A[K], S[K], T[K]}, sums[B*3K] = sum w_y*nll, sums[B*3K+1] = sum w_y (zeroed by the caller).
 // Grid (x chunks, B): a workgroup walks pixels of ONE image, keeps 3K+2 partials per lane, reduces them across its
 // four waves through LDS and issues one atomic per destination (Guideline 12).
-template <typename T, int KT>
-__global__ __launch_bounds__(256) void sem_k_sums_kernel(View x, const uint8_t* labels, const float* cfg, float* sums) {
+// PW: the CE weight of pixel i is m_i * w_y with m = pixw [B,H,W]; without it pixw is never read.
+template <typename T, int KT, bool PW>
+__global__ __launch_bounds__(256) void sem_k_sums_kernel(View x, const uint8_t* labels, const float* cfg, const float* pixw,
+                                                         float* sums) {
     __shared__ float sh[4][3 * KT + 2];
     __shared__ float sw[KT];                               // class weights: an LDS read per pixel, not a global one
     const int b = blockIdx.y, K = x.c;
@@ -78,7 +80,8 @@ __global__ __launch_bounds__(256) void sem_k_sums_kernel(View x, const uint8_t* 
             Tg[c] += hit ? 1.f : 0.f;
             ly = hit ? l[c] : ly;
         }
-        const float w = sw[min(y, KT - 1)];              // (the clamp only keeps a bad label's read inside sw)
+        float w = sw[min(y, KT - 1)];                    // (the clamp only keeps a bad label's read inside sw)
+        if constexpr (PW) w *= pixw[(long)b * L + p];
         ce += w * (lse - ly);
         ws += w;
     }
@@ -161,9 +164,17 @@ __global__ __launch_bounds__(1024) void sem_k_assemble_kernel(const float* sums,
 }
 
 // d l_k = ce_scale * w_y * (p_k - [k == y]) + p_k * (v_k - sum_j p_j v_j),  v_c = u_c * (2 g_c / den_c - (2A_c+1)/den_c^2)
+__device__ float k_unit_weight = 1.f;     // what the unweighted entry's pixels read in place of pixw
+
+// pixw (may be NULL): the CE term is scaled by m = pixw of the pixel.  The flag is a run-time one ON PURPOSE: as two template
+// instantiations the compiler contracted the two bodies differently (the exponential's argument fused into an fma in one
+// and not in the other, packed fmas in one only), and pixw = 1 then differed from the unweighted entry in the last bit.
+// One body serves both entries, so unit weights give the unweighted entry's bits by construction: cw * 1.0f is cw.  And it
+// is a stride, not a branch - a loop-invariant branch would be unswitched into two loop bodies, compiled apart again: the
+// unweighted entry reads the one device word above at stride 0.
 template <typename T, int KT>
 __global__ __launch_bounds__(256) void sem_k_grad_kernel(View x, const uint8_t* labels, const float* cfg, const float* coef,
-                                                         View dx, int accumulate) {
+                                                         const float* pixw, View dx, int accumulate) {
     __shared__ float su[4][KT];
     const int b = blockIdx.y, K = x.c, B = x.n;
     const long L = (long)x.h * x.w;
@@ -180,6 +191,8 @@ __global__ __launch_bounds__(256) void sem_k_grad_kernel(View x, const uint8_t* 
 #pragma unroll
     for (int c = 0; c < KT; ++c) { u[c] = su[0][c]; e2[c] = su[1][c]; base[c] = -u[c] * su[2][c]; }
     const float ce_scale = coef[(long)B * K];
+    const float* pw = pixw ? pixw + (long)b * L : &k_unit_weight;
+    const long pw_stride = pixw ? 1 : 0;
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < L; p += (long)gridDim.x * 256) {
         float l[KT], pr[KT];
         load_row<T, KT>(reinterpret_cast<const T*>(x.data) + ((long)b * L + p) * x.ld, K, l);
@@ -193,7 +206,7 @@ __global__ __launch_bounds__(256) void sem_k_grad_kernel(View x, const uint8_t* 
             l[c] = v;                                                 // reuse l[] for v
             sv += pr[c] * v;
         }
-        const float cw = ce_scale * su[3][min(y, KT - 1)];
+        const float cw = ce_scale * su[3][min(y, KT - 1)] * pw[p * pw_stride];
         T* d = reinterpret_cast<T*>(dx.data) + ((long)b * L + p) * dx.ld;
 #pragma unroll
         for (int j = 0; j < KT / 8; ++j) {
@@ -212,27 +225,28 @@ __global__ __launch_bounds__(256) void sem_k_grad_kernel(View x, const uint8_t* 
     }
 }
 
-template <typename T>
-int launch_sums(const isa_tensor* x, const uint8_t* labels, const float* cfg, float* sums, dim3 grid, hipStream_t s) {
+template <typename T, bool PW>
+int launch_sums(const isa_tensor* x, const uint8_t* labels, const float* cfg, const float* pixw, float* sums, dim3 grid,
+                hipStream_t s) {
     const View v = mkview(x);
     switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((sem_k_sums_kernel<T, 8>), grid, dim3(256), 0, s, v, labels, cfg, sums); break;
-        case 2: hipLaunchKernelGGL((sem_k_sums_kernel<T, 16>), grid, dim3(256), 0, s, v, labels, cfg, sums); break;
-        case 3: hipLaunchKernelGGL((sem_k_sums_kernel<T, 24>), grid, dim3(256), 0, s, v, labels, cfg, sums); break;
-        default: hipLaunchKernelGGL((sem_k_sums_kernel<T, 32>), grid, dim3(256), 0, s, v, labels, cfg, sums); break;
+        case 1: hipLaunchKernelGGL((sem_k_sums_kernel<T, 8, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
+        case 2: hipLaunchKernelGGL((sem_k_sums_kernel<T, 16, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
+        case 3: hipLaunchKernelGGL((sem_k_sums_kernel<T, 24, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
+        default: hipLaunchKernelGGL((sem_k_sums_kernel<T, 32, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
     }
     return launch_status();
 }
 
 template <typename T>
-int launch_grad(const isa_tensor* x, const uint8_t* labels, const float* cfg, const float* coef, const isa_tensor* dx,
-                int acc, dim3 grid, hipStream_t s) {
+int launch_grad(const isa_tensor* x, const uint8_t* labels, const float* cfg, const float* coef, const float* pixw,
+                const isa_tensor* dx, int acc, dim3 grid, hipStream_t s) {
     const View v = mkview(x), dv = mkview(dx);
     switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((sem_k_grad_kernel<T, 8>), grid, dim3(256), 0, s, v, labels, cfg, coef, dv, acc); break;
-        case 2: hipLaunchKernelGGL((sem_k_grad_kernel<T, 16>), grid, dim3(256), 0, s, v, labels, cfg, coef, dv, acc); break;
-        case 3: hipLaunchKernelGGL((sem_k_grad_kernel<T, 24>), grid, dim3(256), 0, s, v, labels, cfg, coef, dv, acc); break;
-        default: hipLaunchKernelGGL((sem_k_grad_kernel<T, 32>), grid, dim3(256), 0, s, v, labels, cfg, coef, dv, acc); break;
+        case 1: hipLaunchKernelGGL((sem_k_grad_kernel<T, 8>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
+        case 2: hipLaunchKernelGGL((sem_k_grad_kernel<T, 16>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
+        case 3: hipLaunchKernelGGL((sem_k_grad_kernel<T, 24>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
+        default: hipLaunchKernelGGL((sem_k_grad_kernel<T, 32>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
     }
     return launch_status();
 }
@@ -244,13 +258,43 @@ static inline bool logits_ok(const isa_tensor* x) {
 
 }  // namespace
 
-extern "C" int isa_sem_loss_k_sums(const isa_tensor* logits, const uint8_t* labels, const float* cfg, float* sums,
-                                   void* stream) {
-    if (!logits_ok(logits) || !labels || !cfg || !sums) return ISA_EINVAL;
+namespace {
+template <bool PW>
+int sem_k_sums(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* pixw, float* sums,
+               void* stream) {
+    if (!logits_ok(logits) || !labels || !cfg || !sums || (PW && !pixw)) return ISA_EINVAL;
+    if (PW && reinterpret_cast<uintptr_t>(pixw) % 4 != 0) return ISA_EALIGN;
     const long L = (long)logits->h * logits->w;
     dim3 grid(grid_cap(cdiv(L, 256), 64), logits->n);
-    if (logits->dtype == ISA_BF16) return launch_sums<bf16_t>(logits, labels, cfg, sums, grid, as_stream(stream));
-    return launch_sums<float>(logits, labels, cfg, sums, grid, as_stream(stream));
+    if (logits->dtype == ISA_BF16)
+        return launch_sums<bf16_t, PW>(logits, labels, cfg, pixw, sums, grid, as_stream(stream));
+    return launch_sums<float, PW>(logits, labels, cfg, pixw, sums, grid, as_stream(stream));
+}
+
+template <bool PW>
+int sem_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef, const float* pixw,
+               const isa_tensor* dlogits, int32_t accumulate, void* stream) {
+    if (!logits_ok(logits) || !tensor_ok(dlogits, 8) || !labels || !cfg || !coef || (PW && !pixw)) return ISA_EINVAL;
+    if (dlogits->dtype != logits->dtype || dlogits->n != logits->n || dlogits->h != logits->h || dlogits->w != logits->w ||
+        dlogits->c != logits->c)
+        return ISA_EINVAL;
+    if (PW && reinterpret_cast<uintptr_t>(pixw) % 4 != 0) return ISA_EALIGN;
+    const long L = (long)logits->h * logits->w;
+    dim3 grid(grid_cap(cdiv(L, 256), 128), logits->n);
+    if (logits->dtype == ISA_BF16)
+        return launch_grad<bf16_t>(logits, labels, cfg, coef, pixw, dlogits, accumulate, grid, as_stream(stream));
+    return launch_grad<float>(logits, labels, cfg, coef, pixw, dlogits, accumulate, grid, as_stream(stream));
+}
+}  // namespace
+
+extern "C" int isa_sem_loss_k_sums(const isa_tensor* logits, const uint8_t* labels, const float* cfg, float* sums,
+                                   void* stream) {
+    return sem_k_sums<false>(logits, labels, cfg, nullptr, sums, stream);
+}
+
+extern "C" int isa_sem_loss_k_sums_pw(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* pixw,
+                                      float* sums, void* stream) {
+    return sem_k_sums<true>(logits, labels, cfg, pixw, sums, stream);
 }
 
 extern "C" int isa_sem_loss_k_assemble(const float* sums, const float* cfg, int32_t B, int32_t K, float* coef, float* scal,
@@ -262,15 +306,12 @@ extern "C" int isa_sem_loss_k_assemble(const float* sums, const float* cfg, int3
 
 extern "C" int isa_sem_loss_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
                                    const isa_tensor* dlogits, int32_t accumulate, void* stream) {
-    if (!logits_ok(logits) || !tensor_ok(dlogits, 8) || !labels || !cfg || !coef) return ISA_EINVAL;
-    if (dlogits->dtype != logits->dtype || dlogits->n != logits->n || dlogits->h != logits->h || dlogits->w != logits->w ||
-        dlogits->c != logits->c)
-        return ISA_EINVAL;
-    const long L = (long)logits->h * logits->w;
-    dim3 grid(grid_cap(cdiv(L, 256), 128), logits->n);
-    if (logits->dtype == ISA_BF16)
-        return launch_grad<bf16_t>(logits, labels, cfg, coef, dlogits, accumulate, grid, as_stream(stream));
-    return launch_grad<float>(logits, labels, cfg, coef, dlogits, accumulate, grid, as_stream(stream));
+    return sem_k_grad<false>(logits, labels, cfg, coef, nullptr, dlogits, accumulate, stream);
+}
+
+extern "C" int isa_sem_loss_k_grad_pw(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef,
+                                      const float* pixw, const isa_tensor* dlogits, int32_t accumulate, void* stream) {
+    return sem_k_grad<true>(logits, labels, cfg, coef, pixw, dlogits, accumulate, stream);
 }
 
 // ---- reference-format targets: int64 one-hot [B,K,H,W] -> uint8 labels [B,H,W] and the fp32 argmax map ----------------

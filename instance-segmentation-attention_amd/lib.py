@@ -39,6 +39,14 @@ def cc_select_scratch_bytes(n, h, w):
     return n * (h * w * 4 + CC_TAB_BYTES)
 
 
+EDT_MAX_SIDE, EDT_COL_LANES, EDT_ROW_LANES = 4096, 64, 256      # ISA_EDT_MAX_SIDE, ISA_EDT_COL_LANES, ISA_EDT_ROW_LANES
+
+
+def edt_scratch_bytes(n, h, w):
+    """ISA_EDT_SCRATCH_BYTES: the two packed column entries per pixel of isa_edt2_u8."""
+    return n * h * w * 8
+
+
 DISC_MAX_K, DISC_CFG_FLOATS, DISC_CNT_STRIDE, ROW_CHUNKS = 32, 12, 36, 64     # ISA_DISC_*, ISA_ROW_CHUNKS
 
 
@@ -173,6 +181,8 @@ SIGNATURES = {
     "isa_sem_loss_k_sums": [P_T, VP, VP, VP, VP],
     "isa_sem_loss_k_assemble": [VP, VP, I32, I32, VP, VP, VP],
     "isa_sem_loss_k_grad": [P_T, VP, VP, VP, P_T, I32, VP],
+    "isa_sem_loss_k_sums_pw": [P_T, VP, VP, VP, VP, VP],
+    "isa_sem_loss_k_grad_pw": [P_T, VP, VP, VP, VP, P_T, I32, VP],
     "isa_labels_from_onehot": [VP, I32, I32, I64, VP, VP, VP],
     # stable segmented radix sort and the Lovasz-Softmax criterion built on it
     "isa_segsort_kv_u32": [VP, VP, VP, VP, I32, I64, I32, I32, VP, VP, VP, I64, VP],
@@ -224,6 +234,10 @@ SIGNATURES = {
     # connected components and instance clean-up (ReSeg.components, split_components, clean_instances)
     "isa_cc_label": [VP, I32, I32, I32, I32, VP, VP, VP, I64, VP],
     "isa_cc_select": [VP, VP, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, I64, VP],
+    # distance transform to the two nearest instances (ReSeg.distance_transform, border_weights, fill_instances)
+    "isa_edt2_u8": [VP, I32, I32, I32, VP, VP, VP, VP, I64, VP],
+    "isa_border_weights": [VP, VP, VP, VP, I32, I64, VP, VP],
+    "isa_fill_labels": [VP, VP, VP, VP, I32, I32, I64, VP, VP, VP],
 }
 
 

@@ -95,7 +95,8 @@ class Model(object):
                     row = {}
                 if sem.dtype == torch.uint8:              # compact targets: one-hot on the device (isa_collate_targets)
                     sem, _ = self.model.net.collate_targets(sem, ins)
-                costs = self.model.sem_costs(sem)         # the reference logs CE / Dice in validation too (model.py:255-269)
+                # the reference logs CE / Dice in validation too (model.py:255-269); the border term needs the planes
+                costs = self.model.sem_costs(sem, ins if self.model.net.crit.border_on else None)
                 row.update(self.__sem_row(costs))
                 if self.val_sem_scores:                   # before the next forward: the logits live in this step's arena
                     _, conf = self.model.score_semantic(sem, check=False)
@@ -127,15 +128,19 @@ class Model(object):
             raise ValueError("method must be 'attention', 'meanshift' or 'kmeans', got %r" % (method,))
         return sem_arg, labels, count
 
-    def __score_batch(self, batch, max_objects, check, clean=None, method='attention', bandwidth=None):
+    def __score_batch(self, batch, max_objects, check, clean=None, method='attention', bandwidth=None, fill=False,
+                      fill_max_dist=None):
         """segment() + score_instances() of one loader batch: the device tensor [B,8], and the number of pixels whose
         label the histograms do not hold (a device scalar: the callers read it with their one copy and raise).
-        clean: keyword arguments of ReSeg.clean_instances, applied to the labels before they are scored."""
+        clean: keyword arguments of ReSeg.clean_instances, applied to the labels before they are scored; fill: then the
+        unlabelled foreground of the predicted class map goes to the nearest instance (ReSeg.fill_instances)."""
         images, sem, ins, n_objects = batch
         m = self.model
         sem_arg, labels, count = self.__instances(images, max_objects, method, bandwidth, n_objects)
         if clean is not None:
             labels, count, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
+        if fill:
+            labels, _ = m.fill_instances(labels, m.class_map(), fill_max_dist)
         out = m.score_instances(labels, count, ins, n_objects, sem_arg, sem, max_objects=max_objects, check=check)
         return out, m.last_score_oob.sum()
 
@@ -169,10 +174,12 @@ class Model(object):
     def fit(self, criterion_type, delta_var, delta_dist, norm, learning_rate, weight_decay, clip_grad_norm,
             lr_drop_factor, lr_drop_patience, optimize_bg, optimizer, train_cnn, n_epochs, class_weights,
             train_loader, test_loader, model_save_path, debug, lovasz_per_image=None, lovasz_only_present=None,
-            disc_weight=0.0, disc_form='reference'):
+            border_weight=0.0, border_sigma=5.0, disc_weight=0.0, disc_form='reference'):
         """model.py:359-460.  delta_var, delta_dist, norm: the parameters of the reference's DiscriminativeLoss
         (model.py:109-115, which it builds and never calls); here the loss trains the instance embedding when
-        disc_weight > 0, in the form disc_form ('reference' | 'full', ReSeg.discriminative_loss)."""
+        disc_weight > 0, in the form disc_form ('reference' | 'full', ReSeg.discriminative_loss).
+        border_weight > 0 weighs the cross-entropy of every pixel by the U-Net border map of the step's instance targets,
+        1 + border_weight * exp(-(d1 + d2)^2 / (2 border_sigma^2)), computed on the device (ReSeg.border_weights)."""
         assert criterion_type in ['CE', 'Dice', 'Multi', 'Lovasz', 'CELovasz']  # model.py:364, and the Lovasz criteria
         if lovasz_per_image is None:
             lovasz_per_image = self.lovasz_per_image
@@ -196,7 +203,7 @@ class Model(object):
                                 criterion_type, class_weights, optimize_bg, train_cnn, lovasz_per_image,
                                 lovasz_only_present,
                                 dict(disc_weight=disc_weight, delta_var=delta_var, delta_dist=delta_dist, disc_norm=norm,
-                                     disc_form=disc_form))
+                                     disc_form=disc_form, border_weight=border_weight, border_sigma=border_sigma))
         best_val_cost = np.inf
         if os.environ.get('ISA_PREFETCH', '1') != '0':      # batch i+1 uploads on a side stream while step i runs
             from .data import DevicePrefetcher
@@ -307,7 +314,7 @@ class Model(object):
         return {'keep': keep or 'all', 'connectivity': connectivity, 'min_area': int(min_area)}
 
     def predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
-                          bandwidth=None, n_objects=None):
+                          bandwidth=None, n_objects=None, fill=False, fill_max_dist=None):
         """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
         instance prediction is dead at HEAD).  images: [b,21,h,w] float or raw uint8 RGB [b,h,w,3].  Returns host tensors
         (fg_prob [b,h,w] = softmax probability of the foreground class, labels uint8 [b,h,w] with 0 = no instance,
@@ -317,7 +324,9 @@ class Model(object):
         pieces under min_area pixels dropped; connectivity 4 or 8).  With the defaults none of that runs.
         method='meanshift' | 'kmeans' takes the instances from clusters of the instance embedding instead of the attention
         decoder (ReSeg.segment_embedding, at most 32 per image): mean-shift of radius bandwidth (default 1.5 = delta_dist),
-        or k-means with the object counts n_objects [b]."""
+        or k-means with the object counts n_objects [b].
+        fill=True gives, after the clean-up, every foreground pixel of the predicted class map that is still 0 to the nearest
+        instance (ReSeg.fill_instances), within fill_max_dist pixels when that is given.  Off by default."""
         assert len(images.size()) == 4
         m = self.model
         if not m.use_instance_seg:
@@ -328,6 +337,8 @@ class Model(object):
         _, labels, n_objects = self.__instances(images, max_objects, method, bandwidth, n_objects)
         if clean is not None:
             labels, n_objects, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
+        if fill:
+            labels, _ = m.fill_instances(labels, m.class_map(), fill_max_dist)
         fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
 
@@ -350,7 +361,7 @@ class Model(object):
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
 
     def evaluate(self, loader, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
-                 bandwidth=None):
+                 bandwidth=None, fill=False, fill_max_dist=None):
         """Scores of ground-truth-free instance inference over a loader of (images, sem, ins, n_objects) batches, either
         target form: every batch is segmented (ReSeg.segment, at most max_objects instances per image; default: the
         constructor's max_n_objects) and scored on the device (ReSeg.score_instances); one device-to-host copy at the end.
@@ -358,7 +369,7 @@ class Model(object):
         [N,8] of score_instances, the three means are taken over the images whose value is not NaN (evaluate.py's main
         averages the images it scored), n_skipped counts the images whose SBD is NaN (neither map holds an object).
         min_area / keep / connectivity: the clean-up of predict_instances, applied to every label map before it is scored
-        (with the defaults none of it runs).
+        (with the defaults none of it runs).  fill / fill_max_dist: predict_instances' fill, after the clean-up.
         method='meanshift' | 'kmeans': the instances come from clusters of the instance embedding (predict_instances);
         'kmeans' is given every batch's ground-truth object counts - the reference's protocol, a count supplied.
         It scores what the loader yields on THIS rank; reducing over ranks is left to the caller."""
@@ -368,8 +379,8 @@ class Model(object):
         clean = self.__clean_arguments(min_area, keep, connectivity)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
-        rows = [self.__score_batch(b, max_objects, check=False, clean=clean, method=method, bandwidth=bandwidth)
-                for b in loader]
+        rows = [self.__score_batch(b, max_objects, check=False, clean=clean, method=method, bandwidth=bandwidth, fill=fill,
+                                   fill_max_dist=fill_max_dist) for b in loader]
         if not rows:
             nan = float('nan')
             return {'SBD': nan, '|DiC|': nan, 'FG Dice': nan, 'n_images': 0, 'n_skipped': 0,

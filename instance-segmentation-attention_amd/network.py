@@ -37,11 +37,16 @@ class SemCriterion:
     optimize_bg, lovasz_only_present, w_0 .. w_{K-1}}; no weights = all ones (the same CE and Dice as unweighted).
     "Lovasz" / "CELovasz": the Lovasz-Softmax loss (lovasz_losses.py:156-196), alone or added to CE; class weights are
     the CE term's.  lovasz_per_image sets the segment geometry, so it belongs to a captured step's configuration.
-    `legacy`: the shipped combination (K = 2, Multi, no weights, fg only) runs the 2-class kernels it always ran."""
+    `legacy`: the shipped combination (K = 2, Multi, no weights, fg only) runs the 2-class kernels it always ran.
+    The border term (set_border) weighs the CE of every pixel by the U-Net border map of the step's
+    instance targets: its {w0, sigma} live in a second device buffer, `border`, rewritten in place; on / off belongs to a
+    captured step's configuration (border_key()), the values do not.  With it on no combination is `legacy`."""
 
     def __init__(self, n_classes, device):
         self.K = n_classes
         self.cfg = torch.zeros(4 + n_classes, dtype=torch.float32, device=device)
+        self.border = torch.tensor([0.0, 5.0], dtype=torch.float32, device=device)
+        self.border_on, self.border_weight, self.border_sigma = False, 0.0, 5.0
         self.set("Multi", None, False)
 
     def set(self, criterion="Multi", class_weights=None, optimize_bg=False, lovasz_per_image=False,
@@ -50,6 +55,8 @@ class SemCriterion:
         K = self.K
         if criterion == "Lovasz" and class_weights is not None:
             raise ValueError("class_weights weigh the CE term: the Lovasz criterion has none (use CELovasz)")
+        if criterion == "Lovasz" and self.border_on:
+            raise ValueError("the border weight weighs the CE term: the Lovasz criterion has none (use CELovasz)")
         if class_weights is not None:
             class_weights = [float(v) for v in class_weights]
             if len(class_weights) != K:
@@ -60,7 +67,7 @@ class SemCriterion:
         self.ce, self.dice = criterion in ("CE", "Multi", "CELovasz"), criterion in ("Dice", "Multi")
         self.lovasz = criterion in ("Lovasz", "CELovasz")
         self.lovasz_per_image, self.lovasz_only_present = bool(lovasz_per_image), bool(lovasz_only_present)
-        self.legacy = K == 2 and criterion == "Multi" and class_weights is None and not optimize_bg
+        self._set_legacy()
         w = class_weights if class_weights is not None else [1.0] * K
         self.cfg.copy_(torch.tensor([float(self.ce), float(self.dice), float(self.optimize_bg),
                                      float(self.lovasz and self.lovasz_only_present)] + w))
@@ -69,6 +76,32 @@ class SemCriterion:
     def weights(self):
         """The class weights on the device (a view of the settings buffer: in-place writes reach a captured graph)."""
         return self.cfg[4:]
+
+    def set_border(self, weight, sigma=5.0):
+        """The border term 1 + weight * exp(-(d1 + d2)^2 / (2 sigma^2)) on the CE of unlabelled pixels; weight 0 = off."""
+        weight, sigma = float(weight), float(sigma)
+        if weight < 0 or not sigma > 0:
+            raise ValueError("border weight must not be negative and sigma must be positive, got %r, %r" % (weight, sigma))
+        if weight > 0 and self.criterion == "Lovasz":
+            raise ValueError("the border weight weighs the CE term: the Lovasz criterion has none (use CELovasz)")
+        self.border_on, self.border_weight, self.border_sigma = weight > 0, weight, sigma
+        self._set_legacy()
+        self.border.copy_(torch.tensor([weight, sigma]))
+
+    def _set_legacy(self):
+        self.legacy = (self.K == 2 and self.criterion == "Multi" and self.class_weights is None and not self.optimize_bg
+                       and not self.border_on)
+
+    def set_border_values(self, weight, sigma=None):
+        """In place: a captured step follows it (on / off is part of the step's configuration and stays)."""
+        assert float(weight) > 0 and self.border_on, "the weight of a running border term; switch it with set_border()"
+        sigma = self.border_sigma if sigma is None else float(sigma)
+        assert sigma > 0
+        self.border_weight, self.border_sigma = float(weight), sigma
+        self.border.copy_(torch.tensor([float(weight), sigma]))
+
+    def border_key(self):
+        return self.border_on
 
 
 DISC_FORMS = {"reference": (True, (1.0, 0.0, 0.0, 0.005)), "full": (False, (1.0, 1.0, 0.001, 0.0))}
@@ -245,11 +278,68 @@ class Network:
             E.tape.append(bwd)
         return sem
 
-    def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None):
+    def distance_transform(self, labels: torch.Tensor, want=(True, True, True), alloc=None):
+        """(d1sq int32, d2sq int32, nearest uint8), each [n,h,w] or None where `want` says so, of the uint8 label map
+        [n,h,w] on the device (isa_edt2_u8).  alloc(shape, dtype): where outputs and scratch come from (default: new
+        tensors)."""
+        E = self.E
+        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
+        n, h, w = labels.shape
+        alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=labels.device))
+        d1 = alloc((n, h, w), torch.int32) if want[0] else None
+        d2 = alloc((n, h, w), torch.int32) if want[1] else None
+        near = alloc((n, h, w), torch.uint8) if want[2] else None
+        scratch = alloc((L.edt_scratch_bytes(n, h, w),), torch.uint8)
+        L.check(E.lib.isa_edt2_u8(L.ptr(labels), n, h, w, L.ptr(d1), L.ptr(d2), L.ptr(near), L.ptr(scratch), scratch.numel(),
+                                  E.st()), "isa_edt2_u8")
+        return d1, d2, near
+
+    def border_weights(self, labels: torch.Tensor, cfg: torch.Tensor, alloc=None):
+        """fp32 [n,h,w] border weight map of the uint8 instance label map [n,h,w] (isa_edt2_u8 + isa_border_weights);
+        cfg: device float[2] = {w0, sigma}, read by the kernel at run time."""
+        E = self.E
+        n, h, w = labels.shape
+        alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=labels.device))
+        d1, d2, _ = self.distance_transform(labels, (True, True, False), alloc)
+        out = alloc((n, h, w), torch.float32)
+        L.check(E.lib.isa_border_weights(L.ptr(labels), L.ptr(d1), L.ptr(d2), L.ptr(cfg), n, h * w, L.ptr(out), E.st()),
+                "isa_border_weights")
+        return out
+
+    def fill_labels(self, labels: torch.Tensor, fg: torch.Tensor, max_dist_sq=-1):
+        """(labels uint8 [n,h,w], filled int32 [n]): every pixel with label 0 and fg != 0 takes the nearest label when
+        that lies within max_dist_sq (< 0: no limit) (isa_edt2_u8 + isa_fill_labels).  New tensors."""
+        E = self.E
+        n, h, w = labels.shape
+        assert fg.dtype == torch.uint8 and fg.shape == labels.shape and fg.is_contiguous(), "fg: contiguous uint8 [n,h,w]"
+        d1, _, near = self.distance_transform(labels, (True, False, True))
+        out = torch.empty_like(labels)
+        filled = torch.empty((n,), dtype=torch.int32, device=labels.device)
+        L.check(E.lib.isa_fill_labels(L.ptr(labels), L.ptr(fg), L.ptr(near), L.ptr(d1), int(max_dist_sq), n, h * w, L.ptr(out),
+                                      L.ptr(filled), E.st()), "isa_fill_labels")
+        return out, filled
+
+    def _border_map(self, sem: Act, ins: torch.Tensor):
+        """The step's border weight map fp32 [n,h,w] from its instance planes (either form forward() takes), in the arena."""
+        E = self.E
+        if ins is None or ins.dim() != 4 or ins.numel() == 0:
+            raise ValueError("the border weight is on: the step needs the batch's instance planes")
+        form = {torch.uint8: L.PLANES_U8_NHWK, torch.int64: L.PLANES_I64_NKHW, torch.float32: L.PLANES_F32_NKHW}.get(ins.dtype)
+        if form is None:
+            raise TypeError("instance planes: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % ins.dtype)
+        n, h, w = sem.n, sem.h, sem.w
+        k = ins.shape[3] if form == L.PLANES_U8_NHWK else ins.shape[1]
+        assert ins.is_contiguous() and ins.numel() == n * h * w * k, "instance planes do not match the logits"
+        lab = E.arena.alloc((n, h, w), torch.uint8)
+        L.check(E.lib.isa_labels_from_planes(L.ptr(ins), form, n, k, h * w, L.ptr(lab), E.st()), "isa_labels_from_planes")
+        return self.border_weights(lab, self.crit.border, E.arena.alloc)
+
+    def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None, ins: torch.Tensor = None):
         """Trainer-side semantic criterion on the logits (model.py:255-269), per self.crit: CE (weighted) and / or
         Dice (time=1, per class, fg or all), or Lovasz-Softmax with or without CE.  `labels`: the uint8 label map when
         the caller has it (compact targets), else taken from the one-hot.  Returns device tensor [ce, dice] (0 for a term
-        the criterion lacks), [ce, 0, lovasz] for the Lovasz criteria; records d(sem)."""
+        the criterion lacks), [ce, 0, lovasz] for the Lovasz criteria; records d(sem).  With the border term on, `ins`
+        (the batch's instance planes) gives the weight map of the CE term."""
         E = self.E
         n = sem.n
         if self.crit.legacy:             # the shipped criterion: its pinned 2-class kernels
@@ -271,22 +361,39 @@ class Network:
             L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, K, sem.h * sem.w, L.ptr(labels), None, E.st()),
                     "isa_labels_from_onehot")
         assert labels.dtype == torch.uint8 and tuple(labels.shape) == (n, sem.h, sem.w)
+        pixw = self._border_map(sem, ins) if self.crit.border_on else None
         if self.crit.lovasz:
-            return self._lovasz_loss(sem, labels)
+            return self._lovasz_loss(sem, labels, pixw)
         sums = E.scratch(3 * n * K + 2)
-        L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+        self._k_sums(sem, labels, pixw, sums)
         coef, scal = E.f32(3 * n * K + 1), E.f32(2)
         L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
                 "isa_sem_loss_k_assemble")
         if E.record:
             def bwd():
                 acc = E.grads.claim(sem, E)
-                L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef),
-                                                  E.grads.grad_of(sem).d(), acc, E.st()), "isa_sem_loss_k_grad")
+                self._k_grad(sem, labels, pixw, coef, E.grads.grad_of(sem).d(), acc)
             E.tape.append(bwd)
         return scal
 
-    def _lovasz_loss(self, sem: Act, labels: torch.Tensor):
+    def _k_sums(self, sem, labels, pixw, sums):
+        E, cfg = self.E, self.crit.cfg
+        if pixw is None:
+            L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+        else:
+            L.check(E.lib.isa_sem_loss_k_sums_pw(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(pixw), L.ptr(sums), E.st()),
+                    "isa_sem_loss_k_sums_pw")
+
+    def _k_grad(self, sem, labels, pixw, coef, dsem, acc):
+        E, cfg = self.E, self.crit.cfg
+        if pixw is None:
+            L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), dsem, acc, E.st()),
+                    "isa_sem_loss_k_grad")
+        else:
+            L.check(E.lib.isa_sem_loss_k_grad_pw(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), L.ptr(pixw), dsem, acc,
+                                                 E.st()), "isa_sem_loss_k_grad_pw")
+
+    def _lovasz_loss(self, sem: Act, labels: torch.Tensor, pixw: torch.Tensor = None):
         """CELovasz: the CE term from the K-class kernels as they are, then the Lovasz-Softmax launches (keys, segmented
         sort, coefficients per class group; one assemble); the backward adds both gradients into d(sem).  The launch
         count depends on (K, B, H*W, per_image) alone and nothing is read back: the step captures."""
@@ -303,7 +410,7 @@ class Network:
         coef = None
         if crit.ce:
             sums = E.scratch(3 * n * K + 2)
-            L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+            self._k_sums(sem, labels, pixw, sums)
             coef = E.f32(3 * n * K + 1)
             L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
                     "isa_sem_loss_k_assemble")
@@ -336,8 +443,7 @@ class Network:
                 acc = E.grads.claim(sem, E)
                 dsem = E.grads.grad_of(sem).d()
                 if coef is not None:
-                    L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), dsem, acc, E.st()),
-                            "isa_sem_loss_k_grad")
+                    self._k_grad(sem, labels, pixw, coef, dsem, acc)
                     acc = 1
                 L.check(E.lib.isa_lovasz_grad(sem.d(), L.ptr(gpix), L.ptr(scale), per_image, dsem, acc, E.st()),
                         "isa_lovasz_grad")

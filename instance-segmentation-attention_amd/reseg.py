@@ -192,11 +192,11 @@ class ReSeg(nn.Module):
         "CELovasz" add lovasz_softmax (losses/lovasz_losses.py:156-196) with its per_image / only_present options."""
         self.net.crit.set(criterion, class_weights, optimize_bg, lovasz_per_image, lovasz_only_present)
 
-    def sem_costs(self, sem_seg_target):
+    def sem_costs(self, sem_seg_target, ins=None):
         """Semantic criterion (set_criterion; default CE + Dice(time=1)) of the LAST forward's logits against a one-hot
         int64 target [B,K,H,W] (validation branch of model.py:244-270).  Returns a device tensor [ce, dice] (0 for a
         term the criterion lacks; [ce, 0, lovasz] for the Lovasz criteria); must be called before the next forward (the
-        logits live in that step's arena)."""
+        logits live in that step's arena).  ins: the batch's instance planes, needed when the border term is on."""
         sem = getattr(self, "_last_sem", None)
         assert sem is not None, "sem_costs() follows a forward()"
         t = sem_seg_target.to(self.store.device).contiguous()
@@ -204,7 +204,9 @@ class ReSeg(nn.Module):
         was = self.engine.record
         self.engine.record = False
         try:
-            return self.net.sem_loss(sem, t).clone()
+            if ins is not None:
+                ins = ins.to(self.store.device).contiguous()
+            return self.net.sem_loss(sem, t, None, ins).clone()
         finally:
             self.engine.record = was
 
@@ -565,6 +567,61 @@ class ReSeg(nn.Module):
             t = self._cc_map(labels, connectivity, min_area, max_objects)
             comp, _ = self.net.cc_label(t, connectivity)
             return self.net.cc_select(t, comp, L.CC_LARGEST if keep == 'largest' else L.CC_SPLIT, min_area, max_objects)
+
+    # ------------------------------------------------------------------ distance transform, border weights, instance fill
+    def _edt_map(self, labels):
+        t = labels.to(self.store.device).contiguous()
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise TypeError("expects a uint8 label map [B,H,W], got %s %s" % (t.dtype, tuple(t.shape)))
+        n, h, w = t.shape
+        if w % 4 or max(h, w) > L.EDT_MAX_SIDE or not 1 <= n <= 65535 or h < 1:
+            raise ValueError("labels [B,H,W]: W a multiple of 4, H and W at most %d, 1 <= B <= 65535; got %s"
+                             % (L.EDT_MAX_SIDE, tuple(t.shape)))
+        return t
+
+    def distance_transform(self, labels):
+        """(d1sq int32, d2sq int32, nearest uint8), each [B,H,W] on the device, of a uint8 label map [B,H,W] whose value 0
+        means no instance: the exact squared Euclidean distance of every pixel to the nearest instance of its image and
+        to the second-nearest one (equal to d1sq where two instances tie), and the smallest label at distance d1sq.
+        INT32_MAX / 0 where the image holds no instance, INT32_MAX in d2sq where it holds fewer than two.  Integers
+        only: the same tensors bit for bit on every run (isa_edt2_u8)."""
+        with torch.no_grad():
+            return self.net.distance_transform(self._edt_map(labels))
+
+    def border_weights(self, ins_or_labels, w0=10.0, sigma=5.0):
+        """The U-Net border weight map fp32 [B,H,W] on the device: 1 on instance pixels and where the image holds fewer than
+        two instances, 1 + w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) on the background, d1 and d2 the distances to the two nearest
+        instances.  ins_or_labels: instance planes in any form forward() takes (uint8 [B,H,W,K], int64 or fp32 [B,K,H,W]) or
+        a uint8 label map [B,H,W]."""
+        if float(w0) < 0 or not float(sigma) > 0:
+            raise ValueError("w0 must not be negative and sigma must be positive, got %r, %r" % (w0, sigma))
+        with torch.no_grad():
+            t = ins_or_labels
+            if t.dim() == 4:
+                n = t.shape[0]
+                h, w = (t.shape[1], t.shape[2]) if t.dtype == torch.uint8 else (t.shape[2], t.shape[3])
+                t = self._label_map(t, "ins_or_labels")[0].view(n, h, w)
+            t = self._edt_map(t)
+            cfg = torch.tensor([float(w0), float(sigma)], dtype=torch.float32, device=t.device)
+            return self.net.border_weights(t, cfg)
+
+    def fill_instances(self, labels, fg, max_dist=None):
+        """(labels uint8 [B,H,W], filled int32 [B]), on the device: every pixel of `labels` that is 0 while fg (uint8 or bool
+        [B,H,W], non-zero = foreground, such as class_map()) is set takes the label of the nearest instance of its image,
+        the smaller label on a tie (a Voronoi fill); with max_dist only when that instance lies within max_dist pixels.
+        Labelled pixels and the background stay as they are; filled counts the pixels given a label."""
+        if max_dist is not None and float(max_dist) < 0:
+            raise ValueError("max_dist must not be negative, got %r" % (max_dist,))
+        with torch.no_grad():
+            t = self._edt_map(labels)
+            f = fg.to(self.store.device)
+            if f.dtype == torch.bool:
+                f = f.to(torch.uint8)
+            f = f.contiguous()
+            if f.dtype != torch.uint8 or f.shape != t.shape:
+                raise TypeError("fg: uint8 or bool %s, got %s %s" % (tuple(t.shape), f.dtype, tuple(f.shape)))
+            bound = -1 if max_dist is None else int(min(float(max_dist) ** 2, 2 ** 31 - 1))
+            return self.net.fill_labels(t, f, bound)
 
     # ------------------------------------------------------------------ scoring semantic predictions on the device
     def _semantic_logits(self, x):

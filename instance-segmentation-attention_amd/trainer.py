@@ -33,14 +33,20 @@ class Trainer:
     def __init__(self, model, world_size=1, lr=1.0, weight_decay=1e-3, clip_grad_norm=10.0, rho=0.9, eps=1e-6,
                  criterion='Multi', class_weights=None, optimize_bg=False, optimizer='Adadelta', train_cnn=True,
                  lovasz_per_image=False, lovasz_only_present=False, disc_weight=0.0, delta_var=0.5, delta_dist=1.5,
-                 disc_norm=2, disc_form='reference'):
+                 disc_norm=2, disc_form='reference', border_weight=0.0, border_sigma=5.0):
         assert optimizer in OPTIMIZERS, optimizer
         self.model = model
         self.optimizer, self.train_cnn = optimizer, bool(train_cnn)
         # semantic criterion (model.py:102-133, 255-269): written once into the model's settings buffer, which was
         # allocated with the model - a captured step keeps reading the same device memory
+        # off first: an earlier Trainer's border term must not refuse this one's criterion.  (This resets a border term set
+        # directly on model.net.crit as well: like the criterion, the term is the Trainer's to set.)
+        model.net.crit.set_border(0.0)
         model.set_criterion(criterion, class_weights, optimize_bg, lovasz_per_image, lovasz_only_present)
         self.criterion = criterion
+        # the border term: the CE of every pixel weighted by the U-Net border map of the step's
+        # instance targets, computed on the device inside the step; 0 = off, and then nothing of it runs
+        model.net.crit.set_border(border_weight, border_sigma)
         # the discriminative loss on the instance embedding (DiscriminativeLoss(delta_var, delta_dist, norm), model.py:109-115):
         # runs when disc_weight > 0 and the model has an instance head; its settings live in a device buffer of the model
         model.net.disc.set(disc_weight, delta_var, delta_dist, disc_norm, disc_form)
@@ -103,6 +109,7 @@ class Trainer:
             E.packer.pack()
         m._weights_dirty = False
         labels = None
+        planes = ins                         # as given: the border term builds its label map from them
         if ins.dtype == torch.uint8:         # compact targets (uint8 planes [B,H,W,K] + uint8 map [B,H,W]): expand on device
             if net.crit.legacy:
                 sem, ins = net.collate_targets(sem, ins)
@@ -112,7 +119,7 @@ class Trainer:
         x_dec, feats = net.unet(xin)
         sem_a = net.sem_head(x_dec)
         m._last_sem = sem_a                  # the step's logits (arena view: read before the next step)
-        sem_scal = net.sem_loss(sem_a, sem, labels)
+        sem_scal = net.sem_loss(sem_a, sem, labels, planes)
         head_scal = None
         if m.use_instance_seg:
             n_ins = n_objects if isinstance(n_objects, list) else [int(v) for v in n_objects.reshape(-1).tolist()]
@@ -142,6 +149,11 @@ class Trainer:
         """A new weight (> 0) of the running discriminative loss, written in place into its device settings: a captured
         step follows without re-capture.  Switching the loss on or off is a new Trainer."""
         self.model.net.disc.set_weight(weight)
+
+    def set_border(self, weight, sigma=None):
+        """New values (weight > 0) of the running border term, written in place into its device settings: a captured step
+        follows without re-capture.  Switching the term on or off is a new Trainer."""
+        self.model.net.crit.set_border_values(weight, sigma)
 
     @property
     def class_weights(self):
@@ -220,6 +232,8 @@ class Trainer:
                # the Lovasz criteria have launches of their own (CELovasz three more than Lovasz), and per_image sets
                # their segment geometry
                m.net.crit.criterion if m.net.crit.lovasz else None, m.net.crit.lovasz and m.net.crit.lovasz_per_image,
+               # the border term: on / off adds launches and picks the pixel-weighted kernels; w0 and sigma do not
+               m.net.crit.border_key(),
                # the discriminative loss: on / off adds launches, form and norm pick kernels; weight and deltas do not
                m.net.disc.key() if m.use_instance_seg else None)
         disc_on = m.use_instance_seg and m.net.disc.on

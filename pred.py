@@ -11,6 +11,7 @@ map is materialised.  `--synthetic` predicts one random image when no file is at
 <name>-sem_mask_color.png as pred_list.py --n-classes does (ReSeg.class_map); -fg_mask.png is then class != 0.
 `--min-area`, `--keep`, `--connectivity` and `--components` are pred_list.py's: the clean-up of the `--instances` label
 map on the device, and the instance files from the connected components of the class map without an instance head.
+`--fill [--fill-max-dist D]` is pred_list.py's too: unlabelled foreground goes to the nearest instance after the clean-up.
 The reference's hard-coded checkpoint and image paths (pred.py:25-26,112) are flags here."""
 import argparse
 import os
@@ -23,15 +24,17 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import isa_amd  # noqa: F401,E402
 from isa_amd.model import Model  # noqa: E402
-from pred_list import (H, W, add_cleanup_arguments, add_embedding_arguments, check_cleanup_arguments,  # noqa: E402
-                       check_embedding_arguments, cleanup_arguments, nearest_upsample, write_classes, write_instances)
+from pred_list import (H, W, add_cleanup_arguments, add_embedding_arguments, add_fill_arguments,  # noqa: E402
+                       check_cleanup_arguments, check_embedding_arguments, check_fill_arguments, clean_and_fill,
+                       cleanup_arguments, fill_arguments, nearest_upsample, write_classes, write_instances)
 
 
 def predict_file(model, image, out_dir, name, instances=False, max_objects=32, clean=None, components=None,
-                 instances_from='attention', bandwidth=None):
+                 instances_from='attention', bandwidth=None, fill=None):
     """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask.  clean: ReSeg.clean_instances' keywords for the
     instance map; components: ReSeg.split_components' keywords - the instance files come from the class map's components;
-    instances_from='embedding': the instances are mean-shift clusters of the embedding (ReSeg.segment_embedding)."""
+    instances_from='embedding': the instances are mean-shift clusters of the embedding (ReSeg.segment_embedding); fill:
+    ReSeg.fill_instances' keywords - unlabelled foreground goes to the nearest instance after the clean-up."""
     from PIL import Image
     from isa_amd.data import resize_bilinear
     x = resize_bilinear(torch.from_numpy(image[None]), (H, W))  # uint8 [1,H,W,3] on the device, bit-identical to PIL's
@@ -52,8 +55,8 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32, c
                 _, sem_arg, labels, counts = net.segment_embedding(x, max_objects=min(max_objects, 32), bandwidth=bandwidth)
             else:
                 _, sem_arg, labels, counts = net.segment(x, max_objects)
-            if clean is not None:                              # at model resolution, before the nearest up-sampling
-                labels, counts, _ = net.clean_instances(labels, **clean)
+            # at model resolution, before the nearest up-sampling
+            labels, counts = clean_and_fill(net, labels, counts, clean, fill)
         else:
             _, sem_arg = net(False, x)                         # arg-max map == (softmax[:, 1] > 0.5)
             if components is not None:
@@ -86,6 +89,7 @@ def parse_args(argv=None):
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     add_cleanup_arguments(parser)
     add_embedding_arguments(parser)
+    add_fill_arguments(parser)
     opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
@@ -93,6 +97,7 @@ def parse_args(argv=None):
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     check_cleanup_arguments(parser, opt)
     check_embedding_arguments(parser, opt)
+    check_fill_arguments(parser, opt)
     return opt
 
 
@@ -111,7 +116,7 @@ def main():
     components = {'connectivity': opt.connectivity, 'min_area': opt.min_area, 'max_objects': opt.max_objects} \
         if opt.components else None
     path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects, cleanup_arguments(opt), components,
-                        opt.instances_from, opt.bandwidth)
+                        opt.instances_from, opt.bandwidth, fill_arguments(opt))
     print('wrote', path)
 
 

@@ -22,6 +22,8 @@ resolution and before the up-sampling (ReSeg.clean_instances: the largest connec
 piece as an object of its own; pieces under N pixels dropped).  `--components` needs no instance head: the connected
 components of the predicted class map (ReSeg.split_components; `--min-area`, `--connectivity`, `--max-objects` apply) are
 written as <name>-ins_mask.png, <name>-ins_mask_color.png and <name>-n_objects.npy - the count-the-blobs baseline.
+`--fill` gives, after that clean-up, every foreground pixel of the predicted class map that no instance holds to the
+nearest instance (ReSeg.fill_instances, on the device); `--fill-max-dist D` only within D pixels.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -89,6 +91,7 @@ def parse_args(argv=None):
                         'semantic-only model, also writes -sem_mask.png and -sem_mask_color.png')
     add_cleanup_arguments(parser)
     add_embedding_arguments(parser)
+    add_fill_arguments(parser)
     opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
@@ -96,6 +99,7 @@ def parse_args(argv=None):
         parser.error('--instances needs the 2-class model: a K-class network is semantic-only')
     check_cleanup_arguments(parser, opt)
     check_embedding_arguments(parser, opt)
+    check_fill_arguments(parser, opt)
     return opt
 
 
@@ -143,6 +147,36 @@ def check_cleanup_arguments(parser, opt):
         parser.error('--keep cleans the instances of --instances')
     if opt.min_area > 1 and not (opt.instances or opt.components):
         parser.error('--min-area needs --instances or --components')
+
+
+def add_fill_arguments(parser):
+    parser.add_argument('--fill', action='store_true', help='with --instances: after the clean-up, give every foreground '
+                        'pixel without an instance to the nearest instance')
+    parser.add_argument('--fill-max-dist', type=float, default=None, help='with --fill: only within this many pixels')
+
+
+def check_fill_arguments(parser, opt):
+    if opt.fill and not opt.instances:
+        parser.error('--fill fills the instances of --instances')
+    if opt.fill_max_dist is not None and not opt.fill:
+        parser.error('--fill-max-dist needs --fill')
+    if opt.fill_max_dist is not None and opt.fill_max_dist < 0:
+        parser.error('--fill-max-dist must not be negative')
+
+
+def fill_arguments(opt):
+    """ReSeg.fill_instances' keywords for the --instances label maps, or None without --fill."""
+    return {'max_dist': opt.fill_max_dist} if opt.fill else None
+
+
+def clean_and_fill(net, labels, counts, clean, fill):
+    """The --instances label maps after the clean-up (ReSeg.clean_instances' keywords, or None) and the fill against the
+    foreground of the predicted class map (ReSeg.fill_instances' keywords, or None): at model resolution, on the device."""
+    if clean is not None:
+        labels, counts, _ = net.clean_instances(labels, **clean)
+    if fill is not None:
+        labels, _ = net.fill_instances(labels, net.class_map(), **fill)
+    return labels, counts
 
 
 def cleanup_arguments(opt):
@@ -197,9 +231,8 @@ def main():
             classes = classes.cpu().numpy()
         elif opt.instances:
             sem_arg, labels, counts = segment_instances(net, x, opt)
-            clean = cleanup_arguments(opt)
-            if clean is not None:                        # at model resolution, before the nearest up-sampling
-                labels, counts, _ = net.clean_instances(labels, **clean)
+            # at model resolution, before the nearest up-sampling
+            labels, counts = clean_and_fill(net, labels, counts, cleanup_arguments(opt), fill_arguments(opt))
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         elif opt.components:
             with torch.no_grad():

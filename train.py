@@ -52,6 +52,10 @@ def build_parser():
     parser.add_argument('--disc-norm', type=int, default=2, choices=[1, 2], help='norm of the discriminative loss')
     parser.add_argument('--disc-form', default='reference', choices=['reference', 'full'],
                         help="'reference': var + 0.005 qreg on unit means; 'full': var + dist + 0.001 reg")
+    # the border term of the cross-entropy (U-Net weight map of the step's instance targets, on the device); off at weight 0
+    parser.add_argument('--border-weight', type=float, default=0.0, help='w0 of the border weight map 1 + w0 * '
+                        'exp(-(d1 + d2)^2 / (2 sigma^2)) on the cross-entropy of background pixels (0: off)')
+    parser.add_argument('--border-sigma', type=float, default=5.0, help='sigma of the border weight map, in pixels')
     parser.add_argument('--class-weights', default=None, help='one weight per class, comma separated (w0,w1,...)')
     parser.add_argument('--optimize-bg', action='store_true', help='Dice over every class, background included')
     parser.add_argument('--n-classes', type=int, default=2, help='semantic classes, 2..32 (more than 2 needs --semantic-only)')
@@ -86,6 +90,10 @@ def parse_args(argv=None):
         parser.error('--n-classes must be in [2, 32]')
     if opt.n_classes > 2 and not opt.semantic_only:
         parser.error('--n-classes > 2 needs --semantic-only: the instance head reads a foreground / background mask')
+    if opt.border_weight < 0 or not opt.border_sigma > 0:
+        parser.error('--border-weight must not be negative and --border-sigma must be positive')
+    if opt.border_weight > 0 and opt.criterion == 'Lovasz':
+        parser.error('--border-weight weighs the cross-entropy: --criterion Lovasz has none (use CELovasz)')
     if opt.class_weights is not None:
         try:
             opt.class_weights = [float(v) for v in opt.class_weights.split(',')]
@@ -100,6 +108,12 @@ def fit_arguments(opt):
     """Model.fit's arguments ahead of the loaders, as the reference's train.py passes them (training_settings.py)."""
     return (opt.criterion, opt.delta_var, opt.delta_dist, opt.disc_norm, opt.lr, opt.weight_decay, 10.0, 0.5, 25, opt.optimize_bg, opt.optimizer,
             not opt.freeze_cnn, opt.nepochs, opt.class_weights)
+
+
+def fit_keywords(opt):
+    """Model.fit's keyword arguments: the discriminative loss and the border term."""
+    return dict(disc_weight=opt.disc_weight, disc_form=opt.disc_form, border_weight=opt.border_weight,
+                border_sigma=opt.border_sigma)
 
 
 def photometric_arguments(opt):
@@ -137,8 +151,7 @@ def main(argv=None):
                                     mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt))
         test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
                                    mode='test', seed=SEED, rank=rank, world=world)
-    model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug, disc_weight=opt.disc_weight,
-              disc_form=opt.disc_form)
+    model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug, **fit_keywords(opt))
     if world > 1:
         torch.distributed.destroy_process_group()
 
