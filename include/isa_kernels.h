@@ -941,6 +941,43 @@ typedef struct {
 int isa_photometric_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, const isa_photo_prog* progs_dev,
                        int32_t has_contrast, int64_t* sums_ws, void* stream);
 
+/* ---- elastic deformation: a smooth random displacement field and the warp of uint8 tensors by a field ------------------
+ * (Simard, Steinkraus & Platt 2003; the companion of the border weight map in Ronneberger et al. 2015.)  Both entries
+ * check every argument before they launch or write anything (ISA_EINVAL / ISA_EALIGN / ISA_ENOMEM), are asynchronous on
+ * `stream`, allocate nothing and never synchronise.  n in 1..65535, h and w in 1..ISA_WARP_MAX_SIDE.
+ * isa_elastic_field: noise fp32 [n,h,w,2] (8-byte aligned) with values in [-1, 1) ->
+ *     disp[b,y,x,k] = alpha_dev[b] * G(noise)[b,y,x,k]      (fp32 [n,h,w,2], 8-byte aligned; it must not overlap noise)
+ *   G is a separable Gaussian blur along x and then along y with zeros outside the image (scipy's mode='constant', cval=0).
+ *   Component 0 is dx (along columns), component 1 is dy (along rows).  taps_host: the 2*radius+1 fp32 weights, on the HOST;
+ *   the call reads them before it returns and hands them to the kernels by value.  radius in 0..ISA_ELASTIC_MAX_RADIUS;
+ *   radius == 0: disp = alpha * noise.  alpha_dev: device fp32 [n], 4-byte aligned; an image with alpha 0 gets an all-zero
+ *   field.
+ *   scratch: ISA_ELASTIC_SCRATCH_BYTES(n,h,w) bytes, 16-byte aligned, need not be cleared, apart from noise and disp.
+ *   Two launches: one workgroup per image row (the row and its zeroed halo in LDS), then one workgroup per 64 columns x
+ *   32 rows that slides over the rows it taps in 32-row LDS chunks and scales by alpha.  fp32, taps added in ascending
+ *   order, no atomics: two runs give the same bits.
+ * isa_warp_u8: dst[b,y,x,:] = src uint8 [n,h,w,c] sampled at (x + disp[b,y,x,0], y + disp[b,y,x,1]), coordinates clamped to
+ *   the image (replicate border).  c in 1..ISA_WARP_MAX_CHANNELS; src and dst 4-byte aligned, disp 8-byte aligned; dst may
+ *   overlap neither src nor disp.  The arithmetic is integers after one rounding.  For each component d of disp:
+ *     1. NaN becomes 0, then d is clamped to [-16384, 16384] (+-Inf end there);
+ *     2. q = x * 256 + (int)rintf(d * 256.0f) in int32 (the product is exact, rintf rounds half to even); likewise for y;
+ *     3. ISA_WARP_NEAREST: xs = clamp((qx + 128) >> 8, 0, w-1), likewise ys (arithmetic shifts); dst = src[ys, xs];
+ *     4. ISA_WARP_BILINEAR: x0 = qx >> 8, fx = qx & 255, likewise y; taps (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1), every
+ *        index clamped into the image on its own, weights (256-fx)(256-fy), fx(256-fy), (256-fx)fy, fx*fy;
+ *        dst = (sum + 32768) >> 16.
+ *   One launch: c == 32 a lane per pixel and 16-byte channel group, c <= 4 a lane per pixel, otherwise a lane per byte. */
+#define ISA_ELASTIC_MAX_RADIUS 64
+#define ISA_WARP_MAX_SIDE 1024
+#define ISA_WARP_MAX_CHANNELS 64
+#define ISA_WARP_NEAREST 0
+#define ISA_WARP_BILINEAR 1
+#define ISA_ELASTIC_SCRATCH_BYTES(n, h, w) ((int64_t)(n) * (h) * (w) * 8)
+int isa_elastic_field(const float* noise, const float* alpha_dev, int32_t n, int32_t h, int32_t w,
+                      const float* taps_host, int32_t radius, float* disp,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+int isa_warp_u8(const uint8_t* src, const float* disp, int32_t n, int32_t h, int32_t w, int32_t c,
+                int32_t mode, uint8_t* dst, void* stream);
+
 /* ---- boundary layout converters (the reference passes NCHW fp32: reseg.py:106-110) -----------
  * nchw_to_nhwc: channels [csrc, c) are written as 0; bf16 stores round to nearest even.  Channels at or above c: a dst
  * with ld == rup(c, 8) <= 32, 16-byte aligned src and data and h*w % 4 == 0 is written in whole padded rows (channels

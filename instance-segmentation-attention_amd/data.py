@@ -367,6 +367,113 @@ def photometric(rgb, programs, device="cuda", out=None):
     return dst
 
 
+# ---- elastic deformation (Simard et al. 2003): not in the reference; the arithmetic is defined in include/isa_kernels.h
+# and DESIGN.md section 18 ----------------------------------------------------------------------------------------------
+def gaussian_taps(sigma, truncate=4.0):
+    """The weights of scipy.ndimage.gaussian_filter1d(sigma, truncate=truncate): radius = int(truncate * sigma + 0.5),
+    exp(-0.5 (k / sigma)^2) for k = -radius..radius, normalised in double, rounded to float32.  Returns (taps, radius)."""
+    import numpy as np
+    from . import lib as L
+    sigma = float(sigma)
+    assert sigma >= 0 and truncate >= 0
+    radius = int(truncate * sigma + 0.5)
+    assert radius <= L.ELASTIC_MAX_RADIUS, "radius %d of sigma %g exceeds ISA_ELASTIC_MAX_RADIUS" % (radius, sigma)
+    if radius == 0:
+        return np.ones(1, np.float32), 0
+    k = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return (phi / phi.sum()).astype(np.float32), radius
+
+
+def elastic_field(noise, alpha, sigma, device="cuda"):
+    """The displacement field of an elastic deformation on the device (isa_elastic_field): noise fp32 [n,h,w,2] in
+    [-1, 1) -> disp fp32 [n,h,w,2] = alpha[b] * (Gaussian blur of the noise, sigma pixels, truncated at 4 sigma, zeros
+    outside the image).  Component 0 is dx, component 1 is dy.  alpha: a scalar, a sequence of n or a device tensor [n]."""
+    import ctypes as C
+    from . import lib as L
+    src = noise.to(device).contiguous()
+    assert src.dtype == torch.float32 and src.dim() == 4 and src.shape[3] == 2, "fp32 [n,h,w,2]"
+    n, h, w, _ = src.shape
+    if torch.is_tensor(alpha):
+        a = alpha.to(device=src.device, dtype=torch.float32).reshape(-1).contiguous()
+    else:
+        a = torch.as_tensor(alpha, dtype=torch.float32).reshape(-1).to(src.device)
+    if a.numel() == 1 and n > 1:
+        a = a.repeat(n)
+    assert a.numel() == n, (a.numel(), n)
+    taps, radius = gaussian_taps(sigma)
+    disp = torch.empty_like(src)
+    scratch = torch.empty(L.elastic_scratch_bytes(n, h, w), dtype=torch.uint8, device=src.device)
+    L.check(L.lib().isa_elastic_field(L.ptr(src), L.ptr(a), n, h, w, taps.ctypes.data_as(C.c_void_p), radius, L.ptr(disp),
+                                      L.ptr(scratch), scratch.numel(), L.stream_ptr()), "isa_elastic_field")
+    return disp
+
+
+def warp(tensors, disp, modes, device="cuda"):
+    """uint8 tensors [n,h,w,c] or [n,h,w] sampled at (x + disp[...,0], y + disp[...,1]) on the device (isa_warp_u8), any
+    displacement field fp32 [n,h,w,2]; modes: one of 'nearest' / 'bilinear' (or lib.WARP_*) per tensor.  Coordinates are
+    clamped to the image (replicate border).  Returns new tensors of the inputs' shapes."""
+    from . import lib as L
+    names = dict(nearest=L.WARP_NEAREST, bilinear=L.WARP_BILINEAR)
+    tensors, modes = list(tensors), [names.get(m, m) for m in modes]
+    assert len(tensors) == len(modes)
+    d = disp.to(device).contiguous()
+    assert d.dtype == torch.float32 and d.dim() == 4 and d.shape[3] == 2, "fp32 [n,h,w,2]"
+    out = []
+    for t, mode in zip(tensors, modes):
+        assert t.dtype == torch.uint8 and t.dim() in (3, 4), "uint8 [n,h,w(,c)]"
+        src = t.to(device).contiguous()
+        assert tuple(src.shape[:3]) == tuple(d.shape[:3]), (tuple(src.shape), tuple(d.shape))
+        n, h, w = src.shape[:3]
+        dst = torch.empty_like(src)
+        L.check(L.lib().isa_warp_u8(L.ptr(src), L.ptr(d), n, h, w, 1 if t.dim() == 3 else t.shape[3], int(mode), L.ptr(dst),
+                                    L.stream_ptr()), "isa_warp_u8")
+        out.append(dst)
+    return out
+
+
+def elastic(rgb, sem, planes, n_objects, disp, max_planes=32, device="cuda"):
+    """The loader's elastic stage for a batch: rgb uint8 [n,h,w,3] warped bilinear, sem uint8 [n,h,w(,1)] and planes
+    uint8 [n,h,w,K] warped nearest, all by the same field disp fp32 [n,h,w,2].  n_objects: the real planes per image (an
+    int, a sequence or a tensor).  An image in which the warp left one of its real planes without a pixel has those planes
+    dropped and the survivors compacted to the front, zero planes behind them (isa_plane_sums_u8, isa_crop_planes_u8, as
+    the centre cut does); an image that would keep no plane is returned unwarped with its count unchanged.  Returns
+    (rgb, sem, planes [n,h,w,max_planes], n_objects as a list)."""
+    from . import lib as L
+    lib, st = L.lib(), L.stream_ptr()
+    n, h, w, K = planes.shape
+    if torch.is_tensor(n_objects):
+        n_objects = n_objects.reshape(-1).tolist()
+    counts = [int(n_objects)] * n if isinstance(n_objects, int) else [int(v) for v in n_objects]
+    assert len(counts) == n and all(0 <= k <= K for k in counts), (counts, n, K)
+    rgb2, sem2, p2 = warp([rgb, sem, planes], disp, ["bilinear", "nearest", "nearest"], device)
+    if K != max_planes:                                  # the hand-over has max_planes planes (zero planes behind the real ones)
+        full = torch.zeros((n, h, w, max_planes), dtype=torch.uint8, device=p2.device)
+        full[..., :min(K, max_planes)] = p2[..., :max_planes]
+        p2, K = full, max_planes
+        counts = [min(k, K) for k in counts]
+    sums = torch.zeros((n, K), dtype=torch.int64, device=p2.device)
+    L.check(lib.isa_plane_sums_u8(L.ptr(p2), n, h, w, K, 0, 0, h, w, L.ptr(sums), st), "isa_plane_sums_u8")
+    sums = sums.cpu().tolist()
+    out_counts = list(counts)
+    for b in range(n):
+        keep = [i for i in range(counts[b]) if sums[b][i] > 0]
+        if len(keep) == counts[b]:
+            continue
+        if not keep:                                     # nothing would be left: this image stays as it was
+            rgb2[b], sem2[b] = rgb[b].to(p2.device), sem[b].to(p2.device)
+            p2[b].zero_()
+            p2[b, :, :, :min(planes.shape[3], K)] = planes[b, :, :, :K].to(p2.device)
+            continue
+        chan = torch.tensor(keep + [-1] * (K - len(keep)), dtype=torch.int32, device=p2.device)
+        packed = torch.empty((1, h, w, K), dtype=torch.uint8, device=p2.device)
+        L.check(lib.isa_crop_planes_u8(L.ptr(p2[b]), 1, h, w, K, 0, 0, L.ptr(packed), h, w, K, L.ptr(chan), st),
+                "isa_crop_planes_u8")
+        p2[b] = packed[0]
+        out_counts[b] = len(keep)
+    return rgb2, sem2, p2, out_counts
+
+
 class DevicePrefetcher(object):
     """Wraps an iterable of collated host batches (x, sem, ins, n): batch i+1 travels to the device on its own HIP
     stream while step i computes, so the host-to-device time of the reference's hand-over (373 MB per step at bs=16:

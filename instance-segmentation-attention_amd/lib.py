@@ -47,6 +47,15 @@ def edt_scratch_bytes(n, h, w):
     return n * h * w * 8
 
 
+ELASTIC_MAX_RADIUS, WARP_MAX_SIDE, WARP_MAX_CHANNELS = 64, 1024, 64      # ISA_ELASTIC_MAX_RADIUS, ISA_WARP_MAX_*
+WARP_NEAREST, WARP_BILINEAR = 0, 1
+
+
+def elastic_scratch_bytes(n, h, w):
+    """ISA_ELASTIC_SCRATCH_BYTES: the row-blurred noise between the two passes of isa_elastic_field."""
+    return n * h * w * 8
+
+
 DISC_MAX_K, DISC_CFG_FLOATS, DISC_CNT_STRIDE, ROW_CHUNKS = 32, 12, 36, 64     # ISA_DISC_*, ISA_ROW_CHUNKS
 
 
@@ -238,6 +247,9 @@ SIGNATURES = {
     "isa_edt2_u8": [VP, I32, I32, I32, VP, VP, VP, VP, I64, VP],
     "isa_border_weights": [VP, VP, VP, VP, I32, I64, VP, VP],
     "isa_fill_labels": [VP, VP, VP, VP, I32, I32, I64, VP, VP, VP],
+    # elastic deformation (data.elastic_field, data.warp, data.elastic; RecordLoader(elastic=True))
+    "isa_elastic_field": [VP, VP, I32, I32, I32, VP, I32, VP, VP, I64, VP],
+    "isa_warp_u8": [VP, VP, I32, I32, I32, I32, I32, VP, VP],
 }
 
 

@@ -118,11 +118,22 @@ class RecordLoader(object):
     Like the reference's DataLoader + AlignCollate no sample is dropped: a short last batch is filled by repeating its
     first image (dataset.py:330-333).  With world > 1 the permutation is padded (wrapping around) to a multiple of
     `world` before it is dealt out, so every rank runs the same number of steps - a rank with a step more than the
-    others would wait in its gradient all-reduce forever."""
+    others would wait in its gradient all-reduce forever.
+
+    elastic=True (training mode only; not in the reference) deforms image and annotation together by a smooth random
+    displacement field (Simard et al. 2003; `data.elastic_field`, `data.elastic`).  The stage runs once per batch, after the
+    samples have been resized and concatenated, at the network's resolution on [B,h,w,*]: one field (two launches) and
+    three warps per batch instead of per-sample launches at every sample's own size.  The price is a second interpolation
+    of the image after the resize.  Its draws come from generators of the stage's own, seeded from (seed, epoch, rank):
+    per image u = random() and a = uniform(*elastic_alpha), alpha = a if u < elastic_p else 0 (both are always drawn);
+    per batch torch.rand((B,h,w,2)) * 2 - 1 on the device.  The loader's other generators are not touched, so every other
+    draw is the same with the flag on or off.  The defaults are a stated choice, not a tuned one: at sigma 8 the field's
+    standard deviation is about alpha / 50 pixels, so alpha 100 moves a pixel by roughly 2."""
 
     def __init__(self, dataset, batch_size, height=256, width=256, max_n_objects=32, mode='test', seed=0, device='cuda',
                  rank=0, world=1, d4=True, rotation=True, center_cut=True, color_jitter=False, gamma=False,
-                 channel_swap=False, grayscale=False, resolution=False):
+                 channel_swap=False, grayscale=False, resolution=False, elastic=False, elastic_alpha=(0.0, 100.0),
+                 elastic_sigma=8.0, elastic_p=0.5):
         assert mode in ('training', 'test')
         self.ds, self.bs, self.h, self.w, self.k, self.mode = dataset, batch_size, height, width, max_n_objects, mode
         self.seed, self.epoch, self.device, self.rank, self.world = seed, 0, device, rank, world
@@ -131,8 +142,13 @@ class RecordLoader(object):
         # random_channel_swapping, random_grayscaling, random_resolution); off: no draw is made for them
         self.color_jitter, self.gamma, self.channel_swap, self.grayscale = color_jitter, gamma, channel_swap, grayscale
         self.resolution = resolution
+        # elastic deformation (see the class docstring); off: no draw is made and nothing is allocated for it
+        self.elastic, self.elastic_alpha = elastic, tuple(elastic_alpha)
+        self.elastic_sigma, self.elastic_p = elastic_sigma, elastic_p
+        assert len(self.elastic_alpha) == 2 and 0.0 <= elastic_p <= 1.0
+        self.last_field = None                                           # disp fp32 [B,h,w,2] of the last batch, on the device
         # per image of the last batch: dict(op, angle, bg_key, pick) and, for the flags that are on, ratio / jitter (the
-        # four (name, factor) in shuffled order) / gamma / channels (None: no swap) / gray - tests / logging
+        # four (name, factor) in shuffled order) / gamma / channels (None: no swap) / gray / elastic_alpha - tests / logging
         self.last_draws = []
 
     def indices(self):
@@ -227,9 +243,25 @@ class RecordLoader(object):
         idx = self.indices()
         py_rng = random.Random(1000003 * self.seed + self.epoch + 7919 * self.rank)
         np_rng = np.random.RandomState((1000003 * self.seed + self.epoch + 7919 * self.rank) % (2 ** 32))
+        elastic = self.elastic and self.mode == 'training'
+        if elastic:                                                      # generators of the stage's own (another constant)
+            el_seed = 2000003 * self.seed + self.epoch + 7919 * self.rank + 104729
+            el_rng, el_gen = random.Random(el_seed), torch.Generator(device=self.device)
+            el_gen.manual_seed(el_seed % (2 ** 63))
         for s in range(0, len(idx), self.bs):
             chunk = idx[s:s + self.bs]
             chunk = chunk + [chunk[0]] * (self.bs - len(chunk))         # dataset.py:330-333: repeat the batch's first image
             self.last_draws = []
             rgbs, sems, inss, ns = zip(*(self._one(i, py_rng, np_rng) for i in chunk))
-            yield torch.cat(rgbs), torch.cat(sems), torch.cat(inss), torch.tensor(ns, dtype=torch.int32)
+            rgb, sem, ins = torch.cat(rgbs), torch.cat(sems), torch.cat(inss)
+            if elastic:
+                from . import data as D
+                alphas = []
+                for draws in self.last_draws:
+                    u, a = el_rng.random(), el_rng.uniform(*self.elastic_alpha)
+                    draws["elastic_alpha"] = a if u < self.elastic_p else 0.0
+                    alphas.append(draws["elastic_alpha"])
+                noise = torch.rand((len(chunk), self.h, self.w, 2), generator=el_gen, device=self.device) * 2 - 1
+                self.last_field = D.elastic_field(noise, alphas, self.elastic_sigma, self.device)
+                rgb, sem, ins, ns = D.elastic(rgb, sem, ins, ns, self.last_field, self.k, self.device)
+            yield rgb, sem, ins, torch.tensor(ns, dtype=torch.int32)

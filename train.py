@@ -78,6 +78,13 @@ def build_parser():
     parser.add_argument('--channel-swap', action='store_true', help='random channel map, with probability 0.5')
     parser.add_argument('--grayscale', action='store_true', help='grayscale with probability 0.3')
     parser.add_argument('--resolution', action='store_true', help='Lanczos resize by a ratio in [0.7, 1.3] and back')
+    # elastic deformation of image and annotation together (not in the reference; RecordLoader(elastic=True)): for the
+    # training loader of --data only.  The defaults are a stated choice, not a tuned one
+    parser.add_argument('--elastic', action='store_true', help='smooth random elastic deformation, once per batch')
+    parser.add_argument('--elastic-alpha', type=float, nargs=2, default=[0.0, 100.0], metavar=('LO', 'HI'),
+                        help='the field is alpha * (blurred noise in [-1, 1)), alpha uniform in [LO, HI] per image')
+    parser.add_argument('--elastic-sigma', type=float, default=8.0, help='sigma of the Gaussian blur of the field, in pixels')
+    parser.add_argument('--elastic-p', type=float, default=0.5, help='probability that an image is deformed')
     return parser
 
 
@@ -94,6 +101,9 @@ def parse_args(argv=None):
         parser.error('--border-weight must not be negative and --border-sigma must be positive')
     if opt.border_weight > 0 and opt.criterion == 'Lovasz':
         parser.error('--border-weight weighs the cross-entropy: --criterion Lovasz has none (use CELovasz)')
+    if not (opt.elastic_alpha[0] <= opt.elastic_alpha[1] and 0.0 <= opt.elastic_p <= 1.0 and 0.0 <= opt.elastic_sigma <= 16.0):
+        parser.error('--elastic-alpha LO HI needs LO <= HI, --elastic-p a probability and --elastic-sigma at most 16 '
+                     '(a blur radius of 64 pixels)')
     if opt.class_weights is not None:
         try:
             opt.class_weights = [float(v) for v in opt.class_weights.split(',')]
@@ -122,6 +132,12 @@ def photometric_arguments(opt):
                 resolution=opt.resolution)
 
 
+def elastic_arguments(opt):
+    """RecordLoader's elastic-deformation arguments: the training loader's alone."""
+    return dict(elastic=opt.elastic, elastic_alpha=tuple(opt.elastic_alpha), elastic_sigma=opt.elastic_sigma,
+                elastic_p=opt.elastic_p)
+
+
 def main(argv=None):
     opt = parse_args(argv)
     import isa_amd  # noqa: F401
@@ -148,7 +164,8 @@ def main(argv=None):
     if opt.data:                      # the reference's datasets (train.py:87-147): records -> device-side collate
         from isa_amd.records import RecordDataset, RecordLoader
         train_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'training-lmdb')), per_rank, opt.size, opt.size,
-                                    mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt))
+                                    mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt),
+                                    **elastic_arguments(opt))
         test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
                                    mode='test', seed=SEED, rank=rank, world=world)
     model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug, **fit_keywords(opt))
