@@ -803,12 +803,19 @@ int isa_sdp_scores(const void* q, const void* k, float* out, int32_t b, int32_t 
  * query rows, fc + layer_norm on the attended rows, utils.py:189-201).  fp32, n <= 64; gamma == NULL: no LayerNorm. */
 int isa_linear_ln(const float* x, const float* w, const float* bias, const float* residual, const float* gamma,
                   const float* beta, float eps, int32_t rows, int32_t k, int32_t n, float* y, void* stream);
-/* out = InstanceNorm2d(x + res) (utils.py:301-302: affine=False, biased variance); sums: zeroed float[n][2c]. */
+/* out = InstanceNorm2d(x + res) (utils.py:301-302: affine=False, biased variance); sums: zeroed float[n][2c].
+ * x, res, out: the same n, h, w, c (c <= 64) and dtype.  Two statistics passes over the values minus the (image,
+ * channel)'s first one: sums[b][0..c) receives their sum, sums[b][c..2c) the sum of their squared distances from their
+ * mean, so a channel offset costs no digits of the variance. */
 int isa_instance_norm_res(const isa_tensor* x, const isa_tensor* res, const isa_tensor* out, float eps, float* sums,
                           void* stream);
-/* a20 _ScalePDAttention core (utils.py:276-299): per-pixel softmax over the 3x3 neighbourhood at `dilation` */
+/* a20 _ScalePDAttention core (utils.py:276-299): per-pixel softmax over the 3x3 neighbourhood at `dilation`.
+ * q, k [n,h,w,dk], v, out [n,h,w,dv] (the same n, h, w and dtype; dk, dv <= 32); nomask: fp32 [n, h*w], values in
+ * {0, 1}, non-zero = masked key.  `scale` multiplies the logits <q, k>; finite and > 0.  The reference's is c^-1/2 with
+ * c the per-head INPUT width d_model / n_head (utils.py:273,293: `c` is read off qk after the head view), which equals
+ * d_k^-1/2 only where d_model / n_head == d_k. */
 int isa_local_attention(const isa_tensor* q, const isa_tensor* k, const isa_tensor* v, const float* nomask,
-                        const isa_tensor* out, int32_t dilation, void* stream);
+                        const isa_tensor* out, int32_t dilation, float scale, void* stream);
 /* a21 Decoder.forward (utils.py:59-69): out[b,p] = sigmoid(<q[b,:], enc[b,p,:]>) */
 int isa_point_query(const float* q, const isa_tensor* enc, float* out, void* stream);
 

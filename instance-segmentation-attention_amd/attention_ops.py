@@ -185,14 +185,18 @@ def _pad_nhwc(t, dtype):
     return Act(buf, 0, c)
 
 
-def local_dilated_attention(Q, K, V, nomask, dilation, dtype=torch.float32):
-    """Core of _ScalePDAttention.forward (utils.py:276-299) after the 1x1 projections.  NCHW in/out."""
+def local_dilated_attention(Q, K, V, nomask, dilation, dtype=torch.float32, scale=None):
+    """Core of _ScalePDAttention.forward (utils.py:276-299) after the 1x1 projections.  NCHW in/out.
+    Q,K[B,dk,H,W], V[B,dv,H,W]; nomask[B,1,H,W] with values in {0, 1}, 1 = masked key (the reference's `.byte()`
+    truncates anything else).  scale: factor on the logits; None means d_k ** -0.5, which equals the reference's
+    c ** -0.5 (c = d_model // n_head, utils.py:273,293) only where c == d_k."""
     qa, ka, va = _nhwc(Q, dtype), _nhwc(K, dtype), _nhwc(V, dtype)
     n, dv, h, w = V.shape
+    scale = Q.shape[1] ** -0.5 if scale is None else scale
     out = Act(torch.empty(n, h, w, (dv + 7) // 8 * 8, dtype=dtype, device=V.device), 0, dv)
     nm = nomask.reshape(n, -1).float().contiguous()
-    L.check(L.lib().isa_local_attention(qa.d(), ka.d(), va.d(), L.ptr(nm), out.d(), int(dilation), L.stream_ptr()),
-            "isa_local_attention")
+    L.check(L.lib().isa_local_attention(qa.d(), ka.d(), va.d(), L.ptr(nm), out.d(), int(dilation), float(scale),
+                                        L.stream_ptr()), "isa_local_attention")
     return out.nchw()
 
 
@@ -200,7 +204,9 @@ class ScalePDAttention(nn.Module):
     """_ScalePDAttention (utils.py:248-303): local 3x3-dilated attention with its projections.  forward(qk[b,d_model,h,w],
     v[b,d_model,h,w], nomask[b,1,h,w]) -> InstanceNorm2d(fc(attended) + qk).  The per-head 1x1 convolutions (the
     reference views the batch as b*n_head images of d_model/n_head channels) run as ONE block-diagonal 1x1 convolution
-    over the d_model channels, so every head reads an aligned NHWC tensor."""
+    over the d_model channels, so every head reads an aligned NHWC tensor.  The logits are scaled by
+    (d_model // n_head) ** -0.5 like the reference's (`c` of utils.py:273,293 is the per-head input width, not d_k);
+    nomask holds {0, 1}, 1 = masked key (the reference's `.byte()` truncates anything else)."""
 
     def __init__(self, d_k, d_v, d_model, dilation_rate, n_head=2, dtype=torch.float32):
         super().__init__()
@@ -245,7 +251,7 @@ class ScalePDAttention(nn.Module):
             nmg = nm[idx].contiguous()
             L.check(L.lib().isa_local_attention(QK.slice(g * 2 * dk, dk).d(), QK.slice(g * 2 * dk + dk, dk).d(),
                                                 V.slice(g * dv, dv).d(), L.ptr(nmg), att.slice(g * dv, dv).d(), int(self.d),
-                                                L.stream_ptr()), "isa_local_attention")
+                                                float(cin) ** -0.5, L.stream_ptr()), "isa_local_attention")
         out = H.conv(att, "fc.weight", "fc.bias", dm)
         y = H.engine.new_act(b, h, w, dm)
         sums = torch.zeros(b * 2 * dm, dtype=torch.float32, device=dev)

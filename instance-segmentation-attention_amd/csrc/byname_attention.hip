@@ -14,6 +14,7 @@
 // d != 12, heads = 1), which the reference's configuration (config.py:22-25) never produces; it is reached through the
 // same entry point and covered by the d = 16 / 32 cases of tests/test_gpu_byname.py.
 #include "common.hpp"
+#include <cfloat>
 
 typedef _Float16 f16_t;
 template <> struct st<f16_t> {
@@ -418,45 +419,52 @@ __global__ __launch_bounds__(64) void linear_ln_kernel(const float* x, const flo
     if (n < N) y[(long)r * N + n] = acc;
 }
 
-// InstanceNorm2d(out + residual) of _ScalePDAttention (utils.py:301-302; affine=False, biased variance, eps 1e-5)
-template <typename T>
+// InstanceNorm2d(out + residual) of _ScalePDAttention (utils.py:301-302; affine=False, biased variance, eps 1e-5).
+// Two statistics passes over d = v - v0, v0 = the (image, channel)'s value at its first pixel: PASS 0 adds sum(d) to
+// sums[b][ch], PASS 1 reads m = sum(d) / hw and adds sum((d - m)^2) to sums[b][c + ch].  The one-pass E[v^2] - E[v]^2 this
+// replaces cancels mean^2 / var of the fp32 digits: with a channel offset of 16 over a variance of 2 it was 1e-5 to 4e-5
+// of the largest element away from float64 (float32 emulation of its sums), this form 2e-7 to 4e-7 with or without.
+template <typename T, int PASS>
 __global__ __launch_bounds__(256) void inorm_stats_kernel(const T* x, int ldx, const T* res, int ldr, int c, long hw, float* sums) {
     const int b = blockIdx.y;
-    extern __shared__ float red[];                                   // [2c]
-    for (int i = threadIdx.x; i < 2 * c; i += 256) red[i] = 0.f;
+    extern __shared__ float red[];                                   // [c]
+    for (int i = threadIdx.x; i < c; i += 256) red[i] = 0.f;
     __syncthreads();
     const int lanes_c = c;                                           // c <= 64
     const int rows = 256 / lanes_c, ch = threadIdx.x % lanes_c, rsub = threadIdx.x / lanes_c;
     if (rsub < rows) {
-        float s1 = 0.f, s2 = 0.f;
+        const float v0 = st<T>::ld(x + (b * hw) * ldx + ch) + st<T>::ld(res + (b * hw) * ldr + ch);
+        const float m = PASS ? sums[(long)b * 2 * c + ch] / hw : 0.f;
+        float acc = 0.f;
         for (long pix = (long)blockIdx.x * rows + rsub; pix < hw; pix += (long)gridDim.x * rows) {
-            const float v = st<T>::ld(x + (b * hw + pix) * ldx + ch) + st<T>::ld(res + (b * hw + pix) * ldr + ch);
-            s1 += v; s2 += v * v;
+            const float d = st<T>::ld(x + (b * hw + pix) * ldx + ch) + st<T>::ld(res + (b * hw + pix) * ldr + ch) - v0;
+            acc += PASS ? (d - m) * (d - m) : d;
         }
-        atomicAdd(&red[ch], s1); atomicAdd(&red[c + ch], s2);
+        atomicAdd(&red[ch], acc);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 2 * c; i += 256) atomicAdd(sums + (long)b * 2 * c + i, red[i]);
+    for (int i = threadIdx.x; i < c; i += 256) atomicAdd(sums + (long)b * 2 * c + PASS * c + i, red[i]);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void inorm_apply_kernel(const T* x, int ldx, const T* res, int ldr, int c, long hw, const float* sums,
                                                           float eps, T* out, int ldo, long total) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int ch = (int)(i % c); const long pix = i / c; const long b = pix / hw;
-        const float mean = sums[b * 2 * c + ch] / hw;
-        const float var = fmaxf(sums[b * 2 * c + c + ch] / hw - mean * mean, 0.f);
-        const float v = st<T>::ld(x + pix * ldx + ch) + st<T>::ld(res + pix * ldr + ch);
-        st<T>::stv(out + pix * ldo + ch, (v - mean) * rsqrtf(var + eps));
+        const float v0 = st<T>::ld(x + (b * hw) * ldx + ch) + st<T>::ld(res + (b * hw) * ldr + ch);     // the shift of the sums
+        const float m = sums[b * 2 * c + ch] / hw;                                                       // mean of v - v0
+        const float var = sums[b * 2 * c + c + ch] / hw;                                                 // of centred squares: >= 0
+        const float d = st<T>::ld(x + pix * ldx + ch) + st<T>::ld(res + pix * ldr + ch) - v0;
+        st<T>::stv(out + pix * ldo + ch, (d - m) / sqrtf(var + eps));
     }
 }
 
 // a20: local dilated attention on NHWC tensors.  q,k: [n,h,w,dk]  v: [n,h,w,dv]  nomask: fp32 [n,h*w]
 struct LocalParams { const void* q; const void* k; const void* v; const float* nomask; void* out;
-                     int n, h, w, dk, dv, ldq, ldk, ldv, ldo, d; };
+                     int n, h, w, dk, dv, ldq, ldk, ldv, ldo, d; float scale; };
 template <typename T>
 __global__ __launch_bounds__(256) void local_attn_kernel(LocalParams p) {
     const long pixels = (long)p.n * p.h * p.w;
-    const float scale = rsqrtf((float)p.dk);
+    const float scale = p.scale;     // the caller's: the reference's is c^-1/2 of the per-head INPUT width (utils.py:273,293)
     for (long pix = (long)blockIdx.x * 256 + threadIdx.x; pix < pixels; pix += (long)gridDim.x * 256) {
         const int x = (int)(pix % p.w); const long t = pix / p.w; const int y = (int)(t % p.h); const long b = t / p.h;
         float qv[DMAX];
@@ -582,8 +590,11 @@ extern "C" int isa_sdp_attention(const void* q, const void* k, const void* v, co
                                  float temperature, int32_t dtype, int32_t heads, int32_t mask_per_head,
                                  float* ws, int64_t ws_floats, int32_t tile_keys, void* stream) {
     if (!q || !k || !v || !out || bh <= 0 || lq <= 0 || L <= 0 || dk <= 0 || dk > DMAX || dv <= 0 || dv > DMAX ||
-        temperature <= 0.f || heads < 1) return ISA_EINVAL;
+        !(temperature > 0.f) || heads < 1) return ISA_EINVAL;      /* !(x > 0) refuses a NaN temperature too */
     if (dtype != ISA_F32 && dtype != ISA_BF16 && dtype != ISA_F16) return ISA_EDTYPE;
+    /* refused here for every shape: sdp_fast halves a tile that does not fit the LDS, which used to turn 2048 into 1024 */
+    if (tile_keys != 0 && tile_keys != 256 && tile_keys != 512 && tile_keys != 1024) return ISA_EINVAL;
+    if (ws && ws_floats < 0) return ISA_EINVAL;
     hipStream_t s = as_stream(stream);
     if (dk == dv && ws) {
         int rc = 1;
@@ -719,27 +730,34 @@ extern "C" int isa_linear_ln(const float* x, const float* w, const float* bias, 
 extern "C" int isa_instance_norm_res(const isa_tensor* x, const isa_tensor* res, const isa_tensor* out, float eps,
                                      float* sums /* zeroed [n][2c] */, void* stream) {
     if (!tensor_ok(x, 1) || !tensor_ok(res, 1) || !tensor_ok(out, 1) || !sums || x->c > 64 || res->c != x->c || out->c != x->c ||
-        x->dtype != res->dtype || x->dtype != out->dtype || x->n != res->n || x->h != res->h || x->w != res->w) return ISA_EINVAL;
+        x->dtype != res->dtype || x->dtype != out->dtype || x->n != res->n || x->h != res->h || x->w != res->w ||
+        x->n != out->n || x->h != out->h || x->w != out->w) return ISA_EINVAL;
     const long hw = (long)x->h * x->w, total = hw * x->n * x->c;
     hipStream_t s = as_stream(stream);
     dim3 g1(grid_cap(cdiv(hw, 256), 256), x->n);
     const int g2 = grid_cap(cdiv(total, 256));
     if (x->dtype == ISA_BF16) {
-        hipLaunchKernelGGL(inorm_stats_kernel<bf16_t>, g1, dim3(256), 2 * x->c * 4, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL((inorm_stats_kernel<bf16_t, 0>), g1, dim3(256), x->c * 4, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL((inorm_stats_kernel<bf16_t, 1>), g1, dim3(256), x->c * 4, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums);
         hipLaunchKernelGGL(inorm_apply_kernel<bf16_t>, dim3(g2), dim3(256), 0, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums, eps, (bf16_t*)out->data, out->ld, total);
     } else {
-        hipLaunchKernelGGL(inorm_stats_kernel<float>, g1, dim3(256), 2 * x->c * 4, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL((inorm_stats_kernel<float, 0>), g1, dim3(256), x->c * 4, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL((inorm_stats_kernel<float, 1>), g1, dim3(256), x->c * 4, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums);
         hipLaunchKernelGGL(inorm_apply_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums, eps, (float*)out->data, out->ld, total);
     }
     return launch_status();
 }
 
 extern "C" int isa_local_attention(const isa_tensor* q, const isa_tensor* k, const isa_tensor* v, const float* nomask,
-                                   const isa_tensor* out, int32_t dilation, void* stream) {
+                                   const isa_tensor* out, int32_t dilation, float scale, void* stream) {
     if (!tensor_ok(q, 1) || !tensor_ok(k, 1) || !tensor_ok(v, 1) || !tensor_ok(out, 1) || !nomask || dilation < 1 ||
         q->c != k->c || q->c > DMAX || v->c > DMAX || out->c != v->c || q->dtype != k->dtype || q->dtype != v->dtype ||
         q->dtype != out->dtype) return ISA_EINVAL;
-    LocalParams p{q->data, k->data, v->data, nomask, out->data, q->n, q->h, q->w, q->c, v->c, q->ld, k->ld, v->ld, out->ld, dilation};
+    for (const isa_tensor* t : {k, v, out})
+        if (t->n != q->n || t->h != q->h || t->w != q->w) return ISA_EINVAL;
+    if (!(scale > 0.f) || !(scale <= FLT_MAX)) return ISA_EINVAL;       /* NaN, infinite, zero or negative */
+    LocalParams p{q->data, k->data, v->data, nomask, out->data, q->n, q->h, q->w, q->c, v->c, q->ld, k->ld, v->ld, out->ld, dilation,
+                  scale};
     const int grid = grid_cap(cdiv((long)q->n * q->h * q->w, 256));
     if (q->dtype == ISA_BF16) hipLaunchKernelGGL(local_attn_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p);
     else hipLaunchKernelGGL(local_attn_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p);

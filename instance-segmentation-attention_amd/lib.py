@@ -225,7 +225,7 @@ SIGNATURES = {
     "isa_sdp_scores": [VP, VP, VP, I32, I32, I32, I64, I32, I32, I32, VP],
     "isa_linear_ln": [VP, VP, VP, VP, VP, VP, F, I32, I32, I32, VP, VP],
     "isa_instance_norm_res": [P_T, P_T, P_T, F, VP, VP],
-    "isa_local_attention": [P_T, P_T, P_T, VP, P_T, I32, VP],
+    "isa_local_attention": [P_T, P_T, P_T, VP, P_T, I32, F, VP],
     "isa_point_query": [VP, P_T, VP, VP],
     "isa_image_ex": [VP, P_T, VP],
     "isa_nchw_to_nhwc": [VP, I32, P_T, VP],

@@ -27,7 +27,7 @@ sys.path.insert(0, HERE)
 import ref_shim          # noqa: E402
 import reseg_ref as R    # noqa: E402
 
-from golden_io import pack, pack_bits  # noqa: E402
+from golden_io import pack, pack_bits, subsample_stride  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 
@@ -278,6 +278,94 @@ def byname_cases(store):
     store["local/qk_in"], store["local/v_in"], store["local/out"] = qk.numpy(), vv.numpy(), full.numpy()
 
 
+def byname_shape_cases(store):
+    """a19-a21 off the one configuration of byname_cases: the reference's classes over oracle/byname_ref.py's case lists
+    (seeds of their own: nothing here touches the generators byname_cases draws from after it has seeded them).
+    Stored per case: the state_dict (biases and the LayerNorm affine perturbed - their initial values, 0 and 1, would
+    hide a dropped term), the inputs of at most STORE_MAX elements (larger ones are drawn again from the case's seed by
+    byname_ref.*_inputs), the hooked intermediates and the outputs."""
+    from modules import utils as U
+    import byname_ref as B
+
+    def perturb(mod, seed):
+        rs = np.random.RandomState(seed)
+        with torch.no_grad():
+            for k_, p in mod.state_dict().items():
+                if k_.endswith("bias") or k_.startswith("layer_norm"):
+                    p.add_(torch.from_numpy((0.3 * rs.standard_normal(tuple(p.shape))).astype(np.float32)))
+
+    def put(pre, **tensors):
+        """In full up to STORE_MAX elements; above, golden_io's strided sample plus float64 sums over the whole tensor
+        (sum, sum of magnitudes, sum of squares over the non-NaN elements, and the number of NaNs)."""
+        for nm, t in tensors.items():
+            a = t.detach().numpy()
+            if a.size <= B.STORE_MAX:
+                store[pre + nm] = a
+                continue
+            flat = a.reshape(-1)
+            a64 = flat.astype(np.float64)
+            store[pre + nm + "/shape"] = np.array(a.shape, dtype=np.int64)
+            store[pre + nm + "/sub"] = flat[::subsample_stride(flat.size, B.STORE_MAX)]
+            store[pre + nm + "/sums"] = np.array([np.nansum(a64), np.nansum(np.abs(a64)), np.nansum(a64 * a64),
+                                                  float(np.isnan(a64).sum())])
+
+    def put_inputs(pre, **tensors):
+        put(pre, **{nm: t for nm, t in tensors.items() if t.numel() <= B.STORE_MAX})
+
+    for i, (dk, dv, dm, G, dil, b, h, w) in enumerate(B.SPD_CASES):
+        pre = "spd%d/" % i
+        torch.manual_seed(B.case_seed("spd", i))
+        mod = U._ScalePDAttention(d_k=dk, d_v=dv, d_model=dm, dilation_rate=dil, n_head=G).eval()
+        perturb(mod, B.case_seed("spd", i) + 50)
+        got = {}
+        mod.qk_w.register_forward_hook(lambda _m, _i, o: got.__setitem__("QK", o))
+        mod.v_w.register_forward_hook(lambda _m, _i, o: got.__setitem__("V", o))
+        mod.fc.register_forward_pre_hook(lambda _m, i_: got.__setitem__("att", i_[0]))
+        qk, vv, nomask = B.spd_inputs(i)
+        with torch.no_grad():
+            out = mod(qk, vv, nomask)
+        store[pre + "case"] = np.array(B.SPD_CASES[i], dtype=np.int64)
+        put(pre + "sd/", **mod.state_dict())
+        put_inputs(pre, qk_in=qk, v_in=vv, nomask=nomask)
+        put(pre, QK=got["QK"], V=got["V"], att=got["att"], out=out)
+    for i, (G, dm, dk, dv, b, lq, L) in enumerate(B.MHA_CASES):
+        pre = "mha%d/" % i
+        torch.manual_seed(B.case_seed("mha", i))
+        mha = U.MultiHeadAttention(G, dm, dk, dv).eval()
+        perturb(mha, B.case_seed("mha", i) + 50)
+        q, k, v, mask = B.mha_inputs(i)
+        with torch.no_grad():
+            o1, a1 = mha(q, k, v, mask=mask)
+            o2, none = mha(q, k, v, mask=mask, last=True)
+        assert none is None
+        store[pre + "case"] = np.array(B.MHA_CASES[i], dtype=np.int64)
+        put(pre + "sd/", **mha.state_dict())
+        put_inputs(pre, q=q, k=k, v=v)
+        store[pre + "mask_bits"] = np.packbits(mask.numpy().reshape(-1))
+        put(pre, out=o1, attn=a1, last=o2)
+    for i, (b, c, h, w) in enumerate(B.DEC_CASES):
+        pre = "dec%d/" % i
+        torch.manual_seed(B.case_seed("dec", i))
+        dec = U.Decoder(1, c, 40, 2, 12, 12).eval()
+        q, enc = B.dec_inputs(i)
+        with torch.no_grad():
+            o = dec(q, enc, None)
+        store[pre + "case"] = np.array(B.DEC_CASES[i], dtype=np.int64)
+        put_inputs(pre, q=q, enc=enc)
+        put(pre, out=o)
+
+
+def write_byname_shapes():
+    """tests/golden/byname_shapes.npz alone: python oracle/gen_golden.py byname_shapes"""
+    ref_shim.install()
+    os.makedirs(OUT, exist_ok=True)
+    st = {}
+    byname_shape_cases(st)
+    path = os.path.join(OUT, "byname_shapes.npz")
+    np.savez_compressed(path, **st)
+    print("byname_shapes", len(st), "arrays", os.path.getsize(path) // 1024, "KiB")
+
+
 def main():
     torch.set_num_threads(8)
     reseg, config = ref_shim.install()
@@ -304,13 +392,14 @@ def main():
         path = os.path.join(OUT, name + ".npz")
         np.savez_compressed(path, **st)
         print(name, len(st), "arrays", os.path.getsize(path) // 1024, "KiB")
-    if only and "byname_ops" not in only:
-        return
-    st = {}
-    byname_cases(st)
-    path = os.path.join(OUT, "byname_ops.npz")
-    np.savez_compressed(path, **st)
-    print("byname_ops", os.path.getsize(path) // 1024, "KiB")
+    if not only or "byname_ops" in only:
+        st = {}
+        byname_cases(st)
+        path = os.path.join(OUT, "byname_ops.npz")
+        np.savez_compressed(path, **st)
+        print("byname_ops", os.path.getsize(path) // 1024, "KiB")
+    if not only or "byname_shapes" in only:
+        write_byname_shapes()
 
 
 if __name__ == "__main__":

@@ -502,18 +502,20 @@ def sdp_attention(q, k, v, temperature, mask=None):
     return torch.bmm(attn, v), attn
 
 
-def local_dilated_attention(Q, K, V, nomask, d):
+def local_dilated_attention(Q, K, V, nomask, d, scale=None):
     """Core of _ScalePDAttention.forward (utils.py:276-299) after the 1x1 projections.
-    Q,K[B,dk,H,W], V[B,dv,H,W], nomask[B,1,H,W] (non-zero = masked key), dilation d.
+    Q,K[B,dk,H,W], V[B,dv,H,W], nomask[B,1,H,W] with values in {0, 1}, 1 = masked key (the reference's `.byte()`
+    truncates anything else), dilation d.  scale: factor on the logits; None means dk ** -0.5, which equals the
+    reference's c ** -0.5 (c = d_model // n_head, the per-head input width: utils.py:273,293) only where c == dk.
     Returns [B,dv,H,W]: per pixel softmax over its 3x3 dilated neighbourhood."""
     b, dk, h, w = K.shape
+    scale = dk ** -0.5 if scale is None else scale
     Kp, Vp, Mp = (F.pad(t, (d, d, d, d)) for t in (K, V, nomask))
     logits, vals = [], []
     for i in range(9):
         oy, ox = (i // 3) * d, (i % 3) * d
         kk = Kp[:, :, oy:oy + h, ox:ox + w]
-        logits.append(((kk * Q).sum(1) * dk ** -0.5).masked_fill(Mp[:, 0, oy:oy + h, ox:ox + w] != 0,
-                                                                  float("-inf")))
+        logits.append(((kk * Q).sum(1) * scale).masked_fill(Mp[:, 0, oy:oy + h, ox:ox + w] != 0, float("-inf")))
         vals.append(Vp[:, :, oy:oy + h, ox:ox + w])
     p = torch.softmax(torch.stack(logits, 1), 1)
     p = torch.where(torch.isnan(p), torch.zeros_like(p), p)
