@@ -985,6 +985,53 @@ int isa_elastic_field(const float* noise, const float* alpha_dev, int32_t n, int
 int isa_warp_u8(const uint8_t* src, const float* disp, int32_t n, int32_t h, int32_t w, int32_t c,
                 int32_t mode, uint8_t* dst, void* stream);
 
+/* ---- copy-paste augmentation (Ghiasi et al., CVPR 2021): instances of another image of the batch pasted over the target ----
+ * One entry runs the whole stage on `stream`: the paste plan, the capacity limit, the occluded planes, the compaction of
+ * the survivors and the new object counts, all on the device.  It allocates nothing, never synchronises and reads nothing
+ * back; the launch sequence does not depend on the data (a launch that clears the scratch, then three), so the call can
+ * be captured in a hipGraph.  Every argument is checked before anything is launched or written.
+ * Inputs, device memory, a batch of n images of one size h x w:
+ *   rgb uint8 [n,h,w,c], c in 1..4;  sem uint8 [n,h,w];
+ *   planes uint8 [n,h,w,k], k in 1..ISA_PASTE_MAX_PLANES: the first n_objects[b] planes of image b are real.  Only "zero /
+ *     non-zero" of a plane byte matters for decisions; byte values are carried through unchanged;
+ *   n_objects int32 [n], clamped to 0..k by the kernels;
+ *   xform int32 [n,4] = {src, flip, dy, dx} per target image;  select uint32 [n]: bit j = source plane j is a candidate;
+ *   min_area by value; values < 1 mean 1.
+ * For target image b with s = src; any s outside 0..n-1 means "no paste" (s == b is allowed):
+ *  1. Geometry.  For a target pixel (y, x): u = x - dx, v = y - dy.  The pixel is IN FRAME iff 0 <= u < w and 0 <= v < h.
+ *     The source pixel is xs = (flip & 1) ? w-1-u : u, ys = (flip & 2) ? h-1-v : v: the source is flipped, then shifted by
+ *     (dy, dx).  Any int32 shift is legal; a shift that leaves nothing in frame pastes nothing.
+ *  2. Areas.  area[j] = the number of in-frame target pixels whose source byte planes[s,ys,xs,j] is non-zero, for
+ *     j < n_objects[s].  Planes at or beyond n_objects[s] are ignored even if they hold non-zero bytes.
+ *  3. Paste set P.  Walk j ascending over j < n_objects[s]: j is a candidate iff bit j of select[b] is set and
+ *     area[j] >= max(min_area, 1).  P is the first k - n_objects[b] candidates (the capacity rule: the count of target
+ *     planes BEFORE occlusion bounds it, which keeps the rule non-circular).
+ *  4. P empty: image b passes through.  rgb, sem and the planes 0..n_objects[b]-1 are copied byte for byte, the planes
+ *     behind them are zero, n_out[b] = n_objects[b]; nothing is dropped, even an empty real plane.
+ *  5. Otherwise M(y,x) = in frame and some j in P has a non-zero source byte.  Where M holds: rgb_out = rgb[s,ys,xs,:],
+ *     sem_out = sem[s,ys,xs], every target plane byte becomes 0.  Elsewhere the outputs equal the target's inputs.
+ *  6. Pasted planes.  For j in P: q_j(y,x) = planes[s,ys,xs,j] in frame, 0 outside.
+ *  7. Survival and order.  A target plane i < n_objects[b] is kept iff it has a non-zero byte left after step 5.  Output
+ *     planes: first the kept target planes in ascending i, then the pasted planes in ascending j, then zero planes up to k.
+ *     n_out[b] = kept + |P|, at least 1 and at most k.
+ *  8. plan int32 [n,4] = {pasted bits (over j), kept-target bits (over i), n_out, area-limited flag}.  The flag is 1 iff a
+ *     plane j < n_objects[s] with its select bit set was refused by min_area or by capacity.  A pass-through image has
+ *     pasted bits 0 and kept bits (1 << n_objects[b]) - 1; with s outside 0..n-1 the flag is 0.
+ * No blending of the seam.  No output (rgb_out, sem_out, planes_out, n_out, plan, scratch) may overlap an input or another
+ * output: ISA_EINVAL (another target may still read image b as its source).
+ * Limits: n in 1..65535; h, w in 1..ISA_PASTE_MAX_SIDE.  Alignment (ISA_EALIGN): n_objects, xform, select, n_out, plan and
+ * scratch 4 bytes; planes and planes_out 16 bytes when k % 16 == 0 (pixel vectors then move as 16-byte loads and stores),
+ * 1 byte otherwise; rgb, sem and their outputs 1 byte.  scratch: ISA_COPY_PASTE_SCRATCH_BYTES(n, k) bytes (the int32 area
+ * and remaining-area counters per image and plane), ISA_ENOMEM when smaller; it need not be cleared by the caller.
+ * Counters are integer atomics and there is no float arithmetic: two runs give the same bytes. */
+#define ISA_PASTE_MAX_SIDE 4096
+#define ISA_PASTE_MAX_PLANES 32
+#define ISA_COPY_PASTE_SCRATCH_BYTES(n, k) ((int64_t)(n) * (k) * 8)
+int isa_copy_paste_u8(const uint8_t* rgb, const uint8_t* sem, const uint8_t* planes, const int32_t* n_objects,
+                      const int32_t* xform, const uint32_t* select, int32_t n, int32_t h, int32_t w, int32_t c, int32_t k,
+                      int32_t min_area, uint8_t* rgb_out, uint8_t* sem_out, uint8_t* planes_out, int32_t* n_out,
+                      int32_t* plan, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- boundary layout converters (the reference passes NCHW fp32: reseg.py:106-110) -----------
  * nchw_to_nhwc: channels [csrc, c) are written as 0; bf16 stores round to nearest even.  Channels at or above c: a dst
  * with ld == rup(c, 8) <= 32, 16-byte aligned src and data and h*w % 4 == 0 is written in whole padded rows (channels

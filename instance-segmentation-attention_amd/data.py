@@ -474,6 +474,58 @@ def elastic(rgb, sem, planes, n_objects, disp, max_planes=32, device="cuda"):
     return rgb2, sem2, p2, out_counts
 
 
+# ---- copy-paste (Ghiasi et al. 2021): not in the reference; the contract is in include/isa_kernels.h and DESIGN.md
+# section 19 ------------------------------------------------------------------------------------------------------------
+def _device_i32(v, n, width, device):
+    """A sequence (copied to the device) or a device tensor (used where it is) as contiguous int32 [n] or [n,width]."""
+    shape = (n,) if width == 1 else (n, width)
+    if torch.is_tensor(v):
+        if v.dtype == getattr(torch, "uint32", None):
+            v = v.view(torch.int32)
+        t = v.to(device=device, dtype=torch.int32).reshape(shape)
+    else:
+        t = torch.from_numpy((np.asarray(v, np.int64).reshape(shape) & 0xffffffff).astype(np.uint32).view(np.int32)).to(device)
+    return t.contiguous()
+
+
+def copy_paste(rgb, sem, planes, n_objects, src, select, flip, shift, min_area=1, device="cuda", out=None, scratch=None):
+    """The loader's copy-paste stage for a batch on the device (isa_copy_paste_u8): instances of image src[b], chosen by
+    the bits of select[b] (bit j: source plane j is a candidate), flipped (flip[b]: bit 0 along x, bit 1 along y) and
+    shifted by shift[b] = (dy, dx), are pasted over image b.  rgb uint8 [n,h,w,c], sem uint8 [n,h,w], planes uint8
+    [n,h,w,k]; n_objects, src, select, flip [n] and shift [n,2] are sequences or device tensors (int32; select may be
+    uint32) - with device tensors nothing is copied to the host or from it.  src outside 0..n-1: no paste.  A plane whose
+    pasted area is below min_area pixels is not pasted, nor is one for which the target has no free plane; target planes the
+    paste covers entirely are dropped and the survivors compacted.  Returns (rgb, sem, planes, n_out int32 [n], plan int32
+    [n,4] = (pasted bits, kept-target bits, n_out, area-limited flag)), all on the device; nothing is read back, so the
+    call can be captured in a HIP graph once `out` (those five tensors, to be written) and `scratch` (uint8, at least
+    lib.copy_paste_scratch_bytes(n, k) bytes) are given."""
+    from . import lib as L
+    rgb, sem, planes = (t.to(device).contiguous() for t in (rgb, sem, planes))
+    assert all(t.dtype == torch.uint8 for t in (rgb, sem, planes)) and planes.dim() == 4 and rgb.dim() == 4
+    n, h, w, k = planes.shape
+    c = rgb.shape[3]
+    assert tuple(rgb.shape[:3]) == (n, h, w) and sem.numel() == n * h * w, (tuple(rgb.shape), tuple(sem.shape), tuple(planes.shape))
+    dev = planes.device
+    nobj = _device_i32(n_objects, n, 1, dev)
+    xform = torch.cat([_device_i32(src, n, 1, dev)[:, None], _device_i32(flip, n, 1, dev)[:, None], _device_i32(shift, n, 2, dev)], 1)
+    sel = _device_i32(select, n, 1, dev)
+    if out is None:
+        out = (torch.empty_like(rgb), torch.empty_like(sem), torch.empty_like(planes),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev))
+    rgb2, sem2, p2, n_out, plan = out
+    for t, like in ((rgb2, rgb), (sem2, sem), (p2, planes)):
+        assert t.is_contiguous() and t.dtype == torch.uint8 and t.shape == like.shape and t.device == dev
+    assert n_out.dtype == torch.int32 and n_out.numel() == n and plan.dtype == torch.int32 and plan.numel() == 4 * n
+    need = L.copy_paste_scratch_bytes(n, k)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.dtype == torch.uint8 and scratch.device == dev
+    L.check(L.lib().isa_copy_paste_u8(L.ptr(rgb), L.ptr(sem), L.ptr(planes), L.ptr(nobj), L.ptr(xform), L.ptr(sel), n, h, w, c, k,
+                                      int(min_area), L.ptr(rgb2), L.ptr(sem2), L.ptr(p2), L.ptr(n_out), L.ptr(plan),
+                                      L.ptr(scratch), scratch.numel(), L.stream_ptr()), "isa_copy_paste_u8")
+    return rgb2, sem2, p2, n_out, plan
+
+
 class DevicePrefetcher(object):
     """Wraps an iterable of collated host batches (x, sem, ins, n): batch i+1 travels to the device on its own HIP
     stream while step i computes, so the host-to-device time of the reference's hand-over (373 MB per step at bs=16:

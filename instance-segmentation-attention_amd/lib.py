@@ -56,6 +56,14 @@ def elastic_scratch_bytes(n, h, w):
     return n * h * w * 8
 
 
+PASTE_MAX_SIDE, PASTE_MAX_PLANES = 4096, 32      # ISA_PASTE_MAX_SIDE, ISA_PASTE_MAX_PLANES
+
+
+def copy_paste_scratch_bytes(n, k):
+    """ISA_COPY_PASTE_SCRATCH_BYTES: the int32 area and remaining-area counters per image and plane of isa_copy_paste_u8."""
+    return n * k * 8
+
+
 DISC_MAX_K, DISC_CFG_FLOATS, DISC_CNT_STRIDE, ROW_CHUNKS = 32, 12, 36, 64     # ISA_DISC_*, ISA_ROW_CHUNKS
 
 
@@ -250,6 +258,8 @@ SIGNATURES = {
     # elastic deformation (data.elastic_field, data.warp, data.elastic; RecordLoader(elastic=True))
     "isa_elastic_field": [VP, VP, I32, I32, I32, VP, I32, VP, VP, I64, VP],
     "isa_warp_u8": [VP, VP, I32, I32, I32, I32, I32, VP, VP],
+    # copy-paste augmentation (data.copy_paste; RecordLoader(copy_paste=True))
+    "isa_copy_paste_u8": [VP, VP, VP, VP, VP, VP, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP, I64, VP],
 }
 
 

@@ -128,12 +128,27 @@ class RecordLoader(object):
     per image u = random() and a = uniform(*elastic_alpha), alpha = a if u < elastic_p else 0 (both are always drawn);
     per batch torch.rand((B,h,w,2)) * 2 - 1 on the device.  The loader's other generators are not touched, so every other
     draw is the same with the flag on or off.  The defaults are a stated choice, not a tuned one: at sigma 8 the field's
-    standard deviation is about alpha / 50 pixels, so alpha 100 moves a pixel by roughly 2."""
+    standard deviation is about alpha / 50 pixels, so alpha 100 moves a pixel by roughly 2.
+
+    copy_paste=True (training mode only; not in the reference) pastes instances of another image of the batch over an
+    image (Ghiasi et al. 2021; `data.copy_paste`, isa_copy_paste_u8): image, semantic map, occluded instance planes and
+    object count change together.  The stage runs once per batch after the samples are concatenated and BEFORE the elastic
+    stage, so a following deformation also bends the seam.  The whole bookkeeping - which planes fit, which target planes
+    survive, the compaction, the new counts - happens on the device without a read-back; the one copy of B counts to the
+    host is the hand-over's.  Its draws come from a generator of the stage's own, seeded from (seed, epoch, rank); per
+    image, always in this order: u = random(), s = randrange(B), bits = getrandbits(32), fl = getrandbits(2),
+    dy = randint(-int(copy_paste_shift * h), int(copy_paste_shift * h)), dx likewise with w; the source is s if
+    u < copy_paste_p, else none.  Bit j of `bits` makes plane j of the source a candidate; a candidate whose pasted area is
+    below copy_paste_min_area pixels, or for which the target has no free plane left, is not pasted (`last_paste_plan`, int32
+    [B,4] on the device: pasted bits, kept target bits, count, and a flag for such a refusal).  The loader's other
+    generators are not touched.  The defaults are a stated choice, not a tuned one: half the images receive about half the
+    instances of another one, moved by up to half a side."""
 
     def __init__(self, dataset, batch_size, height=256, width=256, max_n_objects=32, mode='test', seed=0, device='cuda',
                  rank=0, world=1, d4=True, rotation=True, center_cut=True, color_jitter=False, gamma=False,
                  channel_swap=False, grayscale=False, resolution=False, elastic=False, elastic_alpha=(0.0, 100.0),
-                 elastic_sigma=8.0, elastic_p=0.5):
+                 elastic_sigma=8.0, elastic_p=0.5, copy_paste=False, copy_paste_p=0.5, copy_paste_min_area=16,
+                 copy_paste_shift=0.5):
         assert mode in ('training', 'test')
         self.ds, self.bs, self.h, self.w, self.k, self.mode = dataset, batch_size, height, width, max_n_objects, mode
         self.seed, self.epoch, self.device, self.rank, self.world = seed, 0, device, rank, world
@@ -147,6 +162,11 @@ class RecordLoader(object):
         self.elastic_sigma, self.elastic_p = elastic_sigma, elastic_p
         assert len(self.elastic_alpha) == 2 and 0.0 <= elastic_p <= 1.0
         self.last_field = None                                           # disp fp32 [B,h,w,2] of the last batch, on the device
+        # copy-paste (see the class docstring); off: no draw is made and nothing is allocated for it
+        self.copy_paste, self.copy_paste_p = copy_paste, copy_paste_p
+        self.copy_paste_min_area, self.copy_paste_shift = copy_paste_min_area, copy_paste_shift
+        assert 0.0 <= copy_paste_p <= 1.0 and copy_paste_min_area >= 1 and 0.0 <= copy_paste_shift <= 1.0
+        self.last_paste_plan = None                                      # plan int32 [B,4] of the last batch, on the device
         # per image of the last batch: dict(op, angle, bg_key, pick) and, for the flags that are on, ratio / jitter (the
         # four (name, factor) in shuffled order) / gamma / channels (None: no swap) / gray / elastic_alpha - tests / logging
         self.last_draws = []
@@ -248,12 +268,27 @@ class RecordLoader(object):
             el_seed = 2000003 * self.seed + self.epoch + 7919 * self.rank + 104729
             el_rng, el_gen = random.Random(el_seed), torch.Generator(device=self.device)
             el_gen.manual_seed(el_seed % (2 ** 63))
+        paste = self.copy_paste and self.mode == 'training'
+        if paste:                                                        # a generator of the stage's own (another constant)
+            cp_rng = random.Random(3000017 * self.seed + self.epoch + 7919 * self.rank + 611953)
         for s in range(0, len(idx), self.bs):
             chunk = idx[s:s + self.bs]
             chunk = chunk + [chunk[0]] * (self.bs - len(chunk))         # dataset.py:330-333: repeat the batch's first image
             self.last_draws = []
             rgbs, sems, inss, ns = zip(*(self._one(i, py_rng, np_rng) for i in chunk))
             rgb, sem, ins = torch.cat(rgbs), torch.cat(sems), torch.cat(inss)
+            if paste:
+                from . import data as D
+                ry, rx = int(self.copy_paste_shift * self.h), int(self.copy_paste_shift * self.w)
+                for draws in self.last_draws:
+                    u, src, bits, fl = cp_rng.random(), cp_rng.randrange(len(chunk)), cp_rng.getrandbits(32), cp_rng.getrandbits(2)
+                    dy, dx = cp_rng.randint(-ry, ry), cp_rng.randint(-rx, rx)
+                    draws["copy_paste"] = dict(src=src if u < self.copy_paste_p else -1, select=bits, flip=fl, dy=dy, dx=dx)
+                cp = [d["copy_paste"] for d in self.last_draws]
+                rgb, sem, ins, ns, self.last_paste_plan = D.copy_paste(
+                    rgb, sem, ins, ns, [d["src"] for d in cp], [d["select"] for d in cp], [d["flip"] for d in cp],
+                    [(d["dy"], d["dx"]) for d in cp], self.copy_paste_min_area, self.device)
+                ns = ns.cpu()                                            # the hand-over keeps its counts on the host: B ints
             if elastic:
                 from . import data as D
                 alphas = []
@@ -264,4 +299,4 @@ class RecordLoader(object):
                 noise = torch.rand((len(chunk), self.h, self.w, 2), generator=el_gen, device=self.device) * 2 - 1
                 self.last_field = D.elastic_field(noise, alphas, self.elastic_sigma, self.device)
                 rgb, sem, ins, ns = D.elastic(rgb, sem, ins, ns, self.last_field, self.k, self.device)
-            yield rgb, sem, ins, torch.tensor(ns, dtype=torch.int32)
+            yield rgb, sem, ins, ns if torch.is_tensor(ns) else torch.tensor(ns, dtype=torch.int32)

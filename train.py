@@ -85,6 +85,13 @@ def build_parser():
                         help='the field is alpha * (blurred noise in [-1, 1)), alpha uniform in [LO, HI] per image')
     parser.add_argument('--elastic-sigma', type=float, default=8.0, help='sigma of the Gaussian blur of the field, in pixels')
     parser.add_argument('--elastic-p', type=float, default=0.5, help='probability that an image is deformed')
+    # copy-paste of instances between the images of a batch (not in the reference; RecordLoader(copy_paste=True)): for the
+    # training loader of --data only.  The defaults are a stated choice, not a tuned one
+    parser.add_argument('--copy-paste', action='store_true', help='paste instances of another image of the batch, once per batch')
+    parser.add_argument('--copy-paste-p', type=float, default=0.5, help='probability that an image receives a paste')
+    parser.add_argument('--copy-paste-min-area', type=int, default=16, help='a pasted instance keeps at least this many pixels')
+    parser.add_argument('--copy-paste-shift', type=float, default=0.5,
+                        help='the pasted instances move by up to this fraction of the side, in both directions')
     return parser
 
 
@@ -104,6 +111,9 @@ def parse_args(argv=None):
     if not (opt.elastic_alpha[0] <= opt.elastic_alpha[1] and 0.0 <= opt.elastic_p <= 1.0 and 0.0 <= opt.elastic_sigma <= 16.0):
         parser.error('--elastic-alpha LO HI needs LO <= HI, --elastic-p a probability and --elastic-sigma at most 16 '
                      '(a blur radius of 64 pixels)')
+    if not (0.0 <= opt.copy_paste_p <= 1.0 and opt.copy_paste_min_area >= 1 and 0.0 <= opt.copy_paste_shift <= 1.0):
+        parser.error('--copy-paste-p needs a probability, --copy-paste-min-area at least 1 and --copy-paste-shift a fraction '
+                     'in [0, 1]')
     if opt.class_weights is not None:
         try:
             opt.class_weights = [float(v) for v in opt.class_weights.split(',')]
@@ -138,6 +148,12 @@ def elastic_arguments(opt):
                 elastic_p=opt.elastic_p)
 
 
+def copy_paste_arguments(opt):
+    """RecordLoader's copy-paste arguments: the training loader's alone."""
+    return dict(copy_paste=opt.copy_paste, copy_paste_p=opt.copy_paste_p, copy_paste_min_area=opt.copy_paste_min_area,
+                copy_paste_shift=opt.copy_paste_shift)
+
+
 def main(argv=None):
     opt = parse_args(argv)
     import isa_amd  # noqa: F401
@@ -165,7 +181,7 @@ def main(argv=None):
         from isa_amd.records import RecordDataset, RecordLoader
         train_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'training-lmdb')), per_rank, opt.size, opt.size,
                                     mode='training', seed=SEED, rank=rank, world=world, **photometric_arguments(opt),
-                                    **elastic_arguments(opt))
+                                    **elastic_arguments(opt), **copy_paste_arguments(opt))
         test_loader = RecordLoader(RecordDataset(os.path.join(opt.data, 'validation-lmdb')), per_rank, opt.size, opt.size,
                                    mode='test', seed=SEED, rank=rank, world=world)
     model.fit(*fit_arguments(opt), train_loader, test_loader, opt.out, opt.debug, **fit_keywords(opt))
