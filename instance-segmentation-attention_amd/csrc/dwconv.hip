@@ -156,16 +156,42 @@ struct TileIter {
     }
 };
 
-// Persistent over tiles of one channel block.  DB (bf16): 512 threads, waves 4-7 stage the next tile into the other
+// Tiles the double-buffered loader keeps in flight ahead of the one it converts (12 VGPRs per tile in bf16).  Measured
+// on HBM-cold operands: two tiles ahead is 0-7 % slower than one at every shape of the training step
+#ifndef ISA_DW_FWD_PF
+#define ISA_DW_FWD_PF 1
+#endif
+
+// Persistent over tiles of one channel block.  DB (bf16): 768 threads, waves 4-11 stage the next tile into the other
 // LDS buffer while waves 0-3 run the stencil on the current one (the same role split as dw_bn_bwd_kernel below);
 // weights, prologue constants and the statistic partial sums live across tiles and are flushed once.
-template <typename T, bool HAS_PRO, int ACT, bool DB>
+//  * The loader is software-pipelined across tiles like the fused backward's: the halo loads are UNCONDITIONAL at a
+//    clamped address (zeroed by selects at conversion), so the tile loop is straight-line code, the loads of the next
+//    ISA_DW_FWD_PF tiles are in flight while a tile is converted and while the loader waits at the barrier, and every
+//    vmcnt wait is partial.  With one predicated load per exec-mask region the compiler waited vmcnt(0) per tile and a CU
+//    had at most one halo tile (21.8 KB) outstanding, none during conversion: ~1.6 TB/s of reads by Little's law.
+//  * ACC: the data-gradient entry point may accumulate into the old output.  Only a launch that does takes the variant
+//    with the operand; every other one compiles it out: its compute role issues no global load, so it has no vmcnt wait
+//    in the tile loop (vmcnt also counts stores: the run-time flag made every tile wait for the previous tile's output
+//    stores, inside the stencil or - with the loads hoisted - ahead of each store).
+//  * Launch prologue: the loader's first tiles are the kernel's first memory instructions; weights, bias and the
+//    prologue constants are requested behind them through pointer selects (a null optional pointer reads element 0 of x,
+//    which always exists, and the value is replaced by the neutral constant) - one round trip and one wait ahead of the
+//    single barrier instead of ~ten dependent ones.  A pending finalize keeps its own dependency (and barrier).
+// Clamped addresses stay inside the tensor: an in-image slot reads channels [c0, c0 + 8) of an image pixel with
+// c0 < c, c0 % 8 == 0, so c0 + 8 <= rup(c, 8) <= ld (tensor_ok(., 8)); every other slot (outside the image, past
+// HALO, or a channel group with c0 >= c) reads the tile's origin pixel (b, ty * TH, tx * TW), which is inside the image
+// for every tile of the walk, at channel offset c0 if c0 < c, else c_base: c_base = 32 * blockIdx.y < c because
+// gridDim.y = ceil(c / 32), and c_base + 8 <= rup(c, 8) <= ld again.  Both hold for c % 32 != 0 and for ld > c.
+template <typename T, bool HAS_PRO, int ACT, bool DB, bool ACC>
 __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(2, 3))) void dw2_fwd_kernel(Dw2Params p) {
     // DB: waves 0-3 compute, waves 4-11 stage (three waves per SIMD: the staging arithmetic of a tile is spread over
     // twice the lanes and the SIMD has one more wave to issue from while the others wait)
     constexpr int NTHR = DB ? 768 : 256;
     constexpr int LTHR = DB ? 512 : 256;              // threads that stage a tile
     constexpr int NBUF = DB ? 2 : 1;
+    constexpr int PF = ISA_DW_FWD_PF;
+    static_assert(PF == 1 || PF == 2, "prefetch distance in tiles");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* tile_base = sm;                          // [NBUF][HALO][PS]
     float* wts = sm + NBUF * HALO * PS;             // [9][CB]
@@ -173,6 +199,7 @@ __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(
     float* fin_tab = red + 2 * CB;                  // [2][CB] scale / shift of this channel block when the finalize runs here
     const int tid = threadIdx.x;
     const bool loader = DB && tid >= 256;
+    const bool stager = !DB || loader;                // this lane stages tiles
     const int ltid = loader ? tid - 256 : tid;        // index inside the role group
     const int c_base = blockIdx.y * CB;
     const GroupSel gs = group_sel(p.G);
@@ -185,30 +212,14 @@ __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(
         p.stats = goff(p.stats, (long)gs.g * ISA_STAT_R * 2 * p.c);
     }
     const T* wp = reinterpret_cast<const T*>(p.w);
-    for (int i = tid; i < 9 * CB; i += NTHR) {
-        const int tp = i / CB, cc = i - tp * CB;
-        wts[i] = (c_base + cc < p.c) ? st<T>::ld(wp + (long)tp * p.wld + c_base + cc) : 0.f;
-    }
-    if (tid < 2 * CB) red[tid] = 0.f;
     const int cg = ltid & 3, g = ltid >> 2, row = g >> 3, x0 = (g & 7) * 4;
     const int c0 = c_base + cg * 8;
     const bool cok = c0 < p.c;
+    const int cc0 = cok ? c0 : c_base;
     const T* xin = reinterpret_cast<const T*>(p.x);
     constexpr int NIT = (HALO * 4 + LTHR - 1) / LTHR;
+    const bool has_bs = HAS_PRO && p.pro.bscale;             // wave-uniform
 
-    // per-channel prologue constants: loaded ONCE per lane (they were re-read from global memory at the top of every
-    // tile: a dependent round trip ahead of the tile's own loads); only the per-image scale changes with the tile
-    // a pending finalize of the input's BatchNorm runs here, for this workgroup's 32 channels; the last workgroup of
-    // each channel block writes the arrays the backward pass reads
-    const bool fin = HAS_PRO && bn_fin_inline<NTHR>(p.fin, p.c, p.G, gs.g, fin_tab, CB, tid, c_base, CB,
-                                                    blockIdx.x == gridDim.x - 1 && blockIdx.z == 0);
-    float sc[8], sh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = min(c0 + j, p.c - 1);
-        sc[j] = fin ? fin_tab[c - c_base] : ((HAS_PRO && p.pro.scale) ? p.pro.scale[c] : 1.f);
-        sh[j] = fin ? fin_tab[CB + c - c_base] : ((HAS_PRO && p.pro.shift) ? p.pro.shift[c] : 0.f);
-    }
     // tile-invariant part of the staging addresses: halo pixel (rr, cc) of slot `it` and its element offset from the
     // tile's halo origin; per tile only a scalar base pointer and (on border tiles) four scalar bounds remain
     int hrc[NIT], hoff[NIT];
@@ -218,79 +229,147 @@ __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(
         const int pix = (ltid + it * LTHR) >> 2;
         const int rr = pix / (TW + 2), cc = pix - rr * (TW + 2);
         hrc[it] = (rr << 16) | cc;
-        hoff[it] = (rr * p.w_ + cc) * p.ldx + (cok ? c0 : c_base);
+        hoff[it] = (rr * p.w_ + cc) * p.ldx + cc0;
         hok[it] = pix < HALO && cok;
     }
+    const int soff = (p.w_ + 1) * p.ldx + cc0;                 // halo (1, 1) = the tile's origin pixel: the clamp target
     const int ooff = (row * p.w_ + x0) * p.ldy + c0;           // output element offset from the tile's origin
 
+    struct Geo { const T* base; int b, rlo, rhi, clo, chi; bool interior; };
+    auto geo = [&](int b, int ty, int tx) {
+        Geo q;
+        q.base = xin + (((long)b * p.h + ty * TH - 1) * p.w_ + tx * TW - 1) * p.ldx;   // halo origin (may lie outside)
+        q.b = b;
+        // scalar bounds of the in-image part of the halo, in halo coordinates
+        q.rlo = 1 - ty * TH; q.rhi = p.h + 1 - ty * TH; q.clo = 1 - tx * TW; q.chi = p.w_ + 1 - tx * TW;
+        q.interior = q.rlo <= 0 && q.rhi >= TH + 2 && q.clo <= 0 && q.chi >= TW + 2;
+        return q;
+    };
+    auto slot_ok = [&](const Geo& q, int it) {
+        const int rr = hrc[it] >> 16, cc = hrc[it] & 0xffff;
+        return hok[it] && (q.interior || (rr >= q.rlo && rr < q.rhi && cc >= q.clo && cc < q.chi));
+    };
+    // The empty asm keeps a load where it is written (see dw_bn_bwd_kernel::issue): LLVM otherwise sinks a prefetch to
+    // its first use, across the LDS-only barrier and the loop back-edge.
+    auto issue = [&](const Geo& q, int it, raw8<T>& v) {
+        v.load(q.base + (slot_ok(q, it) ? hoff[it] : soff));
+        asm volatile("" ::: "memory");
+    };
+
+    // ---- launch prologue: everything but the tile loads, requested in one round trip.  Each role calls it once (the
+    // loader behind its first tiles' loads, so the tile registers live on the loader side only); b_first: image of the
+    // loader's first tile.  Ends with the barrier that publishes the weights and the zeroed `red`.
+    float bv[8], sc[8], sh[8], bs[8];
+    auto prologue = [&](int b_first) {
+    const float* dummy = reinterpret_cast<const float*>(p.x);   // always present, 16-byte aligned, >= 16 bytes
+    constexpr int NW = (9 * CB + NTHR - 1) / NTHR;
+    float wv[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int i = min(tid + k * NTHR, 9 * CB - 1);
+        const int tp = i / CB, cc = i - tp * CB;
+        wv[k] = st<T>::ld(wp + (long)tp * p.wld + min(c_base + cc, p.c - 1));
+    }
+    // a pending finalize of the input's BatchNorm produces scale / shift below: the arrays are not read here then
+    const bool fin_pending = HAS_PRO && p.fin.stats != nullptr;
+    const bool ld_sc = HAS_PRO && p.pro.scale && !fin_pending, ld_sh = HAS_PRO && p.pro.shift && !fin_pending;
+    if (!loader) {                                              // the compute role's bias, kept in registers across tiles
+        const float* bp = p.bias ? p.bias : dummy;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bv[j] = bp[p.bias ? min(c0 + j, p.c - 1) : 0];
+    }
+    if (HAS_PRO && stager) {
+        const float* sp = ld_sc ? p.pro.scale : dummy;
+        const float* hp = ld_sh ? p.pro.shift : dummy;
+        const float* mp = (DB && has_bs) ? p.pro.bscale + (long)b_first * p.c : dummy;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = min(c0 + j, p.c - 1);
+            sc[j] = sp[ld_sc ? c : 0];
+            sh[j] = hp[ld_sh ? c : 0];
+            if constexpr (DB) bs[j] = mp[has_bs ? c : 0];
+        }
+    }
+    asm volatile("" ::: "memory");
+    // a pending finalize of the input's BatchNorm runs here, for this workgroup's 32 channels, behind the requests
+    // above; the last workgroup of each channel block writes the arrays the backward pass reads
+    const bool fin = HAS_PRO && bn_fin_inline<NTHR>(p.fin, p.c, p.G, gs.g, fin_tab, CB, tid, c_base, CB,
+                                                    blockIdx.x == gridDim.x - 1 && blockIdx.z == 0);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int i = tid + k * NTHR;
+        if (i < 9 * CB) wts[i] = (c_base + (i & (CB - 1)) < p.c) ? wv[k] : 0.f;
+    }
+    if (tid < 2 * CB) red[tid] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = min(c0 + j, p.c - 1);
+        bv[j] = (p.bias && c0 + j < p.c) ? bv[j] : 0.f;
+        sc[j] = ld_sc ? sc[j] : 1.f;
+        sh[j] = ld_sh ? sh[j] : 0.f;
+        if (fin) { sc[j] = fin_tab[c - c_base]; sh[j] = fin_tab[CB + c - c_base]; }
+        bs[j] = (DB && has_bs) ? bs[j] : 1.f;                    // z * 1.f == z bit for bit: no branch in convert
+    }
+    __syncthreads();                                             // weights + zeroed `red` visible
+    };
+
+    // one halo slot: lazy prologue, zero outside the image, fp32 into the LDS tile
+    auto convert = [&](bool ok, int it, const raw8<T>& r, float* tile) {
+        const int pix = (ltid + it * LTHR) >> 2;
+        if (pix >= HALO) return;
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float z = r.get(j);
+            if constexpr (HAS_PRO) z = act_t<ACT>(fmaf(z, sc[j], sh[j]), p.pro.act);
+            o[j] = z;
+        }
+        if constexpr (HAS_PRO) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] *= bs[j];
+        }
+        // slots outside the image were fetched from the tile's origin pixel: zero them.  Interior tiles have none
+        // (uniform over the wave), so the selects are skipped there
+        if (__builtin_amdgcn_ballot_w64(!ok) != 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = ok ? o[j] : 0.f;
+        }
+        store8<float>(tile + pix * PS + cg * 8, o);
+    };
+
+    // single-buffer form: one tile, all loads then all conversions; the per-image scale row is refetched only when the
+    // image changes
+    int bs_img = -1;
     auto stage = [&](int b, int ty, int tx, float* tile) {
-        float bs[8];
-        if (HAS_PRO && p.pro.bscale) {
+        if (has_bs && b != bs_img) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) bs[j] = p.pro.bscale[(long)b * p.c + min(c0 + j, p.c - 1)];
+            bs_img = b;
         }
-        const T* base = xin + (((long)b * p.h + ty * TH - 1) * p.w_ + tx * TW - 1) * p.ldx;   // halo origin (may lie outside)
-        // scalar bounds of the in-image part of the halo, in halo coordinates
-        const int rlo = 1 - ty * TH, rhi = p.h + 1 - ty * TH, clo = 1 - tx * TW, chi = p.w_ + 1 - tx * TW;
-        const bool interior = rlo <= 0 && rhi >= TH + 2 && clo <= 0 && chi >= TW + 2;
-        raw8<T> v[NIT]; bool ok[NIT];
-        if (interior) {
+        const Geo q = geo(b, ty, tx);
+        raw8<T> r[NIT];
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) { ok[it] = hok[it]; if (ok[it]) v[it].load(base + hoff[it]); }
-        } else {
+        for (int it = 0; it < NIT; ++it) issue(q, it, r[it]);
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int rr = hrc[it] >> 16, cc = hrc[it] & 0xffff;
-                ok[it] = hok[it] && rr >= rlo && rr < rhi && cc >= clo && cc < chi;
-                if (ok[it]) v[it].load(base + hoff[it]);
-            }
-        }
-        const bool has_bs = HAS_PRO && p.pro.bscale;             // wave-uniform: hoisted out of the element loops
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int pix = (ltid + it * LTHR) >> 2;
-            if (pix >= HALO) continue;
-            float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = 0.f;
-            if (ok[it]) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float z = v[it].get(j);
-                    if constexpr (HAS_PRO) z = act_t<ACT>(fmaf(z, sc[j], sh[j]), p.pro.act);
-                    o[j] = z;
-                }
-                if (has_bs) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] *= bs[j];
-                }
-            }
-            store8<float>(tile + pix * PS + cg * 8, o);
-        }
+        for (int it = 0; it < NIT; ++it) convert(slot_ok(q, it), it, r[it], tile);
     };
 
     auto compute = [&](int b, int ty, int tx, const float* tile, float (&s1)[8], float (&s2)[8]) {
         T* ybase = reinterpret_cast<T*>(p.y) + (((long)b * p.h + ty * TH) * p.w_ + tx * TW) * p.ldy;   // tile origin
         const bool rowok = ty * TH + row < p.h && cok;
         const int xlim = p.w_ - tx * TW;                          // x0 + o < xlim
+        // the old output (data gradient only): requested before the stencil at a clamped address, used after it
         raw8<T> oc[4];
-        if (p.accumulate && rowok) {
+        if constexpr (ACC) {
 #pragma unroll
-            for (int o = 0; o < 4; ++o)
-                if (x0 + o < xlim) oc[o].load(ybase + ooff + o * p.ldy);
+            for (int o = 0; o < 4; ++o) oc[o].load(ybase + ((rowok && x0 + o < xlim) ? ooff + o * p.ldy : cc0));
+            asm volatile("" ::: "memory");
         }
         float acc[4][8];
-        if (p.bias) {
 #pragma unroll
-            for (int o = 0; o < 4; ++o)
+        for (int o = 0; o < 4; ++o)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc[o][j] = (c0 + j < p.c) ? p.bias[c0 + j] : 0.f;
-        } else {
-#pragma unroll
-            for (int o = 0; o < 4; ++o)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[o][j] = 0.f;
-        }
+            for (int j = 0; j < 8; ++j) acc[o][j] = bv[j];
 #pragma unroll 1
         for (int dy = 0; dy < 3; ++dy) {
             float wr[3][8], in[6][8];
@@ -311,7 +390,7 @@ __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(
                 T* dst = ybase + ooff + o * p.ldy;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { s1[j] += acc[o][j]; s2[j] += acc[o][j] * acc[o][j]; }
-                if (p.accumulate) {
+                if constexpr (ACC) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) acc[o][j] += oc[o].get(j);
                 }
@@ -320,24 +399,95 @@ __global__ __launch_bounds__(DB ? 768 : 256) __attribute__((amdgpu_waves_per_eu(
         }
     };
 
-    __syncthreads();                                             // weights + zeroed `red` visible
     if (loader) {
-        TileIter ti; ti.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y);
-        int buf = 0;
-        if (ti.valid()) stage(ti.b, ti.ty, ti.tx, tile_base);
-        __syncthreads();
-        while (ti.valid()) {
-            ti.next();                                           // the tile the compute waves will consume next
-            if (ti.valid()) stage(ti.b, ti.ty, ti.tx, tile_base + (buf ^ 1) * HALO * PS);
+        // Barriers: one per staged tile (the first is the compute side's "first tile staged", every later one closes the
+        // compute side's previous tile) plus one closing its last tile: n + 1 on both sides.  Slot d of the register
+        // ring holds tiles d, d + PF, ...; a slot is refilled, load by load, right after its conversion consumed it.
+        if constexpr (DB) {
+            TileIter tn;                                         // the next tile to request
+            Geo gq[PF];
+            bool val[PF];
+            raw8<T> v[PF][NIT];
+            tn.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y);
+            // every slot is requested, a slot without a tile from tile (0, 0, 0), which always exists: the number of
+            // loads in flight at the top of the steady loop is then known at compile time and its waits are partial
+#pragma unroll
+            for (int d = 0; d < PF; ++d) {
+                val[d] = tn.valid();
+                gq[d] = val[d] ? geo(tn.b, tn.ty, tn.tx) : geo(0, 0, 0);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) issue(gq[d], it, v[d][it]);
+                tn.next();
+            }
+            prologue(gq[0].b);
+            // per-image scale row: `bs` is the row of the tile being converted; the row of the next tile's image is
+            // requested one tile ahead (into bsn) only when the image changes
+            float bsn[8];
+            bool bs_new = false;
+            TileIter tb;
+            if (has_bs) { tb.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y); tb.next(); }
+            int buf = 0;
+            // one tile: convert slot d into the free LDS buffer and (REFILL) request the tile PF after it into the slot
+            auto step = [&](auto dsel, auto refill) {
+                constexpr int d = decltype(dsel)::value;
+                constexpr bool REFILL = decltype(refill)::value;
+                float* tile = tile_base + buf * HALO * PS;
+                const Geo gc = gq[d];
+                if (has_bs) {
+                    if (bs_new) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bs[j] = bsn[j];
+                    }
+                    bs_new = tb.valid() && tb.b != gc.b;
+                    if (bs_new) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bsn[j] = p.pro.bscale[(long)tb.b * p.c + min(c0 + j, p.c - 1)];
+                        asm volatile("" ::: "memory");
+                    }
+                    tb.next();
+                }
+                if constexpr (REFILL) {
+                    gq[d] = geo(tn.b, tn.ty, tn.tx);
+#pragma unroll
+                    for (int it = 0; it < NIT; ++it) {
+                        convert(slot_ok(gc, it), it, v[d][it], tile);
+                        issue(gq[d], it, v[d][it]);
+                    }
+                    tn.next();
+                } else {
+#pragma unroll
+                    for (int it = 0; it < NIT; ++it) convert(slot_ok(gc, it), it, v[d][it], tile);
+                    val[d] = false;
+                }
+                lds_barrier();
+                buf ^= 1;
+            };
+            // steady state: every slot holds a tile and PF more remain to be requested - straight-line code with the
+            // same PF * NIT loads in flight at its top and bottom
+            while (tn.t + (PF - 1) * tn.step < tn.end) {
+                step(std::integral_constant<int, 0>{}, std::true_type{});
+                if constexpr (PF > 1) step(std::integral_constant<int, 1>{}, std::true_type{});
+            }
+            // drain: the last tiles, fewer than PF left to request
+            while (val[0]) {
+                if (PF > 1 && tn.valid()) step(std::integral_constant<int, 0>{}, std::true_type{});
+                else step(std::integral_constant<int, 0>{}, std::false_type{});
+                if constexpr (PF > 1) {
+                    if (val[1]) {
+                        if (tn.valid()) step(std::integral_constant<int, 1>{}, std::true_type{});
+                        else step(std::integral_constant<int, 1>{}, std::false_type{});
+                    }
+                }
+            }
             lds_barrier();
-            buf ^= 1;
         }
     } else {
+        prologue(0);
         float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if constexpr (DB) {
             TileIter ti; ti.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y);
             int buf = 0;
-            __syncthreads();
+            lds_barrier();                                       // first tile staged
             for (; ti.valid(); ti.next()) {
                 compute(ti.b, ti.ty, ti.tx, tile_base + buf * HALO * PS, s1, s2);
                 lds_barrier();
@@ -471,20 +621,21 @@ __global__ __launch_bounds__(256) void dw2_wgrad_reduce_kernel(const float* ws, 
     }
 }
 
-template <typename T, bool HAS_PRO, int ACT>
+template <typename T, bool HAS_PRO, int ACT, bool ACC = false>
 int launch_fwd2_inst(Dw2Params& p, dim3 grid, hipStream_t s) {
     constexpr bool DB = sizeof(T) == 2;
     constexpr size_t lds = ((size_t)(DB ? 2 : 1) * HALO * PS + 9 * CB + 2 * CB + 2 * CB) * 4;
     static bool configured = false;
     if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dw2_fwd_kernel<T, HAS_PRO, ACT, DB>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dw2_fwd_kernel<T, HAS_PRO, ACT, DB, ACC>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ISA_ELAUNCH;
         configured = true;
     }
-    hipLaunchKernelGGL((dw2_fwd_kernel<T, HAS_PRO, ACT, DB>), grid, dim3(DB ? 768 : 256), lds, s, p);
+    hipLaunchKernelGGL((dw2_fwd_kernel<T, HAS_PRO, ACT, DB, ACC>), grid, dim3(DB ? 768 : 256), lds, s, p);
     return launch_status();
 }
 
+// The data-gradient entry point (no prologue) is the only caller that may accumulate into the old output
 template <typename T>
 int launch_fwd2(Dw2Params& p, bool has_pro, hipStream_t s) {
     p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
@@ -497,6 +648,7 @@ int launch_fwd2(Dw2Params& p, bool has_pro, hipStream_t s) {
     if (gx > p.ntiles * p.G) gx = p.ntiles * p.G;
     gx = group_grid(gx, p.G);
     dim3 grid((unsigned)gx, ncb);
+    if (p.accumulate) return has_pro ? ISA_EINVAL : launch_fwd2_inst<T, false, ISA_ACT_NONE, true>(p, grid, s);
     if (has_pro && p.pro.act == ISA_ACT_RELU6) return launch_fwd2_inst<T, true, ISA_ACT_RELU6>(p, grid, s);
     if (has_pro) return launch_fwd2_inst<T, true, ACT_RT>(p, grid, s);
     return launch_fwd2_inst<T, false, ISA_ACT_NONE>(p, grid, s);
@@ -601,26 +753,6 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     const int c0 = c_base + cg * 8;
     const bool cok = c0 < p.c;
     const T* wp = reinterpret_cast<const T*>(p.w);
-    for (int i = tid; i < 9 * CB; i += NTHR) {
-        const int tp = i / CB, cc = i - tp * CB;
-        wts[i] = (c_base + cc < p.c) ? st<T>::ld(wp + (long)tp * p.wld + c_base + cc) : 0.f;
-    }
-    if (tid < CB) {
-        const int c = min(c_base + tid, p.c - 1);
-        cst[0 * CB + tid] = p.ysc[c]; cst[1 * CB + tid] = p.ysh[c];
-        cst[2 * CB + tid] = p.ymu[c]; cst[3 * CB + tid] = p.yis[c];
-        float r0 = 0.f, r1 = 0.f;                                // fold the ISA_STAT_R replicas of BN(y)'s backward sums
-#pragma unroll
-        for (int r = 0; r < ISA_STAT_R; ++r) { r0 += p.yred[r * 2 * p.c + c]; r1 += p.yred[r * 2 * p.c + p.c + c]; }
-        cst[4 * CB + tid] = r0 * p.ycnt_inv; cst[5 * CB + tid] = r1 * p.ycnt_inv;
-        cst[6 * CB + tid] = (XMODE && p.xsc) ? p.xsc[c] : 1.f; cst[7 * CB + tid] = (XMODE && p.xsh) ? p.xsh[c] : 0.f;
-        cst[8 * CB + tid] = (XMODE && p.xmu) ? p.xmu[c] : 0.f; cst[9 * CB + tid] = (XMODE && p.xis) ? p.xis[c] : 1.f;
-        if (gs.bx == 0 && c_base + tid < p.c) {                  // BN(y) parameter gradients: dbeta = sum g', dgamma = sum g'*yhat (per group)
-            if (p.ydgamma) atomicAdd(p.ydgamma + c, r1);
-            if (p.ydbeta) atomicAdd(p.ydbeta + c, r0);
-        }
-    }
-    for (int i = tid; i < 11 * CB; i += NTHR) red[i] = 0.f;     // rows 0-8: dW taps, 9-10: BN(x) sums
     const T* gin = reinterpret_cast<const T*>(p.g);
     const T* yin = reinterpret_cast<const T*>(p.y);
     const T* xin = reinterpret_cast<const T*>(p.x);
@@ -699,6 +831,64 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         xv.load(g.xb + (ok ? hox[it] : g.sx));
         asm volatile("" ::: "memory");
     };
+
+    // ---- launch prologue, one round trip: the loader role's first tile is the kernel's first memory traffic; the
+    // weights, the BN(y) constants with their replica sums and the BN(x) constants are requested behind it, every one
+    // unconditionally (a null optional pointer selects ysc, which always exists, and its value is replaced by the
+    // neutral constant), and waited for once, ahead of the single barrier.  (Conditional loads, each with its own full
+    // wait, and the tile loads behind the barrier made this about seven dependent trips.)
+    TileIter tn;                                                 // loader: the tile whose loads are in flight
+    raw8<T> gv[NIT], yv[NIT], xv[NIT];
+    Geo gn;
+    if constexpr (DB) {
+        if (loader) {
+            tn.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y);
+            if (tn.valid()) {
+                gn = geo(tn.b, tn.ty, tn.tx);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) issue(gn, it, gv[it], yv[it], xv[it]);
+            }
+        }
+    }
+    constexpr int NW = (9 * CB + NTHR - 1) / NTHR;
+    float wv[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int i = min(tid + k * NTHR, 9 * CB - 1);
+        const int tp = i / CB, cc = i - tp * CB;
+        wv[k] = st<T>::ld(wp + (long)tp * p.wld + min(c_base + cc, p.c - 1));
+    }
+    if (tid < CB) {
+        const int c = min(c_base + tid, p.c - 1);
+        const bool hsc = XMODE && p.xsc, hsh = XMODE && p.xsh, hmu = XMODE && p.xmu, his = XMODE && p.xis;
+        const float ysc = p.ysc[c], ysh = p.ysh[c], ymu = p.ymu[c], yis = p.yis[c];
+        float ra[ISA_STAT_R], rb[ISA_STAT_R];
+#pragma unroll
+        for (int r = 0; r < ISA_STAT_R; ++r) { ra[r] = p.yred[r * 2 * p.c + c]; rb[r] = p.yred[r * 2 * p.c + p.c + c]; }
+        float xsc = 1.f, xsh = 0.f, xmu = 0.f, xis = 1.f;
+        if constexpr (XMODE != 0) {
+            xsc = (hsc ? p.xsc : p.ysc)[c]; xsh = (hsh ? p.xsh : p.ysc)[c];
+            xmu = (hmu ? p.xmu : p.ysc)[c]; xis = (his ? p.xis : p.ysc)[c];
+        }
+        asm volatile("" ::: "memory");
+        cst[0 * CB + tid] = ysc; cst[1 * CB + tid] = ysh; cst[2 * CB + tid] = ymu; cst[3 * CB + tid] = yis;
+        float r0 = 0.f, r1 = 0.f;                                // fold the ISA_STAT_R replicas of BN(y)'s backward sums
+#pragma unroll
+        for (int r = 0; r < ISA_STAT_R; ++r) { r0 += ra[r]; r1 += rb[r]; }
+        cst[4 * CB + tid] = r0 * p.ycnt_inv; cst[5 * CB + tid] = r1 * p.ycnt_inv;
+        cst[6 * CB + tid] = hsc ? xsc : 1.f; cst[7 * CB + tid] = hsh ? xsh : 0.f;
+        cst[8 * CB + tid] = hmu ? xmu : 0.f; cst[9 * CB + tid] = his ? xis : 1.f;
+        if (gs.bx == 0 && c_base + tid < p.c) {                  // BN(y) parameter gradients: dbeta = sum g', dgamma = sum g'*yhat (per group)
+            if (p.ydgamma) atomicAdd(p.ydgamma + c, r1);
+            if (p.ydbeta) atomicAdd(p.ydbeta + c, r0);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int i = tid + k * NTHR;
+        if (i < 9 * CB) wts[i] = (c_base + (i & (CB - 1)) < p.c) ? wv[k] : 0.f;
+    }
+    for (int i = tid; i < 11 * CB; i += NTHR) red[i] = 0.f;     // rows 0-8: dW taps, 9-10: BN(x) sums
 
     // single-buffer form: one tile, chunks of NB slots
     auto stage = [&](int b, int ty, int tx, T* xt, T* dt) {
@@ -851,15 +1041,9 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         StageK K;
         ld8(cst + 0 * CB + cg * 8, K.sc); ld8(cst + 1 * CB + cg * 8, K.sh); ld8(cst + 2 * CB + cg * 8, K.mu);
         ld8(cst + 3 * CB + cg * 8, K.is); ld8(cst + 4 * CB + cg * 8, K.k0); ld8(cst + 5 * CB + cg * 8, K.k1);
-        TileIter tn; tn.init(tile_range(p.ntiles, gs.bx, gs.nbx), p.tiles_x, p.tiles_y);     // the tile whose loads are in flight
-        raw8<T> gv[NIT], yv[NIT], xv[NIT];
-        Geo gs, gn;
+        // (the first tile's loads were issued in the launch prologue)
+        Geo gs;
         bool have = tn.valid();
-        if (have) {
-            gn = geo(tn.b, tn.ty, tn.tx);
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) issue(gn, it, gv[it], yv[it], xv[it]);
-        }
         int buf = 0;
         while (have) {
             gs = gn;
