@@ -13,9 +13,6 @@
 
 namespace {
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
-
 __device__ __forceinline__ float block_sum(float v, float* sh) {
     v = wave_sum(v);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -526,17 +523,14 @@ __global__ __launch_bounds__(256) void mask_loss_sums_kernel(View pred, const fl
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-    do { if ((dtype) == ISA_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
-
 extern "C" int isa_mask_dot(const isa_tensor* x, const float* m, const float* w, const float* bias,
                             float* dot, float* chansum, void* stream) {
     if (!tensor_ok(x, 8) || !m || !w || !bias || !dot || !chansum) return ISA_EINVAL;
     const long items = (long)x->h * x->w * ((x->c + 7) / 8);
     dim3 grid(grid_keep_cg(grid_cap(cdiv(items, 256), 256), (x->c + 7) / 8), x->n);
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(mask_dot_kernel<bf16_t>, grid, dim3(256), x->c * 4, as_stream(stream), mkview(x), m, w, bias, dot, chansum),
-        hipLaunchKernelGGL(mask_dot_kernel<float>, grid, dim3(256), x->c * 4, as_stream(stream), mkview(x), m, w, bias, dot, chansum));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(mask_dot_kernel<decltype(t)>, grid, dim3(256), x->c * 4, as_stream(stream), mkview(x), m, w, bias, dot, chansum);
+    });
     return launch_status();
 }
 
@@ -562,9 +556,9 @@ extern "C" int isa_scaled_stats(const isa_tensor* x, const float* beta, float* s
     if (!tensor_ok(x, 8) || !beta || !stats) return ISA_EINVAL;
     const long items = (long)x->n * x->h * x->w * ((x->c + 7) / 8);
     const int grid = grid_keep_cg(grid_cap(cdiv(items, 256), 1024), (x->c + 7) / 8);
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(scaled_stats_kernel<bf16_t>, dim3(grid), dim3(256), 2 * x->c * 4, as_stream(stream), mkview(x), beta, stats),
-        hipLaunchKernelGGL(scaled_stats_kernel<float>, dim3(grid), dim3(256), 2 * x->c * 4, as_stream(stream), mkview(x), beta, stats));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(scaled_stats_kernel<decltype(t)>, dim3(grid), dim3(256), 2 * x->c * 4, as_stream(stream), mkview(x), beta, stats);
+    });
     return launch_status();
 }
 
@@ -574,18 +568,18 @@ extern "C" int isa_sp_apply(const isa_tensor* x, const float* beta, const float*
         return ISA_EINVAL;
     const long items = (long)x->n * x->h * x->w * ((x->c + 7) / 8);
     const int grid = grid_cap(cdiv(items, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(sp_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), beta, m, scale, shift, mkview(out)),
-        hipLaunchKernelGGL(sp_apply_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), beta, m, scale, shift, mkview(out)));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(sp_apply_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), beta, m, scale, shift, mkview(out));
+    });
     return launch_status();
 }
 
 extern "C" int isa_maskbn_stats(const isa_tensor* e, const float* m, const float* mean_in, float* out, void* stream) {
     if (!tensor_ok(e, 1) || !m || !out) return ISA_EINVAL;
     const long L = (long)e->h * e->w;
-    DISPATCH_T(e->dtype,
-        hipLaunchKernelGGL(maskbn_stats_kernel<bf16_t>, dim3(e->n), dim3(1024), 0, as_stream(stream), mkview(e), m, mean_in, out, L),
-        hipLaunchKernelGGL(maskbn_stats_kernel<float>, dim3(e->n), dim3(1024), 0, as_stream(stream), mkview(e), m, mean_in, out, L));
+    by_dtype(e->dtype, [&](auto t) {
+        hipLaunchKernelGGL(maskbn_stats_kernel<decltype(t)>, dim3(e->n), dim3(1024), 0, as_stream(stream), mkview(e), m, mean_in, out, L);
+    });
     return launch_status();
 }
 
@@ -601,9 +595,9 @@ extern "C" int isa_maskbn_apply_pool(const isa_tensor* e, const float* sem, cons
                                      const float* b, float eps, float* merge, void* stream) {
     if (!tensor_ok(e, 1) || !sem || !mean_var || !w || !b || !merge) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)e->n * e->h * e->w, 256));
-    DISPATCH_T(e->dtype,
-        hipLaunchKernelGGL(maskbn_apply_pool_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(e), sem, mean_var, w, b, eps, merge),
-        hipLaunchKernelGGL(maskbn_apply_pool_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(e), sem, mean_var, w, b, eps, merge));
+    by_dtype(e->dtype, [&](auto t) {
+        hipLaunchKernelGGL(maskbn_apply_pool_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(e), sem, mean_var, w, b, eps, merge);
+    });
     return launch_status();
 }
 
@@ -674,9 +668,9 @@ extern "C" int isa_dropout_mask(const float* u, int64_t n, float keep, float* ou
 extern "C" int isa_softmax_nchw(const isa_tensor* x, float* out, void* stream) {
     if (!tensor_ok(x, 1) || !out) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)x->n * x->h * x->w, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(softmax_nchw_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), out),
-        hipLaunchKernelGGL(softmax_nchw_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), out));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(softmax_nchw_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), out);
+    });
     return launch_status();
 }
 
@@ -696,9 +690,9 @@ extern "C" int isa_concat_aux(const isa_tensor* dst, const float* mask_all, cons
     if (mask_n <= 0) mask_n = dst->n;
     if (dst->n % mask_n) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)dst->n * dst->h * dst->w * dst->c, 256));
-    DISPATCH_T(dst->dtype,
-        hipLaunchKernelGGL(concat_aux_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(dst), mask_all, s_t, W_full, f, nb, mask_n),
-        hipLaunchKernelGGL(concat_aux_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(dst), mask_all, s_t, W_full, f, nb, mask_n));
+    by_dtype(dst->dtype, [&](auto t) {
+        hipLaunchKernelGGL(concat_aux_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(dst), mask_all, s_t, W_full, f, nb, mask_n);
+    });
     return launch_status();
 }
 
@@ -707,9 +701,9 @@ extern "C" int isa_gate(const isa_tensor* up, const isa_tensor* pred, const isa_
         up->h != 2 * pred->h || up->w != 2 * pred->w || up->dtype != pred->dtype || up->dtype != out->dtype) return ISA_EINVAL;
     const long items = (long)up->n * up->h * up->w * ((up->c + 7) / 8);
     const int grid = grid_cap(cdiv(items, 256));
-    DISPATCH_T(up->dtype,
-        hipLaunchKernelGGL(gate_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(up), mkview(pred), mkview(out), gmap),
-        hipLaunchKernelGGL(gate_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(up), mkview(pred), mkview(out), gmap));
+    by_dtype(up->dtype, [&](auto t) {
+        hipLaunchKernelGGL(gate_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(up), mkview(pred), mkview(out), gmap);
+    });
     return launch_status();
 }
 
@@ -718,8 +712,8 @@ extern "C" int isa_mask_loss_sums(const isa_tensor* pred, const float* target, c
     if (!tensor_ok(pred, 1) || pred->c != 2 || (!target && !onehot) || !sums) return ISA_EINVAL;
     const long L = (long)pred->h * pred->w;
     dim3 grid(grid_cap(cdiv(L, 256), 64), pred->n);
-    DISPATCH_T(pred->dtype,
-        hipLaunchKernelGGL(mask_loss_sums_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, sums),
-        hipLaunchKernelGGL(mask_loss_sums_kernel<float>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, sums));
+    by_dtype(pred->dtype, [&](auto t) {
+        hipLaunchKernelGGL(mask_loss_sums_kernel<decltype(t)>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, sums);
+    });
     return launch_status();
 }

@@ -607,8 +607,7 @@ extern "C" int isa_sdp_attention(const void* q, const void* k, const void* v, co
     if (heads != 1 || dtype == ISA_F16) return ISA_EINVAL;
     SdpParams p{q, k, v, mask, out, attn, lq, dk, dv, (long)L, 1.f / temperature};
     dim3 grid(bh, lq);
-    if (dtype == ISA_BF16) hipLaunchKernelGGL(sdp_kernel<bf16_t>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(sdp_kernel<float>, grid, dim3(256), 0, s, p);
+    by_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(sdp_kernel<decltype(t)>, grid, dim3(256), 0, s, p); });
     return launch_status();
 }
 
@@ -736,15 +735,12 @@ extern "C" int isa_instance_norm_res(const isa_tensor* x, const isa_tensor* res,
     hipStream_t s = as_stream(stream);
     dim3 g1(grid_cap(cdiv(hw, 256), 256), x->n);
     const int g2 = grid_cap(cdiv(total, 256));
-    if (x->dtype == ISA_BF16) {
-        hipLaunchKernelGGL((inorm_stats_kernel<bf16_t, 0>), g1, dim3(256), x->c * 4, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums);
-        hipLaunchKernelGGL((inorm_stats_kernel<bf16_t, 1>), g1, dim3(256), x->c * 4, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums);
-        hipLaunchKernelGGL(inorm_apply_kernel<bf16_t>, dim3(g2), dim3(256), 0, s, (const bf16_t*)x->data, x->ld, (const bf16_t*)res->data, res->ld, x->c, hw, sums, eps, (bf16_t*)out->data, out->ld, total);
-    } else {
-        hipLaunchKernelGGL((inorm_stats_kernel<float, 0>), g1, dim3(256), x->c * 4, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums);
-        hipLaunchKernelGGL((inorm_stats_kernel<float, 1>), g1, dim3(256), x->c * 4, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums);
-        hipLaunchKernelGGL(inorm_apply_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)x->data, x->ld, (const float*)res->data, res->ld, x->c, hw, sums, eps, (float*)out->data, out->ld, total);
-    }
+    by_dtype(x->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((inorm_stats_kernel<T, 0>), g1, dim3(256), x->c * 4, s, (const T*)x->data, x->ld, (const T*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL((inorm_stats_kernel<T, 1>), g1, dim3(256), x->c * 4, s, (const T*)x->data, x->ld, (const T*)res->data, res->ld, x->c, hw, sums);
+        hipLaunchKernelGGL(inorm_apply_kernel<T>, dim3(g2), dim3(256), 0, s, (const T*)x->data, x->ld, (const T*)res->data, res->ld, x->c, hw, sums, eps, (T*)out->data, out->ld, total);
+    });
     return launch_status();
 }
 
@@ -759,8 +755,7 @@ extern "C" int isa_local_attention(const isa_tensor* q, const isa_tensor* k, con
     LocalParams p{q->data, k->data, v->data, nomask, out->data, q->n, q->h, q->w, q->c, v->c, q->ld, k->ld, v->ld, out->ld, dilation,
                   scale};
     const int grid = grid_cap(cdiv((long)q->n * q->h * q->w, 256));
-    if (q->dtype == ISA_BF16) hipLaunchKernelGGL(local_attn_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(local_attn_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p);
+    by_dtype(q->dtype, [&](auto t) { hipLaunchKernelGGL(local_attn_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), p); });
     return launch_status();
 }
 
@@ -768,9 +763,8 @@ extern "C" int isa_point_query(const float* q, const isa_tensor* enc, float* out
     if (!q || !tensor_ok(enc, 1) || !out) return ISA_EINVAL;
     const long hw = (long)enc->h * enc->w, pixels = hw * enc->n;
     const int grid = grid_cap(cdiv(pixels, 256));
-    if (enc->dtype == ISA_BF16)
-        hipLaunchKernelGGL(point_query_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), q, (const bf16_t*)enc->data, enc->c, enc->ld, hw, pixels, out);
-    else
-        hipLaunchKernelGGL(point_query_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), q, (const float*)enc->data, enc->c, enc->ld, hw, pixels, out);
+    by_dtype(enc->dtype, [&](auto t) {
+        hipLaunchKernelGGL(point_query_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), q, (const decltype(t)*)enc->data, enc->c, enc->ld, hw, pixels, out);
+    });
     return launch_status();
 }

@@ -30,8 +30,6 @@ constexpr int NOISE = 255;
 enum { MS_SHIFT = 0, MS_CLAIM = 1, MS_FINAL = 2 };
 enum { PEND_NONE = 0, PEND_CLAIM = 1, PEND_INIT = 2 };
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
 
 struct Geo { int chunks; long per; };
 static inline Geo geometry(long L) {
@@ -537,22 +535,10 @@ __global__ __launch_bounds__(1024) void cluster_kmeans_out_kernel(Scratch s, int
 
 static_assert(NW * SLAB <= NW * TP * XS, "the accumulator fold reuses the tile buffer");
 
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-int emb_status(const isa_tensor* x) {
-    if (!x || !x->data || x->n <= 0 || x->n > 65535 || x->h <= 0 || x->w <= 0 || x->c < 1 || x->c > CH || x->ld < x->c ||
-        x->ld % 8 || tensor_groups(x) != 1)
-        return ISA_EINVAL;
-    if ((int64_t)x->h * x->w >= (1ll << 31)) return ISA_EINVAL;
-    if (x->dtype != ISA_F32 && x->dtype != ISA_BF16) return ISA_EDTYPE;
-    if (!aligned(x->data, 16)) return ISA_EALIGN;
-    return ISA_OK;
-}
-
 // the arguments both entries share
 int common_status(const isa_tensor* emb, const uint8_t* fg, const uint8_t* labels, const int32_t* n_objects,
                   const float* centres, const int32_t* sizes, const int32_t* moved, const void* scratch) {
-    const int rc = emb_status(emb);
+    const int rc = emb_status(emb, CH);
     if (rc != ISA_OK) return rc;
     if (!fg || !labels || !n_objects || !centres || !sizes || !moved || !scratch) return ISA_EINVAL;
     if (!aligned(n_objects, 4) || !aligned(centres, 16) || !aligned(sizes, 4) || !aligned(moved, 4) || !aligned(scratch, 16))
@@ -579,28 +565,21 @@ extern "C" int isa_cluster_meanshift(const isa_tensor* emb, const uint8_t* fg, f
     hipStream_t st = as_stream(stream);
     const View v = mkview(emb);
     const float bw2 = bandwidth * bandwidth;
-    const bool bf = emb->dtype == ISA_BF16;
     hipLaunchKernelGGL(cluster_init_kernel, grid, dim3(NT), 0, st, fg, labels, L, geo.per, s);
     int q = 1;
-#define ISA_MS(KIND, first)                                                                                                  \
-    do {                                                                                                                     \
-        if (bf)                                                                                                              \
-            hipLaunchKernelGGL((cluster_ms_kernel<bf16_t, KIND>), grid, dim3(NT), 0, st, v, fg, labels, (int)(first), q, bw2, \
-                               (int)max_objects, (int)min_pixels, (int)assign_rest, geo.per, s, centres, sizes, n_objects,   \
-                               moved);                                                                                       \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((cluster_ms_kernel<float, KIND>), grid, dim3(NT), 0, st, v, fg, labels, (int)(first), q, bw2,  \
-                               (int)max_objects, (int)min_pixels, (int)assign_rest, geo.per, s, centres, sizes, n_objects,   \
-                               moved);                                                                                       \
-        ++q;                                                                                                                 \
-    } while (0)
+    auto ms = [&](auto kind, bool first) {
+        by_dtype(emb->dtype, [&](auto t) {
+            hipLaunchKernelGGL((cluster_ms_kernel<decltype(t), decltype(kind)::value>), grid, dim3(NT), 0, st, v, fg, labels, (int)first, q,
+                               bw2, (int)max_objects, (int)min_pixels, (int)assign_rest, geo.per, s, centres, sizes, n_objects, moved);
+        });
+        ++q;
+    };
     // a round opens with a seed and ends with a ball that becomes an object or noise: the budget counts both kinds
     for (int round = 0; round < max_rounds; ++round) {
-        for (int t = 0; t < shifts; ++t) ISA_MS(MS_SHIFT, t == 0);
-        ISA_MS(MS_CLAIM, shifts == 0);
+        for (int t = 0; t < shifts; ++t) ms(std::integral_constant<int, MS_SHIFT>{}, t == 0);
+        ms(std::integral_constant<int, MS_CLAIM>{}, shifts == 0);
     }
-    ISA_MS(MS_FINAL, 1);
-#undef ISA_MS
+    ms(std::integral_constant<int, MS_FINAL>{}, true);
     return launch_status();
 }
 
@@ -617,22 +596,16 @@ extern "C" int isa_cluster_kmeans(const isa_tensor* emb, const uint8_t* fg, cons
     const dim3 grid(geo.chunks, emb->n);
     hipStream_t st = as_stream(stream);
     const View v = mkview(emb);
-    const bool bf = emb->dtype == ISA_BF16;
     hipLaunchKernelGGL(cluster_init_kernel, grid, dim3(NT), 0, st, fg, labels, L, geo.per, s);
-    if (!init)
-        for (int j = 1; j <= kmax; ++j) {
-            if (bf) hipLaunchKernelGGL(cluster_far_kernel<bf16_t>, grid, dim3(NT), 0, st, v, fg, n_objects_in, j, (int)kmax, geo.per, s);
-            else hipLaunchKernelGGL(cluster_far_kernel<float>, grid, dim3(NT), 0, st, v, fg, n_objects_in, j, (int)kmax, geo.per, s);
-        }
     const float* cen_in = init ? init : s.cen;
-    for (int i = 0; i <= iters; ++i) {
-        if (bf)
-            hipLaunchKernelGGL(cluster_lloyd_kernel<bf16_t>, grid, dim3(NT), 0, st, v, fg, labels, n_objects_in, cen_in,
+    by_dtype(emb->dtype, [&](auto t) {
+        if (!init)
+            for (int j = 1; j <= kmax; ++j)
+                hipLaunchKernelGGL(cluster_far_kernel<decltype(t)>, grid, dim3(NT), 0, st, v, fg, n_objects_in, j, (int)kmax, geo.per, s);
+        for (int i = 0; i <= iters; ++i)
+            hipLaunchKernelGGL(cluster_lloyd_kernel<decltype(t)>, grid, dim3(NT), 0, st, v, fg, labels, n_objects_in, cen_in,
                                init ? 1 : 0, i, (int)kmax, geo.per, s);
-        else
-            hipLaunchKernelGGL(cluster_lloyd_kernel<float>, grid, dim3(NT), 0, st, v, fg, labels, n_objects_in, cen_in,
-                               init ? 1 : 0, i, (int)kmax, geo.per, s);
-    }
+    });
     hipLaunchKernelGGL(cluster_kmeans_out_kernel, dim3(emb->n), dim3(1024), 0, st, s, geo.chunks, (int)iters, centres, sizes,
                        n_objects, moved);
     return launch_status();

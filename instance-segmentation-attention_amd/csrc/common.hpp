@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/isa_kernels.h"
 
 typedef __bf16 bf16_t;
@@ -32,6 +33,47 @@ static inline bool tensor_ok(const isa_tensor* t, int align_elems) {
         if (t->ld % align_elems) return false;
     }
     return true;
+}
+
+static inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+static inline bool same_shape(const isa_tensor* a, const isa_tensor* b) {
+    return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c && a->dtype == b->dtype;
+}
+// the embedding of the isa_disc_* and isa_cluster_* entries (at most max_c channels): 0 when fine, else the status to return
+static inline int emb_status(const isa_tensor* x, int max_c) {
+    if (!x || !x->data || x->n <= 0 || x->n > 65535 || x->h <= 0 || x->w <= 0 || x->c < 1 || x->c > max_c || x->ld < x->c ||
+        x->ld % 8 || x->groups > 1)
+        return ISA_EINVAL;
+    if ((int64_t)x->h * x->w >= (1ll << 31)) return ISA_EINVAL;
+    if (x->dtype != ISA_F32 && x->dtype != ISA_BF16) return ISA_EDTYPE;
+    if (!aligned(x->data, 16)) return ISA_EALIGN;
+    return ISA_OK;
+}
+
+// the by-value form of an NHWC isa_tensor that kernels take
+struct View { void* data; int n, h, w, c, ld; };
+static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
+
+// ---- launch dispatch --------------------------------------------------------------------------
+// One launch expression per kernel: the element type, a bool template flag and the channel width are picked by calling a
+// generic lambda with a tag value (`decltype(t)`, `decltype(b)::value`, `decltype(k)::value` inside it); nest them where
+// two axes combine.  An unknown dtype runs as float (entry points validate with tensor_ok first).
+template <typename F> static inline auto by_dtype(int dtype, F&& f) {
+    if (dtype == ISA_BF16) return f(bf16_t{});
+    return f(float{});
+}
+template <typename F> static inline auto by_flag(bool on, F&& f) {
+    if (on) return f(std::true_type{});
+    return f(std::false_type{});
+}
+// channels (classes) held per thread, rounded up to eights: 8, 16, 24, else 32
+template <typename F> static inline auto by_width8(int c, F&& f) {
+    switch ((c + 7) / 8) {
+        case 1:  return f(std::integral_constant<int, 8>{});
+        case 2:  return f(std::integral_constant<int, 16>{});
+        case 3:  return f(std::integral_constant<int, 24>{});
+        default: return f(std::integral_constant<int, 32>{});
+    }
 }
 
 // ---- storage-type traits --------------------------------------------------------------------

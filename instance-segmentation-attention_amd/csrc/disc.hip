@@ -30,8 +30,6 @@ namespace {
 constexpr int NT = 256, NW = 4, TP = 64, KI = ISA_DISC_MAX_K, CH = 32, SLAB = KI * CH;
 constexpr int CNT = ISA_DISC_CNT_STRIDE;
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
 
 struct Geo { int chunks; long per; };
 static inline Geo geometry(long L) {
@@ -415,34 +413,21 @@ __global__ __launch_bounds__(NT) void disc_grad_kernel(View x, const uint8_t* __
     }
 }
 
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-// the embedding of the isa_disc_* entries: 0 when fine, else the status to return
-int emb_status(const isa_tensor* x) {
-    if (!x || !x->data || x->n <= 0 || x->n > 65535 || x->h <= 0 || x->w <= 0 || x->c < 1 || x->c > CH || x->ld < x->c ||
-        x->ld % 8 || tensor_groups(x) != 1)
-        return ISA_EINVAL;
-    if ((int64_t)x->h * x->w >= (1ll << 31)) return ISA_EINVAL;
-    if (x->dtype != ISA_F32 && x->dtype != ISA_BF16) return ISA_EDTYPE;
-    if (!aligned(x->data, 16)) return ISA_EALIGN;
-    return ISA_OK;
-}
 bool batch_ok(int32_t n, int64_t L) { return n >= 1 && n <= 65535 && L >= 1 && L < (1ll << 31); }
 
 }  // namespace
 
 extern "C" int isa_disc_sums(const isa_tensor* emb, const uint8_t* labels, int32_t k, float* slab, int32_t* cslab,
                              void* stream) {
-    const int rc = emb_status(emb);
+    const int rc = emb_status(emb, CH);
     if (rc != ISA_OK) return rc;
     if (!labels || !slab || !cslab || k < 1 || k > KI) return ISA_EINVAL;
     if (!aligned(slab, 16) || !aligned(cslab, 4)) return ISA_EALIGN;
     const Geo geo = geometry((long)emb->h * emb->w);
     const dim3 grid(geo.chunks, emb->n);
-    if (emb->dtype == ISA_BF16)
-        hipLaunchKernelGGL(disc_sums_kernel<bf16_t>, grid, dim3(NT), 0, as_stream(stream), mkview(emb), labels, (int)k, geo.per, slab, cslab);
-    else
-        hipLaunchKernelGGL(disc_sums_kernel<float>, grid, dim3(NT), 0, as_stream(stream), mkview(emb), labels, (int)k, geo.per, slab, cslab);
+    by_dtype(emb->dtype, [&](auto t) {
+        hipLaunchKernelGGL(disc_sums_kernel<decltype(t)>, grid, dim3(NT), 0, as_stream(stream), mkview(emb), labels, (int)k, geo.per, slab, cslab);
+    });
     return launch_status();
 }
 
@@ -460,7 +445,7 @@ extern "C" int isa_disc_means(const float* slab, const int32_t* cslab, const int
 
 extern "C" int isa_disc_hinge(const isa_tensor* emb, const uint8_t* labels, int32_t k, const int32_t* n_objects,
                               const float* mu, const float* cfg, int32_t norm, float* hslab, double* partial, void* stream) {
-    const int rc = emb_status(emb);
+    const int rc = emb_status(emb, CH);
     if (rc != ISA_OK) return rc;
     if (!labels || !n_objects || !mu || !cfg || !hslab || !partial || k < 1 || k > KI || (norm != 1 && norm != 2))
         return ISA_EINVAL;
@@ -469,12 +454,10 @@ extern "C" int isa_disc_hinge(const isa_tensor* emb, const uint8_t* labels, int3
     const Geo geo = geometry((long)emb->h * emb->w);
     const dim3 grid(geo.chunks, emb->n);
     hipStream_t st = as_stream(stream);
-    const View v = mkview(emb);
-#define ISA_DISC_HINGE(T, N) \
-    hipLaunchKernelGGL((disc_hinge_kernel<T, N>), grid, dim3(NT), 0, st, v, labels, (int)k, n_objects, mu, cfg, geo.per, hslab, partial)
-    if (emb->dtype == ISA_BF16) { if (norm == 2) ISA_DISC_HINGE(bf16_t, 2); else ISA_DISC_HINGE(bf16_t, 1); }
-    else { if (norm == 2) ISA_DISC_HINGE(float, 2); else ISA_DISC_HINGE(float, 1); }
-#undef ISA_DISC_HINGE
+    by_dtype(emb->dtype, [&](auto t) { by_flag(norm == 2, [&](auto l2) {
+        hipLaunchKernelGGL((disc_hinge_kernel<decltype(t), decltype(l2)::value ? 2 : 1>), grid, dim3(NT), 0, st, mkview(emb), labels, (int)k,
+                           n_objects, mu, cfg, geo.per, hslab, partial);
+    }); });
     return launch_status();
 }
 
@@ -490,12 +473,10 @@ extern "C" int isa_disc_assemble(const float* hslab, const double* partial, cons
         return ISA_EALIGN;
     const Geo geo = geometry((long)L);
     hipStream_t st = as_stream(stream);
-    if (norm == 2)
-        hipLaunchKernelGGL(disc_image_kernel<2>, dim3(n), dim3(1024), 0, st, hslab, partial, mu, mnorm, cnt, n_objects, cfg, (int)n,
-                           geo.chunks, gconst, coef, img);
-    else
-        hipLaunchKernelGGL(disc_image_kernel<1>, dim3(n), dim3(1024), 0, st, hslab, partial, mu, mnorm, cnt, n_objects, cfg, (int)n,
-                           geo.chunks, gconst, coef, img);
+    by_flag(norm == 2, [&](auto l2) {
+        hipLaunchKernelGGL((disc_image_kernel<decltype(l2)::value ? 2 : 1>), dim3(n), dim3(1024), 0, st, hslab, partial, mu, mnorm, cnt, n_objects,
+                           cfg, (int)n, geo.chunks, gconst, coef, img);
+    });
     hipLaunchKernelGGL(disc_total_kernel, dim3(1), dim3(64), 0, st, (const double*)img, cfg, (int)n, coef, scal);
     return launch_status();
 }
@@ -503,25 +484,21 @@ extern "C" int isa_disc_assemble(const float* hslab, const double* partial, cons
 extern "C" int isa_disc_grad(const isa_tensor* emb, const uint8_t* labels, int32_t k, const int32_t* n_objects,
                              const float* mu, const float* gconst, const float* coef, const float* cfg, int32_t norm,
                              const isa_tensor* demb, int32_t accumulate, void* stream) {
-    const int rc = emb_status(emb);
+    const int rc = emb_status(emb, CH);
     if (rc != ISA_OK) return rc;
     if (!labels || !n_objects || !mu || !gconst || !coef || !cfg || !demb || !demb->data || k < 1 || k > KI ||
         (norm != 1 && norm != 2))
         return ISA_EINVAL;
-    if (demb->dtype != emb->dtype || demb->n != emb->n || demb->h != emb->h || demb->w != emb->w || demb->c != emb->c ||
-        demb->ld < demb->c || demb->ld % 8 || tensor_groups(demb) != 1)
-        return ISA_EINVAL;
+    if (!same_shape(demb, emb) || demb->ld < demb->c || demb->ld % 8 || tensor_groups(demb) != 1) return ISA_EINVAL;
     if (!aligned(demb->data, 16) || !aligned(n_objects, 4) || !aligned(mu, 16) || !aligned(gconst, 16) || !aligned(coef, 4) ||
         !aligned(cfg, 4))
         return ISA_EALIGN;
     const long L = (long)emb->h * emb->w;
     const dim3 grid(grid_cap(cdiv(4 * L, NT), 256), emb->n);
     hipStream_t st = as_stream(stream);
-    const View v = mkview(emb), dv = mkview(demb);
-#define ISA_DISC_GRAD(T, N) \
-    hipLaunchKernelGGL((disc_grad_kernel<T, N>), grid, dim3(NT), 0, st, v, labels, (int)k, n_objects, mu, gconst, coef, cfg, dv, (int)accumulate)
-    if (emb->dtype == ISA_BF16) { if (norm == 2) ISA_DISC_GRAD(bf16_t, 2); else ISA_DISC_GRAD(bf16_t, 1); }
-    else { if (norm == 2) ISA_DISC_GRAD(float, 2); else ISA_DISC_GRAD(float, 1); }
-#undef ISA_DISC_GRAD
+    by_dtype(emb->dtype, [&](auto t) { by_flag(norm == 2, [&](auto l2) {
+        hipLaunchKernelGGL((disc_grad_kernel<decltype(t), decltype(l2)::value ? 2 : 1>), grid, dim3(NT), 0, st, mkview(emb), labels, (int)k,
+                           n_objects, mu, gconst, coef, cfg, mkview(demb), (int)accumulate);
+    }); });
     return launch_status();
 }

@@ -88,8 +88,6 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(BnUpdChunk ch, f
 // ------------------------------------------------------------------------------------------
 // generic vectorised NHWC walker
 // ------------------------------------------------------------------------------------------
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
 
 struct BnBwdParams {
     View dt, y, dy;
@@ -689,23 +687,16 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_rows_kernel(const float* nch
     }
 }
 
-static inline bool same_shape(const isa_tensor* a, const isa_tensor* b) {
-    return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c && a->dtype == b->dtype;
-}
-
 }  // namespace
-
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-    do { if ((dtype) == ISA_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
 
 extern "C" int isa_pack_weights(const isa_pack_entry* table_dev, int32_t n_entries,
                                 const int32_t* kmap_dev, const float* src_base, void* dst_base,
                                 int32_t dst_dtype, void* stream) {
     if (!table_dev || n_entries <= 0 || !src_base || !dst_base) return ISA_EINVAL;
     dim3 grid(32, n_entries);
-    DISPATCH_T(dst_dtype,
-        hipLaunchKernelGGL(pack_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), table_dev, kmap_dev, src_base, (bf16_t*)dst_base),
-        hipLaunchKernelGGL(pack_kernel<float>, grid, dim3(256), 0, as_stream(stream), table_dev, kmap_dev, src_base, (float*)dst_base));
+    by_dtype(dst_dtype, [&](auto t) {
+        hipLaunchKernelGGL(pack_kernel<decltype(t)>, grid, dim3(256), 0, as_stream(stream), table_dev, kmap_dev, src_base, (decltype(t)*)dst_base);
+    });
     return launch_status();
 }
 
@@ -778,23 +769,15 @@ static int bn_bwd_common(const isa_tensor* dt, const isa_tensor* y, const isa_te
         if (!apply && grid > 1024) grid = 1024;     // every block ends with 2C global atomics (8 replicas)
     }
     const size_t lds = 2 * (size_t)y->c * 4;
-#define BN_BWD_LAUNCH_T(TT, AP, ACTV) \
-    do { if (p.bscale) hipLaunchKernelGGL((bn_bwd_kernel<TT, AP, ACTV, true>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk); \
-         else hipLaunchKernelGGL((bn_bwd_kernel<TT, AP, ACTV, false>), dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk); } while (0)
-#define BN_BWD_LAUNCH(AP, ACTV) \
-    DISPATCH_T(y->dtype, \
-        BN_BWD_LAUNCH_T(bf16_t, AP, ACTV), BN_BWD_LAUNCH_T(float, AP, ACTV))
-    if (apply) {
-        if (p.act == ISA_ACT_RELU6) BN_BWD_LAUNCH(true, ISA_ACT_RELU6);
-        else if (p.act == ISA_ACT_NONE) BN_BWD_LAUNCH(true, ISA_ACT_NONE);
-        else BN_BWD_LAUNCH(true, ACT_RT);
-    } else {
-        if (p.act == ISA_ACT_RELU6) BN_BWD_LAUNCH(false, ISA_ACT_RELU6);
-        else if (p.act == ISA_ACT_NONE) BN_BWD_LAUNCH(false, ISA_ACT_NONE);
-        else BN_BWD_LAUNCH(false, ACT_RT);
-    }
-#undef BN_BWD_LAUNCH
-#undef BN_BWD_LAUNCH_T
+    auto launch = [&](auto actv) {
+        by_dtype(y->dtype, [&](auto t) { by_flag(apply, [&](auto ap) { by_flag(p.bscale != nullptr, [&](auto bs) {
+            hipLaunchKernelGGL((bn_bwd_kernel<decltype(t), decltype(ap)::value, decltype(actv)::value, decltype(bs)::value>),
+                               dim3(grid, gy, G), dim3(256), lds, as_stream(stream), p, wk);
+        }); }); });
+    };
+    if (p.act == ISA_ACT_RELU6) launch(std::integral_constant<int, ISA_ACT_RELU6>{});
+    else if (p.act == ISA_ACT_NONE) launch(std::integral_constant<int, ISA_ACT_NONE>{});
+    else launch(std::integral_constant<int, ACT_RT>{});
     return launch_status();
 }
 
@@ -850,12 +833,10 @@ extern "C" int isa_affine_act_res(const isa_tensor* x, const isa_pro* pro, const
     const Walk wk = mkwalk(x->c, p.pixels);
     const dim3 grid(walk_grid(wk), 1, G);
     const bool pi = p.pro.bscale || p.oscale;
-#define MAT_LAUNCH(TT, ACTV) \
-    do { if (pi) hipLaunchKernelGGL((materialize_kernel<TT, ACTV, true>), grid, dim3(256), 0, as_stream(stream), p, wk); \
-         else hipLaunchKernelGGL((materialize_kernel<TT, ACTV, false>), grid, dim3(256), 0, as_stream(stream), p, wk); } while (0)
-    if (p.pro.act == ISA_ACT_NONE) DISPATCH_T(x->dtype, MAT_LAUNCH(bf16_t, ISA_ACT_NONE), MAT_LAUNCH(float, ISA_ACT_NONE));
-    else DISPATCH_T(x->dtype, MAT_LAUNCH(bf16_t, ACT_RT), MAT_LAUNCH(float, ACT_RT));
-#undef MAT_LAUNCH
+    by_dtype(x->dtype, [&](auto t) { by_flag(p.pro.act == ISA_ACT_NONE, [&](auto none) { by_flag(pi, [&](auto scaled) {
+        constexpr int ACTV = decltype(none)::value ? (int)ISA_ACT_NONE : ACT_RT;
+        hipLaunchKernelGGL((materialize_kernel<decltype(t), ACTV, decltype(scaled)::value>), grid, dim3(256), 0, as_stream(stream), p, wk);
+    }); }); });
     return launch_status();
 }
 
@@ -866,13 +847,13 @@ extern "C" int isa_axpy(const isa_tensor* src, const isa_tensor* dst, float alph
     const bool vec = tensor_ok(src, 8) && tensor_ok(dst, 8) && src->c % 8 == 0;
     const int grid = grid_cap(cdiv(p.pixels * (vec ? src->c / 8 : src->c), 256));
     if (vec)
-        DISPATCH_T(src->dtype,
-            hipLaunchKernelGGL(axpy8_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p),
-            hipLaunchKernelGGL(axpy8_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p));
+        by_dtype(src->dtype, [&](auto t) {
+            hipLaunchKernelGGL(axpy8_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), p);
+        });
     else
-        DISPATCH_T(src->dtype,
-            hipLaunchKernelGGL(axpy_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p),
-            hipLaunchKernelGGL(axpy_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p));
+        by_dtype(src->dtype, [&](auto t) {
+            hipLaunchKernelGGL(axpy_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), p);
+        });
     return launch_status();
 }
 
@@ -881,9 +862,9 @@ extern "C" int isa_avgpool2(const isa_tensor* x, const isa_tensor* y, void* stre
         x->n != y->n || x->h != 2 * y->h || x->w != 2 * y->w) return ISA_EINVAL;
     PoolParams p{mkview(x), mkview(y), 0};
     const int grid = grid_cap(cdiv((long)y->n * y->h * y->w * (y->c / 8), 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL((avgpool2_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, as_stream(stream), p),
-        hipLaunchKernelGGL((avgpool2_kernel<float, false>), dim3(grid), dim3(256), 0, as_stream(stream), p));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL((avgpool2_kernel<decltype(t), false>), dim3(grid), dim3(256), 0, as_stream(stream), p);
+    });
     return launch_status();
 }
 
@@ -893,9 +874,9 @@ extern "C" int isa_avgpool2_bwd(const isa_tensor* dy, const isa_tensor* dx, int3
         dy->c % 8 || dy->n != dx->n || dx->h != 2 * dy->h || dx->w != 2 * dy->w) return ISA_EINVAL;
     PoolParams p{mkview(dy), mkview(dx), accumulate};
     const int grid = grid_cap(cdiv((long)dy->n * dy->h * dy->w * (dy->c / 8), 256));
-    DISPATCH_T(dy->dtype,
-        hipLaunchKernelGGL((avgpool2_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, as_stream(stream), p),
-        hipLaunchKernelGGL((avgpool2_kernel<float, true>), dim3(grid), dim3(256), 0, as_stream(stream), p));
+    by_dtype(dy->dtype, [&](auto t) {
+        hipLaunchKernelGGL((avgpool2_kernel<decltype(t), true>), dim3(grid), dim3(256), 0, as_stream(stream), p);
+    });
     return launch_status();
 }
 
@@ -906,18 +887,17 @@ extern "C" int isa_avgpool3(const isa_tensor* x, const isa_tensor* mask, const i
                  mask->dtype != x->dtype)) return ISA_EINVAL;
     Pool3Params p{mkview(x), mask ? mkview(mask) : View{}, mkview(y), mask != nullptr, accumulate};
     const long vec_items = (long)y->n * y->h * y->w * (y->c / 8);
-    const bool aligned = (reinterpret_cast<uintptr_t>(x->data) % 16 == 0) && (reinterpret_cast<uintptr_t>(y->data) % 16 == 0);
-    if (y->c % 8 == 0 && x->ld % 8 == 0 && y->ld % 8 == 0 && aligned && vec_items < (1L << 31)) {
+    if (y->c % 8 == 0 && x->ld % 8 == 0 && y->ld % 8 == 0 && aligned(x->data, 16) && aligned(y->data, 16) && vec_items < (1L << 31)) {
         const int gridv = grid_cap(cdiv(vec_items, 256), 256 * 16);
-        DISPATCH_T(x->dtype,
-            hipLaunchKernelGGL(avgpool3_vec_kernel<bf16_t>, dim3(gridv), dim3(256), 0, as_stream(stream), p),
-            hipLaunchKernelGGL(avgpool3_vec_kernel<float>, dim3(gridv), dim3(256), 0, as_stream(stream), p));
+        by_dtype(x->dtype, [&](auto t) {
+            hipLaunchKernelGGL(avgpool3_vec_kernel<decltype(t)>, dim3(gridv), dim3(256), 0, as_stream(stream), p);
+        });
         return launch_status();
     }
     const int grid = grid_cap(cdiv((long)y->n * y->h * y->w * y->c, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(avgpool3_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p),
-        hipLaunchKernelGGL(avgpool3_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), p));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(avgpool3_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), p);
+    });
     return launch_status();
 }
 
@@ -927,9 +907,9 @@ extern "C" int isa_chan_mean(const isa_tensor* x, const isa_pro* pro, float* out
     MeanParams p{mkview(x), make_pro(pro), out, 1.f / ((float)x->h * x->w), tensor_groups(x)};
     const long items = (long)x->h * x->w * (x->c / 8);
     dim3 grid(grid_cap(cdiv(items, 256), 128), x->n);
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(chan_mean_kernel<bf16_t>, grid, dim3(256), x->c * 4, as_stream(stream), p),
-        hipLaunchKernelGGL(chan_mean_kernel<float>, grid, dim3(256), x->c * 4, as_stream(stream), p));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(chan_mean_kernel<decltype(t)>, grid, dim3(256), x->c * 4, as_stream(stream), p);
+    });
     return launch_status();
 }
 
@@ -946,9 +926,9 @@ extern "C" int isa_chan_argmax(const isa_tensor* x, const isa_tensor* y, void* s
     if (!tensor_ok(x, 1) || !tensor_ok(y, 1) || x->dtype != y->dtype || x->n != y->n ||
         x->h != y->h || x->w != y->w) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)x->n * x->h * x->w, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(chan_argmax_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), mkview(y)),
-        hipLaunchKernelGGL(chan_argmax_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), mkview(y)));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(chan_argmax_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(x), mkview(y));
+    });
     return launch_status();
 }
 
@@ -956,29 +936,28 @@ extern "C" int isa_nchw_to_nhwc(const float* src, int32_t csrc, const isa_tensor
     if (!src || !tensor_ok(dst, 1) || csrc <= 0 || csrc > dst->c) return ISA_EINVAL;
     const int cp = (dst->c + 7) / 8 * 8;
     if (tensor_ok(dst, 8) && dst->c <= 32 && dst->ld == cp && ((long)dst->h * dst->w) % 4 == 0 &&
-        (reinterpret_cast<uintptr_t>(src) % 16) == 0) {
+        aligned(src, 16)) {
         // the network input (21 -> 24) and other narrow maps whose padded rows are contiguous: row form (pad channels = 0)
         const int gridp = grid_cap(cdiv((long)dst->n * dst->h * dst->w, 1024), 256 * 8);
         const size_t esz = dst->dtype == ISA_BF16 ? 2 : 4;
-#define ROWS(CPV) DISPATCH_T(dst->dtype, \
-            hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<bf16_t, CPV>), dim3(gridp), dim3(256), 1024 * CPV * esz, as_stream(stream), src, mkview(dst), csrc), \
-            hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<float, CPV>), dim3(gridp), dim3(256), 1024 * CPV * esz, as_stream(stream), src, mkview(dst), csrc))
-        if (cp <= 8) ROWS(8); else if (cp <= 16) ROWS(16); else if (cp <= 24) ROWS(24); else ROWS(32);
-#undef ROWS
+        by_dtype(dst->dtype, [&](auto t) { by_width8(dst->c, [&](auto k) {          // dst->c <= 32: k = cp
+            constexpr int CPV = decltype(k)::value;
+            hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<decltype(t), CPV>), dim3(gridp), dim3(256), 1024 * CPV * esz, as_stream(stream), src, mkview(dst), csrc);
+        }); });
         return launch_status();
     }
     const int grid = grid_cap(cdiv((long)dst->n * dst->h * dst->w * dst->c, 256));
-    DISPATCH_T(dst->dtype,
-        hipLaunchKernelGGL((layout_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, as_stream(stream), (float*)src, mkview(dst), csrc),
-        hipLaunchKernelGGL((layout_kernel<float, true>), dim3(grid), dim3(256), 0, as_stream(stream), (float*)src, mkview(dst), csrc));
+    by_dtype(dst->dtype, [&](auto t) {
+        hipLaunchKernelGGL((layout_kernel<decltype(t), true>), dim3(grid), dim3(256), 0, as_stream(stream), (float*)src, mkview(dst), csrc);
+    });
     return launch_status();
 }
 
 extern "C" int isa_nhwc_to_nchw(const isa_tensor* src, float* dst, void* stream) {
     if (!dst || !tensor_ok(src, 1)) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)src->n * src->h * src->w * src->c, 256));
-    DISPATCH_T(src->dtype,
-        hipLaunchKernelGGL((layout_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, as_stream(stream), dst, mkview(src), src->c),
-        hipLaunchKernelGGL((layout_kernel<float, false>), dim3(grid), dim3(256), 0, as_stream(stream), dst, mkview(src), src->c));
+    by_dtype(src->dtype, [&](auto t) {
+        hipLaunchKernelGGL((layout_kernel<decltype(t), false>), dim3(grid), dim3(256), 0, as_stream(stream), dst, mkview(src), src->c);
+    });
     return launch_status();
 }

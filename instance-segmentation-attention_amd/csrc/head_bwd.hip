@@ -8,9 +8,6 @@
 
 namespace {
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
-
 __device__ __forceinline__ float block_sum(float v, float* sh) {
     v = wave_sum(v);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -704,9 +701,6 @@ __global__ __launch_bounds__(256) void adadelta_kernel(float* p, const float* g,
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-    do { if ((dtype) == ISA_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
-
 extern "C" int isa_head_loss(const float* sums, const float* alpha, const int32_t* s_t, int64_t L, int32_t B,
                              const float* level_w, float ce_weight, float lambda_l, float lambda_r, float inv_iter,
                              float* baseline, int32_t training, float* coef, float* adv, float* scal, int32_t iters, void* stream) {
@@ -732,9 +726,9 @@ extern "C" int isa_mask_loss_grad(const isa_tensor* pred, const float* target, c
     if (!tensor_ok(pred, 1) || !tensor_ok(dpred, 1) || pred->c != 2 || dpred->c != 2 || (!target && !onehot) || !coef) return ISA_EINVAL;
     const long L = (long)pred->h * pred->w;
     dim3 grid(grid_cap(cdiv(L, 256), 128), pred->n);
-    DISPATCH_T(pred->dtype,
-        hipLaunchKernelGGL(mask_loss_grad_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, coef, mkview(dpred), accumulate),
-        hipLaunchKernelGGL(mask_loss_grad_kernel<float>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, coef, mkview(dpred), accumulate));
+    by_dtype(pred->dtype, [&](auto t) {
+        hipLaunchKernelGGL(mask_loss_grad_kernel<decltype(t)>, grid, dim3(256), 0, as_stream(stream), mkview(pred), target, onehot, coef, mkview(dpred), accumulate);
+    });
     return launch_status();
 }
 
@@ -755,13 +749,13 @@ extern "C" int isa_maskbn_bwd(const isa_tensor* e, const float* sem, const float
     if (!tensor_ok(e, 1) || !tensor_ok(de, 1) || !sem || !dmerge || !mean_var || !w || !am || !red4 || !k2 || !dw || !db) return ISA_EINVAL;
     const int grid = grid_cap(cdiv((long)e->n * e->h * e->w, 256));
     hipStream_t s = as_stream(stream);
-    DISPATCH_T(e->dtype,
-        hipLaunchKernelGGL(maskbn_bwd_reduce_kernel<bf16_t>, dim3(grid < 1024 ? grid : 1024), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, red4),
-        hipLaunchKernelGGL(maskbn_bwd_reduce_kernel<float>, dim3(grid < 1024 ? grid : 1024), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, red4));
+    by_dtype(e->dtype, [&](auto t) {
+        hipLaunchKernelGGL(maskbn_bwd_reduce_kernel<decltype(t)>, dim3(grid < 1024 ? grid : 1024), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, red4);
+    });
     hipLaunchKernelGGL(maskbn_bwd_finalize_kernel, dim3(1), dim3(64), 0, s, red4, am, mean_var, e->n, eps, train, k2, dw, db);
-    DISPATCH_T(e->dtype,
-        hipLaunchKernelGGL(maskbn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, am, k2, train, mkview(de), accumulate),
-        hipLaunchKernelGGL(maskbn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, am, k2, train, mkview(de), accumulate));
+    by_dtype(e->dtype, [&](auto t) {
+        hipLaunchKernelGGL(maskbn_bwd_apply_kernel<decltype(t)>, dim3(grid), dim3(256), 0, s, mkview(e), sem, dmerge, mean_var, w, eps, am, k2, train, mkview(de), accumulate);
+    });
     return launch_status();
 }
 
@@ -786,17 +780,17 @@ extern "C" int isa_sp_bwd(const isa_tensor* dout, const isa_tensor* x, const flo
     const long items = (long)n * L * ((C + 7) / 8);
     const int grid = grid_keep_cg(grid_cap(cdiv(items, 256)), (C + 7) / 8);
     if (train)
-        DISPATCH_T(x->dtype,
-            hipLaunchKernelGGL(sp_bwd_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 2 * C * 4, s, p),
-            hipLaunchKernelGGL(sp_bwd_reduce_kernel<float>, dim3(grid), dim3(256), 2 * C * 4, s, p));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(sp_bwd_dbeta_kernel<bf16_t>, dim3(grid_cap(cdiv((long)n * L, 256))), dim3(256), 5 * C * 4, s, p),
-        hipLaunchKernelGGL(sp_bwd_dbeta_kernel<float>, dim3(grid_cap(cdiv((long)n * L, 256))), dim3(256), 5 * C * 4, s, p));
+        by_dtype(x->dtype, [&](auto t) {
+            hipLaunchKernelGGL(sp_bwd_reduce_kernel<decltype(t)>, dim3(grid), dim3(256), 2 * C * 4, s, p);
+        });
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(sp_bwd_dbeta_kernel<decltype(t)>, dim3(grid_cap(cdiv((long)n * L, 256))), dim3(256), 5 * C * 4, s, p);
+    });
     hipLaunchKernelGGL(sp_bwd_rowc_kernel, dim3((unsigned)((L + SPB_CHUNK - 1) / SPB_CHUNK), n), dim3(256), 0, s, beta, dbeta, dot, m,
                        rowstat, fcw, sdot, L, ddot, dht, d_fcw, d_fcb);
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(sp_bwd_dx_kernel<bf16_t>, dim3(grid), dim3(256), C * 4, s, p),
-        hipLaunchKernelGGL(sp_bwd_dx_kernel<float>, dim3(grid), dim3(256), C * 4, s, p));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(sp_bwd_dx_kernel<decltype(t)>, dim3(grid), dim3(256), C * 4, s, p);
+    });
     hipLaunchKernelGGL(sp_bwd_params_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, s, red, gw, dht, chansum, n, C, p.inv_L, train,
                        d_gamma, d_beta, d_wv, d_bv, d_lh);
     return launch_status();
@@ -811,18 +805,12 @@ extern "C" int isa_gate_bwd(const isa_tensor* dout, const isa_tensor* up, const 
     const int cgs = (up->c + 7) / 8;
     int sh = 0;
     while ((1 << sh) < cgs) ++sh;
-    if ((1 << sh) == cgs && cgs <= 64) {
-        DISPATCH_T(up->dtype,
-            hipLaunchKernelGGL((gate_bwd_hi_kernel<bf16_t, true>), dim3(g1), dim3(256), 0, s, mkview(dout), mkview(up), gmap, mkview(dup), acc_up, du, sh),
-            hipLaunchKernelGGL((gate_bwd_hi_kernel<float, true>), dim3(g1), dim3(256), 0, s, mkview(dout), mkview(up), gmap, mkview(dup), acc_up, du, sh));
-    } else {
-        DISPATCH_T(up->dtype,
-            hipLaunchKernelGGL((gate_bwd_hi_kernel<bf16_t, false>), dim3(g1), dim3(256), 0, s, mkview(dout), mkview(up), gmap, mkview(dup), acc_up, du, sh),
-            hipLaunchKernelGGL((gate_bwd_hi_kernel<float, false>), dim3(g1), dim3(256), 0, s, mkview(dout), mkview(up), gmap, mkview(dup), acc_up, du, sh));
-    }
-    DISPATCH_T(up->dtype,
-        hipLaunchKernelGGL(gate_bwd_lo_kernel<bf16_t>, dim3(g2), dim3(256), 0, s, du, up->h, up->w, mkview(dpred), acc_pred),
-        hipLaunchKernelGGL(gate_bwd_lo_kernel<float>, dim3(g2), dim3(256), 0, s, du, up->h, up->w, mkview(dpred), acc_pred));
+    by_dtype(up->dtype, [&](auto t) { by_flag((1 << sh) == cgs && cgs <= 64, [&](auto pow2) {
+        hipLaunchKernelGGL((gate_bwd_hi_kernel<decltype(t), decltype(pow2)::value>), dim3(g1), dim3(256), 0, s, mkview(dout), mkview(up), gmap, mkview(dup), acc_up, du, sh);
+    }); });
+    by_dtype(up->dtype, [&](auto t) {
+        hipLaunchKernelGGL(gate_bwd_lo_kernel<decltype(t)>, dim3(g2), dim3(256), 0, s, du, up->h, up->w, mkview(dpred), acc_pred);
+    });
     return launch_status();
 }
 
@@ -834,14 +822,14 @@ extern "C" int isa_se_bwd(const isa_tensor* dxa, const isa_tensor* x, const floa
     const int C = x->c, n = x->n;
     const long items = (long)x->h * x->w * (C / 8);
     dim3 g1(grid_cap(cdiv(items, 256), 128), n);
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(se_bwd_reduce_kernel<bf16_t>, g1, dim3(256), C * 4, s, mkview(dxa), mkview(x), dg),
-        hipLaunchKernelGGL(se_bwd_reduce_kernel<float>, g1, dim3(256), C * 4, s, mkview(dxa), mkview(x), dg));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(se_bwd_reduce_kernel<decltype(t)>, g1, dim3(256), C * 4, s, mkview(dxa), mkview(x), dg);
+    });
     hipLaunchKernelGGL(se_fc_bwd_kernel, dim3(n), dim3(64), (C + hidden) * 4, s, dg, gate, hid, mean, w1, w2, C, hidden, dw1, db1, dw2, db2, dmean);
     const int g3 = grid_cap(cdiv((long)n * items, 256));
-    DISPATCH_T(x->dtype,
-        hipLaunchKernelGGL(se_bwd_apply_kernel<bf16_t>, dim3(g3), dim3(256), 0, s, mkview(dxa), gate, dmean, 1.f / ((float)x->h * x->w), mkview(dx), accumulate),
-        hipLaunchKernelGGL(se_bwd_apply_kernel<float>, dim3(g3), dim3(256), 0, s, mkview(dxa), gate, dmean, 1.f / ((float)x->h * x->w), mkview(dx), accumulate));
+    by_dtype(x->dtype, [&](auto t) {
+        hipLaunchKernelGGL(se_bwd_apply_kernel<decltype(t)>, dim3(g3), dim3(256), 0, s, mkview(dxa), gate, dmean, 1.f / ((float)x->h * x->w), mkview(dx), accumulate);
+    });
     return launch_status();
 }
 
@@ -851,9 +839,9 @@ extern "C" int isa_scale_bc(const isa_tensor* src, const float* s_bc, const isa_
     const int fold = src->n / dst->n;                  // 1: plain; G: sum over the G groups of src
     const long items = (long)dst->n * src->h * src->w * ((src->c + 7) / 8);
     const int grid = grid_cap(cdiv(items, 256));
-    DISPATCH_T(src->dtype,
-        hipLaunchKernelGGL(scale_bc_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(src), s_bc, mkview(dst), accumulate, fold),
-        hipLaunchKernelGGL(scale_bc_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(src), s_bc, mkview(dst), accumulate, fold));
+    by_dtype(src->dtype, [&](auto t) {
+        hipLaunchKernelGGL(scale_bc_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), mkview(src), s_bc, mkview(dst), accumulate, fold);
+    });
     return launch_status();
 }
 

@@ -88,12 +88,11 @@ __global__ __launch_bounds__(256) void image_ex_kernel(const uint8_t* rgb, long 
 extern "C" int isa_image_ex(const uint8_t* rgb, const isa_tensor* out, void* stream) {
     if (!rgb || !out || !out->data || out->c != 21 || out->ld < 21 || out->n <= 0 || out->h <= 0 || out->w <= 0) return ISA_EINVAL;
     if (out->dtype != ISA_F32 && out->dtype != ISA_BF16) return ISA_EINVAL;
-    if (out->ld >= 24 && (out->ld % 8 || reinterpret_cast<uintptr_t>(out->data) % 16)) return ISA_EALIGN;
+    if (out->ld >= 24 && (out->ld % 8 || !aligned(out->data, 16))) return ISA_EALIGN;
     const long pixels = (long)out->n * out->h * out->w;
     const int grid = grid_cap(cdiv(pixels, 256), 256 * 16);
-    if (out->dtype == ISA_BF16)
-        hipLaunchKernelGGL(image_ex_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), rgb, pixels, (bf16_t*)out->data, out->ld);
-    else
-        hipLaunchKernelGGL(image_ex_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), rgb, pixels, (float*)out->data, out->ld);
+    by_dtype(out->dtype, [&](auto t) {
+        hipLaunchKernelGGL(image_ex_kernel<decltype(t)>, dim3(grid), dim3(256), 0, as_stream(stream), rgb, pixels, (decltype(t)*)out->data, out->ld);
+    });
     return launch_status();
 }

@@ -27,8 +27,6 @@ namespace {
 constexpr int TILE = ISA_SEGSORT_TILE, NT = 256, ROUNDS = TILE / NT, PER_WAVE = TILE / 4;
 constexpr uint32_t ONE_BITS = 0x3F800000u, FG_BIT = 0x80000000u;
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
 
 template <typename T, int KT>
 __device__ __forceinline__ void load_row(const T* q, int K, float (&l)[KT]) {
@@ -254,32 +252,6 @@ __global__ __launch_bounds__(NT) void lovasz_grad_kernel(View x, const float* __
     }
 }
 
-template <typename T>
-void launch_keys(const isa_tensor* x, const uint8_t* labels, int c0, int nc, int per_image, uint32_t* keys, uint32_t* vals,
-                 int32_t* G, dim3 grid, hipStream_t s) {
-    const View v = mkview(x);
-    switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((lovasz_keys_kernel<T, 8>), grid, dim3(NT), 0, s, v, labels, c0, nc, per_image, keys, vals, G); break;
-        case 2: hipLaunchKernelGGL((lovasz_keys_kernel<T, 16>), grid, dim3(NT), 0, s, v, labels, c0, nc, per_image, keys, vals, G); break;
-        case 3: hipLaunchKernelGGL((lovasz_keys_kernel<T, 24>), grid, dim3(NT), 0, s, v, labels, c0, nc, per_image, keys, vals, G); break;
-        default: hipLaunchKernelGGL((lovasz_keys_kernel<T, 32>), grid, dim3(NT), 0, s, v, labels, c0, nc, per_image, keys, vals, G); break;
-    }
-}
-
-template <typename T>
-void launch_grad(const isa_tensor* x, const float* gpix, const float* scale, int per_image, const isa_tensor* dx, int acc,
-                 dim3 grid, hipStream_t s) {
-    const View v = mkview(x), dv = mkview(dx);
-    switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((lovasz_grad_kernel<T, 8>), grid, dim3(NT), 0, s, v, gpix, scale, per_image, dv, acc); break;
-        case 2: hipLaunchKernelGGL((lovasz_grad_kernel<T, 16>), grid, dim3(NT), 0, s, v, gpix, scale, per_image, dv, acc); break;
-        case 3: hipLaunchKernelGGL((lovasz_grad_kernel<T, 24>), grid, dim3(NT), 0, s, v, gpix, scale, per_image, dv, acc); break;
-        default: hipLaunchKernelGGL((lovasz_grad_kernel<T, 32>), grid, dim3(NT), 0, s, v, gpix, scale, per_image, dv, acc); break;
-    }
-}
-
-bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 // the logits of isa_sem_loss_k_*: 0 when fine, else the status to return
 int logits_status(const isa_tensor* x) {
     if (!x || !x->data || x->n <= 0 || x->n > 65535 || x->h <= 0 || x->w <= 0 || x->c < 2 || x->c > ISA_SEM_MAX_CLASSES || x->ld < x->c ||
@@ -305,10 +277,10 @@ extern "C" int isa_lovasz_keys(const isa_tensor* logits, const uint8_t* labels, 
     if (!aligned(keys, 4) || !aligned(vals, 4) || !aligned(G, 4)) return ISA_EALIGN;
     const long L = (long)logits->h * logits->w;
     dim3 grid(grid_cap(cdiv(L, NT), 256), logits->n);
-    if (logits->dtype == ISA_BF16)
-        launch_keys<bf16_t>(logits, labels, c0, nc, per_image != 0, keys, vals, G, grid, as_stream(stream));
-    else
-        launch_keys<float>(logits, labels, c0, nc, per_image != 0, keys, vals, G, grid, as_stream(stream));
+    by_dtype(logits->dtype, [&](auto t) { by_width8(logits->c, [&](auto kt) {
+        hipLaunchKernelGGL((lovasz_keys_kernel<decltype(t), decltype(kt)::value>), grid, dim3(NT), 0, as_stream(stream),
+                           mkview(logits), labels, c0, nc, per_image != 0, keys, vals, G);
+    }); });
     return launch_status();
 }
 
@@ -348,15 +320,13 @@ extern "C" int isa_lovasz_grad(const isa_tensor* logits, const float* gpix, cons
     int rc = logits_status(logits);
     if (rc != ISA_OK) return rc;
     if (!gpix || !scale || !dlogits || !dlogits->data) return ISA_EINVAL;
-    if (dlogits->dtype != logits->dtype || dlogits->n != logits->n || dlogits->h != logits->h || dlogits->w != logits->w ||
-        dlogits->c != logits->c || dlogits->ld < dlogits->c || dlogits->ld % 8 || tensor_groups(dlogits) != 1)
-        return ISA_EINVAL;
+    if (!same_shape(dlogits, logits) || dlogits->ld < dlogits->c || dlogits->ld % 8 || tensor_groups(dlogits) != 1) return ISA_EINVAL;
     if (!aligned(dlogits->data, 16) || !aligned(gpix, 4) || !aligned(scale, 4)) return ISA_EALIGN;
     const long L = (long)logits->h * logits->w;
     dim3 grid(grid_cap(cdiv(L, NT), 256), logits->n);
-    if (logits->dtype == ISA_BF16)
-        launch_grad<bf16_t>(logits, gpix, scale, per_image != 0, dlogits, accumulate, grid, as_stream(stream));
-    else
-        launch_grad<float>(logits, gpix, scale, per_image != 0, dlogits, accumulate, grid, as_stream(stream));
+    by_dtype(logits->dtype, [&](auto t) { by_width8(logits->c, [&](auto kt) {
+        hipLaunchKernelGGL((lovasz_grad_kernel<decltype(t), decltype(kt)::value>), grid, dim3(NT), 0, as_stream(stream),
+                           mkview(logits), gpix, scale, per_image != 0, mkview(dlogits), accumulate);
+    }); });
     return launch_status();
 }

@@ -189,7 +189,6 @@ bool seg_geom(int64_t L, SegGeom* g) {
     *g = SegGeom{(long)L, (int)S, chunk};
     return true;
 }
-bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
 
@@ -199,7 +198,7 @@ extern "C" int isa_seg_begin(const float* sem, const float* merge, int32_t n, in
     if (!sem || !merge || !labels || !count || !s_t || !active || !any_active || !part || n <= 0 || n > 65535 ||
         !seg_geom(L, &g))
         return ISA_EINVAL;
-    if (!aligned_to(sem, 16) || !aligned_to(merge, 16) || !aligned_to(labels, 4)) return ISA_EALIGN;
+    if (!aligned(sem, 16) || !aligned(merge, 16) || !aligned(labels, 4)) return ISA_EALIGN;
     hipLaunchKernelGGL(seg_begin_kernel, dim3(g.S, n), dim3(SEG_THREADS), 0, as_stream(stream), sem, merge, g, labels, part);
     hipLaunchKernelGGL(seg_fold_kernel, dim3(1), dim3(SEG_THREADS), 0, as_stream(stream), part, g.S, n, 1, count, active,
                        s_t, any_active);
@@ -213,16 +212,15 @@ extern "C" int isa_seg_claim(const isa_tensor* pred, const float* sem, const flo
     if (!tensor_ok(pred, 2) || pred->c != 2 || pred->n > 65535 || !sem || !merge || !s_t || !labels || !count || !active ||
         !s_next || !any_active || !part || !seg_geom((int64_t)pred->h * pred->w, &g))
         return ISA_EINVAL;
-    if (!aligned_to(sem, 16) || !aligned_to(merge, 16) || !aligned_to(labels, 4)) return ISA_EALIGN;
+    if (!aligned(sem, 16) || !aligned(merge, 16) || !aligned(labels, 4)) return ISA_EALIGN;
     const int n = pred->n, ld = pred->ld;
-    const bool packed = ld == 2 && aligned_to(pred->data, 16);
+    const bool packed = ld == 2 && aligned(pred->data, 16);
     const dim3 grid(g.S, n), block(SEG_THREADS);
     hipStream_t st = as_stream(stream);
-#define SEG_LAUNCH(T, P) hipLaunchKernelGGL((seg_claim_kernel<T, P>), grid, block, 0, st, reinterpret_cast<const T*>(pred->data), \
-                                            ld, sem, merge, s_t, count, active, g, labels, part)
-    if (pred->dtype == ISA_BF16) { if (packed) SEG_LAUNCH(bf16_t, true); else SEG_LAUNCH(bf16_t, false); }
-    else { if (packed) SEG_LAUNCH(float, true); else SEG_LAUNCH(float, false); }
-#undef SEG_LAUNCH
+    by_dtype(pred->dtype, [&](auto t) { by_flag(packed, [&](auto pk) {
+        hipLaunchKernelGGL((seg_claim_kernel<decltype(t), decltype(pk)::value>), grid, block, 0, st, reinterpret_cast<const decltype(t)*>(pred->data),
+                           ld, sem, merge, s_t, count, active, g, labels, part);
+    }); });
     hipLaunchKernelGGL(seg_fold_kernel, dim3(1), dim3(SEG_THREADS), 0, st, part, g.S, n, 0, count, active, s_next, any_active);
     return launch_status();
 }

@@ -16,8 +16,6 @@
 
 namespace {
 
-struct View { void* data; int n, h, w, c, ld; };
-static inline View mkview(const isa_tensor* t) { return View{t->data, t->n, t->h, t->w, t->c, t->ld}; }
 
 constexpr int CFG_HDR = 4;       // cfg[0] use_ce, cfg[1] use_dice, cfg[2] optimize_bg, cfg[3] unused; weights follow
 
@@ -225,32 +223,6 @@ __global__ __launch_bounds__(256) void sem_k_grad_kernel(View x, const uint8_t* 
     }
 }
 
-template <typename T, bool PW>
-int launch_sums(const isa_tensor* x, const uint8_t* labels, const float* cfg, const float* pixw, float* sums, dim3 grid,
-                hipStream_t s) {
-    const View v = mkview(x);
-    switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((sem_k_sums_kernel<T, 8, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
-        case 2: hipLaunchKernelGGL((sem_k_sums_kernel<T, 16, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
-        case 3: hipLaunchKernelGGL((sem_k_sums_kernel<T, 24, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
-        default: hipLaunchKernelGGL((sem_k_sums_kernel<T, 32, PW>), grid, dim3(256), 0, s, v, labels, cfg, pixw, sums); break;
-    }
-    return launch_status();
-}
-
-template <typename T>
-int launch_grad(const isa_tensor* x, const uint8_t* labels, const float* cfg, const float* coef, const float* pixw,
-                const isa_tensor* dx, int acc, dim3 grid, hipStream_t s) {
-    const View v = mkview(x), dv = mkview(dx);
-    switch ((x->c + 7) / 8) {
-        case 1: hipLaunchKernelGGL((sem_k_grad_kernel<T, 8>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
-        case 2: hipLaunchKernelGGL((sem_k_grad_kernel<T, 16>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
-        case 3: hipLaunchKernelGGL((sem_k_grad_kernel<T, 24>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
-        default: hipLaunchKernelGGL((sem_k_grad_kernel<T, 32>), grid, dim3(256), 0, s, v, labels, cfg, coef, pixw, dv, acc); break;
-    }
-    return launch_status();
-}
-
 // logits: 2 <= K <= 32 classes, ld a multiple of 8 and 16-byte aligned rows (the vector loads read whole 8-groups)
 static inline bool logits_ok(const isa_tensor* x) {
     return tensor_ok(x, 8) && x->c >= 2 && x->c <= ISA_SEM_MAX_CLASSES && tensor_groups(x) == 1;
@@ -263,27 +235,29 @@ template <bool PW>
 int sem_k_sums(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* pixw, float* sums,
                void* stream) {
     if (!logits_ok(logits) || !labels || !cfg || !sums || (PW && !pixw)) return ISA_EINVAL;
-    if (PW && reinterpret_cast<uintptr_t>(pixw) % 4 != 0) return ISA_EALIGN;
+    if (PW && !aligned(pixw, 4)) return ISA_EALIGN;
     const long L = (long)logits->h * logits->w;
     dim3 grid(grid_cap(cdiv(L, 256), 64), logits->n);
-    if (logits->dtype == ISA_BF16)
-        return launch_sums<bf16_t, PW>(logits, labels, cfg, pixw, sums, grid, as_stream(stream));
-    return launch_sums<float, PW>(logits, labels, cfg, pixw, sums, grid, as_stream(stream));
+    by_dtype(logits->dtype, [&](auto t) { by_width8(logits->c, [&](auto kt) {
+        hipLaunchKernelGGL((sem_k_sums_kernel<decltype(t), decltype(kt)::value, PW>), grid, dim3(256), 0, as_stream(stream),
+                           mkview(logits), labels, cfg, pixw, sums);
+    }); });
+    return launch_status();
 }
 
 template <bool PW>
 int sem_k_grad(const isa_tensor* logits, const uint8_t* labels, const float* cfg, const float* coef, const float* pixw,
                const isa_tensor* dlogits, int32_t accumulate, void* stream) {
     if (!logits_ok(logits) || !tensor_ok(dlogits, 8) || !labels || !cfg || !coef || (PW && !pixw)) return ISA_EINVAL;
-    if (dlogits->dtype != logits->dtype || dlogits->n != logits->n || dlogits->h != logits->h || dlogits->w != logits->w ||
-        dlogits->c != logits->c)
-        return ISA_EINVAL;
-    if (PW && reinterpret_cast<uintptr_t>(pixw) % 4 != 0) return ISA_EALIGN;
+    if (!same_shape(dlogits, logits)) return ISA_EINVAL;
+    if (PW && !aligned(pixw, 4)) return ISA_EALIGN;
     const long L = (long)logits->h * logits->w;
     dim3 grid(grid_cap(cdiv(L, 256), 128), logits->n);
-    if (logits->dtype == ISA_BF16)
-        return launch_grad<bf16_t>(logits, labels, cfg, coef, pixw, dlogits, accumulate, grid, as_stream(stream));
-    return launch_grad<float>(logits, labels, cfg, coef, pixw, dlogits, accumulate, grid, as_stream(stream));
+    by_dtype(logits->dtype, [&](auto t) { by_width8(logits->c, [&](auto kt) {
+        hipLaunchKernelGGL((sem_k_grad_kernel<decltype(t), decltype(kt)::value>), grid, dim3(256), 0, as_stream(stream),
+                           mkview(logits), labels, cfg, coef, pixw, mkview(dlogits), accumulate);
+    }); });
+    return launch_status();
 }
 }  // namespace
 

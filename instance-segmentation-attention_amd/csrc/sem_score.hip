@@ -43,7 +43,6 @@ bool sm_geom(int64_t L, int P, SmGeom* g) {
     *g = SmGeom{(long)L, (int)S, chunk};
     return true;
 }
-bool sm_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 template <typename T> struct vec16;
 template <> struct vec16<bf16_t> {
@@ -263,8 +262,8 @@ extern "C" int isa_sem_confusion(const isa_tensor* logits, const uint8_t* labels
     const int P = nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : 8;
     SmGeom g;
     if (!sm_geom(L, P, &g)) return ISA_EINVAL;
-    if (!sm_aligned(logits->data, 16) || !sm_aligned(labels, 4) || !sm_aligned(class_map, 4) ||
-        (labels && (!sm_aligned(conf, 8) || !sm_aligned(oob, 4))))
+    if (!aligned(logits->data, 16) || !aligned(labels, 4) || !aligned(class_map, 4) ||
+        (labels && (!aligned(conf, 8) || !aligned(oob, 4))))
         return ISA_EALIGN;
     hipStream_t st = as_stream(stream);
     const int n = logits->n;
@@ -276,14 +275,13 @@ extern "C" int isa_sem_confusion(const isa_tensor* logits, const uint8_t* labels
             return ISA_ELAUNCH;
     }
     const dim3 grid(g.S, n);
-    if (logits->dtype == ISA_BF16) sm_launch<bf16_t>(P, grid, lds, st, logits, labels, g, conf, oob, class_map);
-    else sm_launch<float>(P, grid, lds, st, logits, labels, g, conf, oob, class_map);
+    by_dtype(logits->dtype, [&](auto t) { sm_launch<decltype(t)>(P, grid, lds, st, logits, labels, g, conf, oob, class_map); });
     return launch_status();
 }
 
 extern "C" int isa_sem_scores(const int64_t* conf, int32_t n, int32_t K, double* out, void* stream) {
     if (!conf || !out || n <= 0 || n > 65535 || K < 2 || K > ISA_SEM_MAX_CLASSES) return ISA_EINVAL;
-    if (!sm_aligned(conf, 8) || !sm_aligned(out, 8)) return ISA_EALIGN;
+    if (!aligned(conf, 8) || !aligned(out, 8)) return ISA_EALIGN;
     hipLaunchKernelGGL(sem_scores_kernel, dim3(n), dim3(64), 0, as_stream(stream), conf, (int)K, out);
     return launch_status();
 }

@@ -64,7 +64,7 @@ def _torch_pw(seen, lab_np, crit, weights, bg, pixw):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("K", [2, 5])
+@pytest.mark.parametrize("K", [2, 5, 12, 21, 32])          # every class width of the kernels: 8, 16, 24, 32
 def test_pixel_weighted_kernels_match_float64_autograd(K, dtype):
     L = _lib()
     gbound = 1e-5 if dtype == torch.float32 else 8e-3

@@ -205,6 +205,7 @@ ROW_CASES = [  # c, csrc, n, h, w: ld == rup(c, 8) <= 32, h * w % 4 == 0, aligne
     (1, 1, 2, 24, 20),
     (3, 2, 3, 64, 44),          # 8448 pixels: 8 full 1024-pixel pieces and a partial one
     (8, 7, 2, 24, 20),
+    (12, 11, 2, 8, 10),         # ld = 16: the one row width no other case takes
     (21, 20, 2, 16, 36),        # the network input (21 -> 24)
     (24, 21, 1, 12, 12),
     (32, 31, 3, 64, 44),

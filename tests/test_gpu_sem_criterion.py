@@ -80,7 +80,7 @@ def _rel_l2(a, b):
 
 # ---------------------------------------------------------------------------------------------------------- (a)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("K", [2, 3, 8, 21, 32])
+@pytest.mark.parametrize("K", [2, 3, 8, 12, 21, 32])       # every class width of the kernels: 8, 16, 24, 32
 def test_loss_kernels_match_the_restatement(K, dtype):
     L = _lib()
     gbound = 1e-5 if dtype == torch.float32 else 8e-3

@@ -282,6 +282,8 @@ BN_CASES = [
     # sh = 3, G = 3 with bscale and tanh (ACT_RT): 2040 px per group, iters 2 -> grid 32, 2 trips
     ("sh3-G3-tanh", F32, 6, 30, 34, 64, 3, "tanh", True, "train", {"reduce": (32, 1, 2), "apply": (32, 1, 2)}),
     ("sh3-G2-bs", BF, 4, 30, 30, 64, 2, "none", True, "chain", {"reduce": (29, 1, 2), "apply": (29, 1, 2)}),
+    # fp32 with bscale and no activation (the one dtype x activation x bscale instantiation no other case launches), C = 20
+    ("sh2-c20-none-bs-f32", F32, 2, 9, 11, 20, 1, "none", True, "train"),
     # sh = 4 at the reduce pass's 1024 cap: 263168 px, iters 16 -> walk_grid 1028; reduce capped at 1024 -> 17 trips of
     # 16 px, the 17th covering only 1024 px (64 workgroups); apply keeps 1028 -> 16 trips, the last ragged
     ("sh4-cap1024", BF, 4, 256, 257, 128, 1, "relu6", False, "train", {"reduce": (1024, 1, 17), "apply": (1028, 1, 16)}),
@@ -687,6 +689,33 @@ def test_avgpool2(case):
             ref = ref + old.double()
         check(tag + " bwd acc%d" % acc, dxs.get(), ref, store_bound(dtype))
         dxs.check_neighbours(tag + " bwd")
+
+
+# isa_avgpool3 (3x3 mean, stride 1, zero border, optional per-pixel mask, optional accumulate): C = 16 takes the 8-channel
+# vector kernel, C = 20 the per-element kernel that the head's 24-channel tensors never reach.  2x7x9 pixels.
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("c", [16, 20])
+def test_avgpool3(c, dtype):
+    L = _gpu()[0]
+    n, h, w = 2, 7, 9
+    x = nhwc(n, h * w, c, dtype, seed=54)
+    m = inp((rand(n, h * w, 1, seed=55) > 0).float() * 1.5, dtype)
+    old = nhwc(n, h * w, c, dtype, seed=56)
+    xs, ms = Slice(L, x, h, w, dtype, c0=8), Slice(L, m, h, w, dtype, c0=8)
+    x4 = x.double().view(n, h, w, c).permute(0, 3, 1, 2)
+    mean = F.avg_pool2d(x4, 3, 1, 1).permute(0, 2, 3, 1).reshape(n, h * w, c)       # zero border, always / 9
+    for mask in (False, True):
+        for acc in (0, 1):
+            ys = Slice(L, old, h, w, dtype, c0=8, fill=None if acc else NAN)
+            L.check(L.lib().isa_avgpool3(xs.d(), ms.d() if mask else None, ys.d(), acc, L.stream_ptr()), "isa_avgpool3")
+            torch.cuda.synchronize()
+            ref = mean * m.double() if mask else mean
+            if acc:
+                ref = ref + old.double()
+            tag = "avgpool3 c%d %s mask%d acc%d" % (c, "bf16" if dtype == BF else "f32", mask, acc)
+            check(tag, ys.get(), ref, store_bound(dtype))
+            ys.check_neighbours(tag)
 
 
 # ------------------------------------------------------------------------------------------------ 4. squeeze-excite
