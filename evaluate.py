@@ -84,10 +84,9 @@ def device_scores(map_a, map_b, n_a=None, n_b=None):
     hist = torch.empty(na * nb, dtype=torch.int32, device="cuda")
     oob = torch.empty(1, dtype=torch.int32, device="cuda")
     out = torch.empty(8, dtype=torch.float64, device="cuda")
-    lib, st = L.lib(), L.stream_ptr()
-    L.check(lib.isa_label_pair_hist(L.ptr(ta), L.ptr(tb), 1, ta.numel(), na, nb, L.ptr(hist), L.ptr(oob),
-                                    L.HIST_AGGREGATE, st), "isa_label_pair_hist")
-    L.check(lib.isa_instance_scores(L.ptr(hist), 1, na, nb, L.ptr(ca), L.ptr(cb), L.ptr(out), st), "isa_instance_scores")
+    lib, st = L.checked(), L.stream_ptr()
+    lib.isa_label_pair_hist(ta, tb, 1, ta.numel(), na, nb, hist, oob, L.HIST_AGGREGATE, st)
+    lib.isa_instance_scores(hist, 1, na, nb, ca, cb, out, st)
     assert int(oob.cpu()[0]) == 0
     return out.cpu().numpy()
 

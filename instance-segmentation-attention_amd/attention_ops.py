@@ -41,9 +41,8 @@ def scaled_dot_product_attention(q, k, v, temperature, mask=None, return_attn=Tr
     attn = torch.empty(heads * b, lq, Lk, dtype=torch.float32, device=q.device) if return_attn else None
     m = mask.to(torch.uint8).contiguous() if mask is not None else None
     ws = _ws(q.device)
-    L.check(L.lib().isa_sdp_attention(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(m), L.ptr(out), L.ptr(attn), b, lq, Lk, dk, dv,
-                                      float(temperature), L.dtype_code(q.dtype), heads, 1 if mask_per_head else 0,
-                                      L.ptr(ws), ws.numel(), int(tile_keys), L.stream_ptr()), "isa_sdp_attention")
+    L.checked().isa_sdp_attention(q, k, v, m, out, attn, b, lq, Lk, dk, dv, float(temperature), L.dtype_code(q.dtype), heads,
+                                  1 if mask_per_head else 0, ws, ws.numel(), int(tile_keys), L.stream_ptr())
     return out, attn
 
 
@@ -57,9 +56,8 @@ def scaled_dot_product_attention_backward(q, k, v, temperature, out, attn, d_out
     q, k, v, out, d_out = (t.contiguous() for t in (q, k, v, out, d_out))
     dq = torch.zeros(b, lq, dq_, dtype=torch.float32, device=q.device)
     dk, dv = torch.empty_like(k), torch.empty_like(v)
-    L.check(L.lib().isa_sdp_attention_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(attn.contiguous()), L.ptr(out), L.ptr(d_out),
-                                          L.ptr(dq), L.ptr(dk), L.ptr(dv), b, lq, Lk, dk_, dv_, float(temperature),
-                                          L.dtype_code(q.dtype), heads, L.stream_ptr()), "isa_sdp_attention_bwd")
+    L.checked().isa_sdp_attention_bwd(q, k, v, attn.contiguous(), out, d_out, dq, dk, dv, b, lq, Lk, dk_, dv_,
+                                      float(temperature), L.dtype_code(q.dtype), heads, L.stream_ptr())
     return dq, dk, dv
 
 
@@ -74,8 +72,8 @@ class ScaledDotProductAttention(nn.Module):
         if last:
             b, lq, d = q.shape
             out = torch.empty(b, lq, k.shape[1], dtype=torch.float32, device=q.device)
-            L.check(L.lib().isa_sdp_scores(L.ptr(q.contiguous()), L.ptr(k.contiguous()), L.ptr(out), b, 1, lq, k.shape[1], d,
-                                           L.dtype_code(q.dtype), 0, L.stream_ptr()), "isa_sdp_scores")
+            L.checked().isa_sdp_scores(q.contiguous(), k.contiguous(), out, b, 1, lq, k.shape[1], d,
+                                       L.dtype_code(q.dtype), 0, L.stream_ptr())
             return out                           # raw q k^T (utils.py:310-313); MultiHeadAttention applies the sigmoid
         return scaled_dot_product_attention(q, k, v, self.temperature, mask)
 
@@ -84,8 +82,7 @@ def _linear_ln(x, w, bias, residual=None, gamma=None, beta=None, eps=1e-5):
     rows, k = x.shape
     n = w.shape[0]
     y = torch.empty(rows, n, dtype=torch.float32, device=x.device)
-    L.check(L.lib().isa_linear_ln(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(residual), L.ptr(gamma), L.ptr(beta), float(eps),
-                                  rows, k, n, L.ptr(y), L.stream_ptr()), "isa_linear_ln")
+    L.checked().isa_linear_ln(x, w, bias, residual, gamma, beta, float(eps), rows, k, n, y, L.stream_ptr())
     return y
 
 
@@ -162,8 +159,8 @@ class MultiHeadAttention(nn.Module):
         kp, vp = self._project_kv(k, v)
         if last:
             out = torch.empty(self.n_head * b, lq, Lk, dtype=torch.float32, device=q.device)
-            L.check(L.lib().isa_sdp_scores(L.ptr(qp), L.ptr(kp), L.ptr(out), b, self.n_head, lq, Lk, self.d_k,
-                                           L.dtype_code(self.storage), 1, L.stream_ptr()), "isa_sdp_scores")
+            L.checked().isa_sdp_scores(qp, kp, out, b, self.n_head, lq, Lk, self.d_k, L.dtype_code(self.storage), 1,
+                                       L.stream_ptr())
             return out.squeeze(1), None
         o, attn = scaled_dot_product_attention(qp, kp, vp, math.sqrt(self.d_k), mask, heads=self.n_head)
         y = _linear_ln(o.float().reshape(b * lq, -1).contiguous(), self.fc.weight.detach().float().contiguous(),
@@ -195,8 +192,7 @@ def local_dilated_attention(Q, K, V, nomask, dilation, dtype=torch.float32, scal
     scale = Q.shape[1] ** -0.5 if scale is None else scale
     out = Act(torch.empty(n, h, w, (dv + 7) // 8 * 8, dtype=dtype, device=V.device), 0, dv)
     nm = nomask.reshape(n, -1).float().contiguous()
-    L.check(L.lib().isa_local_attention(qa.d(), ka.d(), va.d(), L.ptr(nm), out.d(), int(dilation), float(scale),
-                                        L.stream_ptr()), "isa_local_attention")
+    L.checked().isa_local_attention(qa.d(), ka.d(), va.d(), nm, out.d(), int(dilation), float(scale), L.stream_ptr())
     return out.nchw()
 
 
@@ -249,14 +245,13 @@ class ScalePDAttention(nn.Module):
         for g in range(G):
             idx = torch.tensor([(bi * G + g) % b for bi in range(b)], device=dev)
             nmg = nm[idx].contiguous()
-            L.check(L.lib().isa_local_attention(QK.slice(g * 2 * dk, dk).d(), QK.slice(g * 2 * dk + dk, dk).d(),
-                                                V.slice(g * dv, dv).d(), L.ptr(nmg), att.slice(g * dv, dv).d(), int(self.d),
-                                                float(cin) ** -0.5, L.stream_ptr()), "isa_local_attention")
+            L.checked().isa_local_attention(QK.slice(g * 2 * dk, dk).d(), QK.slice(g * 2 * dk + dk, dk).d(),
+                                            V.slice(g * dv, dv).d(), nmg, att.slice(g * dv, dv).d(), int(self.d),
+                                            float(cin) ** -0.5, L.stream_ptr())
         out = H.conv(att, "fc.weight", "fc.bias", dm)
         y = H.engine.new_act(b, h, w, dm)
         sums = torch.zeros(b * 2 * dm, dtype=torch.float32, device=dev)
-        L.check(L.lib().isa_instance_norm_res(out.d(), xa.d(), y.d(), 1e-5, L.ptr(sums), L.stream_ptr()),
-                "isa_instance_norm_res")
+        L.checked().isa_instance_norm_res(out.d(), xa.d(), y.d(), 1e-5, sums, L.stream_ptr())
         return y.nchw()
 
 
@@ -266,5 +261,5 @@ def point_query_mask(q, enc, dtype=torch.float32):
     n, c, h, w = enc.shape
     out = torch.empty(n, h * w, dtype=torch.float32, device=enc.device)
     qq = q.float().contiguous()
-    L.check(L.lib().isa_point_query(L.ptr(qq), ea.d(), L.ptr(out), L.stream_ptr()), "isa_point_query")
+    L.checked().isa_point_query(qq, ea.d(), out, L.stream_ptr())
     return out

@@ -100,8 +100,7 @@ def d4_augment(tensors, ops, device="cuda"):
         shape = (n, w, h) + tuple(src.shape[3:]) if swap else tuple(src.shape)
         dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
         c = 1 if t.dim() == 3 else t.shape[3]
-        L.check(L.lib().isa_d4_augment(L.ptr(src), L.ptr(dst), n, h, w, c, 1 if swap else 0, L.ptr(ops_dev),
-                                       L.stream_ptr()), "isa_d4_augment")
+        L.checked().isa_d4_augment(src, dst, n, h, w, c, 1 if swap else 0, ops_dev, L.stream_ptr())
         out.append(dst)
     return out
 
@@ -158,8 +157,7 @@ def rotate_nearest(tensors, angle, device="cuda"):
         m, (nw, nh) = g
         coef = (C.c_int32 * 6)(*_fixed_coeffs(m))
         dst = torch.empty((n, nh, nw, c), dtype=torch.uint8, device=src.device)
-        L.check(L.lib().isa_rotate_nearest_u8(L.ptr(src), n, h, w, c, L.ptr(dst), nh, nw, coef, L.stream_ptr()),
-                "isa_rotate_nearest_u8")
+        L.checked().isa_rotate_nearest_u8(src, n, h, w, c, dst, nh, nw, coef, L.stream_ptr())
         out.append(dst)
     return out
 
@@ -194,8 +192,7 @@ def rotate_image(rgb, angle, bg, device="cuda"):
     mat = (C.c_double * 6)(*m)
     bgc = (C.c_uint8 * 4)(*([int(v) for v in bg] + [255] * (4 - len(bg))))
     dst = torch.empty((n, nh, nw, c), dtype=torch.uint8, device=src.device)
-    L.check(L.lib().isa_rotate_bilinear_u8(L.ptr(src), n, h, w, c, L.ptr(dst), nh, nw, mat, bgc, L.stream_ptr()),
-            "isa_rotate_bilinear_u8")
+    L.checked().isa_rotate_bilinear_u8(src, n, h, w, c, dst, nh, nw, mat, bgc, L.stream_ptr())
     return dst
 
 
@@ -224,12 +221,12 @@ def center_cut(rgb, sem, planes, n_objects, draw, out_h, out_w, max_planes=32, d
     chosen centre in the row-major list of pixels covered by exactly one plane.  Returns (rgb, sem, planes [1,h',w',
     max_planes] with the surviving planes first, n_objects') - the has-object filter (window sum > 30) drops planes."""
     from . import lib as L
-    lib, st = L.lib(), L.stream_ptr()
+    lib, st = L.checked(), L.stream_ptr()
     _, H, W, K = planes.shape
     single = torch.empty((1, H, W), dtype=torch.uint8, device=device)
     rows = torch.empty((1, H), dtype=torch.int32, device=device)
     real = planes if n_objects == K else planes[..., :n_objects].contiguous()
-    L.check(lib.isa_cover_rows_u8(L.ptr(real), 1, H, W, n_objects, L.ptr(single), L.ptr(rows), st), "isa_cover_rows_u8")
+    lib.isa_cover_rows_u8(real, 1, H, W, n_objects, single, rows, st)
     counts = rows[0].cpu().numpy().astype("int64")
     total = int(counts.sum())
     assert total > 0, "no pixel is covered by exactly one instance (the reference raises here too)"
@@ -241,17 +238,15 @@ def center_cut(rgb, sem, planes, n_objects, draw, out_h, out_w, max_planes=32, d
     center = (r, int(cols[j]))
     y0, x0, hh, ww = center_cut_window(H, W, center, out_h, out_w)
     sums = torch.zeros((1, n_objects), dtype=torch.int64, device=device)
-    L.check(lib.isa_plane_sums_u8(L.ptr(real), 1, H, W, n_objects, y0, x0, hh, ww, L.ptr(sums), st), "isa_plane_sums_u8")
+    lib.isa_plane_sums_u8(real, 1, H, W, n_objects, y0, x0, hh, ww, sums, st)
     keep = [i for i, v in enumerate(sums[0].cpu().tolist()) if v > 30]
     chan = torch.tensor(keep + [-1] * (max_planes - len(keep)), dtype=torch.int32, device=device)
     p2 = torch.empty((1, hh, ww, max_planes), dtype=torch.uint8, device=device)
-    L.check(lib.isa_crop_planes_u8(L.ptr(real), 1, H, W, n_objects, y0, x0, L.ptr(p2), hh, ww, max_planes, L.ptr(chan), st),
-            "isa_crop_planes_u8")
+    lib.isa_crop_planes_u8(real, 1, H, W, n_objects, y0, x0, p2, hh, ww, max_planes, chan, st)
     r2 = torch.empty((1, hh, ww, rgb.shape[3]), dtype=torch.uint8, device=device)
-    L.check(lib.isa_crop_planes_u8(L.ptr(rgb), 1, H, W, rgb.shape[3], y0, x0, L.ptr(r2), hh, ww, rgb.shape[3], None, st),
-            "isa_crop_planes_u8")
+    lib.isa_crop_planes_u8(rgb, 1, H, W, rgb.shape[3], y0, x0, r2, hh, ww, rgb.shape[3], None, st)
     s2 = torch.empty((1, hh, ww, 1), dtype=torch.uint8, device=device)
-    L.check(lib.isa_crop_planes_u8(L.ptr(sem), 1, H, W, 1, y0, x0, L.ptr(s2), hh, ww, 1, None, st), "isa_crop_planes_u8")
+    lib.isa_crop_planes_u8(sem, 1, H, W, 1, y0, x0, s2, hh, ww, 1, None, st)
     return r2, s2, p2, len(keep)
 
 
@@ -267,12 +262,11 @@ def resize_bilinear(images, size, device="cuda"):
     assert src.dtype == torch.uint8 and src.dim() == 4
     n, h0, w0, c = src.shape
     dst = torch.empty((n, h, w, c), dtype=torch.uint8, device=src.device)
-    need = int(L.lib().isa_resize_bilinear_ws_bytes(n, h0, w0, c, h, w))
+    need = int(L.checked().isa_resize_bilinear_ws_bytes(n, h0, w0, c, h, w))
     ws = _RESIZE_WS.get(src.device)
     if ws is None or ws.numel() < need:
         ws = _RESIZE_WS[src.device] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=src.device)
-    L.check(L.lib().isa_resize_bilinear_u8(L.ptr(src), n, h0, w0, c, L.ptr(dst), h, w, L.ptr(ws), ws.numel(), L.stream_ptr()),
-            "isa_resize_bilinear_u8")
+    L.checked().isa_resize_bilinear_u8(src, n, h0, w0, c, dst, h, w, ws, ws.numel(), L.stream_ptr())
     return dst
 
 
@@ -288,13 +282,12 @@ def resize_lanczos(images, size, device="cuda"):
     n, h0, w0, c = src.shape
     dst = torch.empty((n, h, w, c), dtype=torch.uint8, device=src.device)
     need = C.c_int64(0)
-    L.check(L.lib().isa_resize_lanczos_ws_bytes(n, h0, w0, c, h, w, C.byref(need)), "isa_resize_lanczos_ws_bytes")
+    L.checked().isa_resize_lanczos_ws_bytes(n, h0, w0, c, h, w, C.byref(need))
     need = need.value
     ws = _RESIZE_WS.get(src.device)
     if ws is None or ws.numel() < need:
         ws = _RESIZE_WS[src.device] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=src.device)
-    L.check(L.lib().isa_resize_lanczos_u8(L.ptr(src), n, h0, w0, c, L.ptr(dst), h, w, L.ptr(ws), ws.numel(), L.stream_ptr()),
-            "isa_resize_lanczos_u8")
+    L.checked().isa_resize_lanczos_u8(src, n, h0, w0, c, dst, h, w, ws, ws.numel(), L.stream_ptr())
     return dst
 
 
@@ -362,8 +355,7 @@ def photometric(rgb, programs, device="cuda", out=None):
     sums = torch.empty(n, dtype=torch.int64, device=src.device) if contrast else None
     dst = torch.empty_like(src) if out is None else out
     assert dst.is_contiguous() and dst.dtype == torch.uint8 and dst.shape == src.shape and dst.device == src.device
-    L.check(L.lib().isa_photometric_u8(L.ptr(src), L.ptr(dst), n, h, w, L.ptr(progs), int(contrast), L.ptr(sums),
-                                       L.stream_ptr()), "isa_photometric_u8")
+    L.checked().isa_photometric_u8(src, dst, n, h, w, progs, int(contrast), sums, L.stream_ptr())
     return dst
 
 
@@ -404,8 +396,8 @@ def elastic_field(noise, alpha, sigma, device="cuda"):
     taps, radius = gaussian_taps(sigma)
     disp = torch.empty_like(src)
     scratch = torch.empty(L.elastic_scratch_bytes(n, h, w), dtype=torch.uint8, device=src.device)
-    L.check(L.lib().isa_elastic_field(L.ptr(src), L.ptr(a), n, h, w, taps.ctypes.data_as(C.c_void_p), radius, L.ptr(disp),
-                                      L.ptr(scratch), scratch.numel(), L.stream_ptr()), "isa_elastic_field")
+    L.checked().isa_elastic_field(src, a, n, h, w, taps.ctypes.data_as(C.c_void_p), radius, disp, scratch, scratch.numel(),
+                                  L.stream_ptr())
     return disp
 
 
@@ -426,8 +418,7 @@ def warp(tensors, disp, modes, device="cuda"):
         assert tuple(src.shape[:3]) == tuple(d.shape[:3]), (tuple(src.shape), tuple(d.shape))
         n, h, w = src.shape[:3]
         dst = torch.empty_like(src)
-        L.check(L.lib().isa_warp_u8(L.ptr(src), L.ptr(d), n, h, w, 1 if t.dim() == 3 else t.shape[3], int(mode), L.ptr(dst),
-                                    L.stream_ptr()), "isa_warp_u8")
+        L.checked().isa_warp_u8(src, d, n, h, w, 1 if t.dim() == 3 else t.shape[3], int(mode), dst, L.stream_ptr())
         out.append(dst)
     return out
 
@@ -440,7 +431,7 @@ def elastic(rgb, sem, planes, n_objects, disp, max_planes=32, device="cuda"):
     the centre cut does); an image that would keep no plane is returned unwarped with its count unchanged.  Returns
     (rgb, sem, planes [n,h,w,max_planes], n_objects as a list)."""
     from . import lib as L
-    lib, st = L.lib(), L.stream_ptr()
+    lib, st = L.checked(), L.stream_ptr()
     n, h, w, K = planes.shape
     if torch.is_tensor(n_objects):
         n_objects = n_objects.reshape(-1).tolist()
@@ -453,7 +444,7 @@ def elastic(rgb, sem, planes, n_objects, disp, max_planes=32, device="cuda"):
         p2, K = full, max_planes
         counts = [min(k, K) for k in counts]
     sums = torch.zeros((n, K), dtype=torch.int64, device=p2.device)
-    L.check(lib.isa_plane_sums_u8(L.ptr(p2), n, h, w, K, 0, 0, h, w, L.ptr(sums), st), "isa_plane_sums_u8")
+    lib.isa_plane_sums_u8(p2, n, h, w, K, 0, 0, h, w, sums, st)
     sums = sums.cpu().tolist()
     out_counts = list(counts)
     for b in range(n):
@@ -467,8 +458,7 @@ def elastic(rgb, sem, planes, n_objects, disp, max_planes=32, device="cuda"):
             continue
         chan = torch.tensor(keep + [-1] * (K - len(keep)), dtype=torch.int32, device=p2.device)
         packed = torch.empty((1, h, w, K), dtype=torch.uint8, device=p2.device)
-        L.check(lib.isa_crop_planes_u8(L.ptr(p2[b]), 1, h, w, K, 0, 0, L.ptr(packed), h, w, K, L.ptr(chan), st),
-                "isa_crop_planes_u8")
+        lib.isa_crop_planes_u8(p2[b], 1, h, w, K, 0, 0, packed, h, w, K, chan, st)
         p2[b] = packed[0]
         out_counts[b] = len(keep)
     return rgb2, sem2, p2, out_counts
@@ -520,9 +510,8 @@ def copy_paste(rgb, sem, planes, n_objects, src, select, flip, shift, min_area=1
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     assert scratch.dtype == torch.uint8 and scratch.device == dev
-    L.check(L.lib().isa_copy_paste_u8(L.ptr(rgb), L.ptr(sem), L.ptr(planes), L.ptr(nobj), L.ptr(xform), L.ptr(sel), n, h, w, c, k,
-                                      int(min_area), L.ptr(rgb2), L.ptr(sem2), L.ptr(p2), L.ptr(n_out), L.ptr(plan),
-                                      L.ptr(scratch), scratch.numel(), L.stream_ptr()), "isa_copy_paste_u8")
+    L.checked().isa_copy_paste_u8(rgb, sem, planes, nobj, xform, sel, n, h, w, c, k, int(min_area), rgb2, sem2, p2, n_out,
+                                  plan, scratch, scratch.numel(), L.stream_ptr())
     return rgb2, sem2, p2, n_out, plan
 
 
@@ -579,10 +568,9 @@ def device_collate_targets(planes, sem, ops=None, size=256, device="cuda"):
     st = L.stream_ptr()
     p2 = torch.empty((n, size, size, k), dtype=torch.uint8, device=device)
     s2 = torch.empty((n, size, size, 1), dtype=torch.uint8, device=device)
-    L.check(L.lib().isa_resize_nearest_u8(L.ptr(planes), n, h0, w0, k, L.ptr(p2), size, size, st), "isa_resize_nearest_u8")
-    L.check(L.lib().isa_resize_nearest_u8(L.ptr(sem4), n, h0, w0, 1, L.ptr(s2), size, size, st), "isa_resize_nearest_u8")
+    L.checked().isa_resize_nearest_u8(planes, n, h0, w0, k, p2, size, size, st)
+    L.checked().isa_resize_nearest_u8(sem4, n, h0, w0, 1, s2, size, size, st)
     ins_out = torch.empty((n, k, size, size), dtype=torch.int64, device=device)
     sem_out = torch.empty((n, 2, size, size), dtype=torch.int64, device=device)
-    L.check(L.lib().isa_collate_targets(L.ptr(p2), L.ptr(s2), n, size, size, k, L.ptr(ins_out), L.ptr(sem_out), st),
-            "isa_collate_targets")
+    L.checked().isa_collate_targets(p2, s2, n, size, size, k, ins_out, sem_out, st)
     return sem_out, ins_out

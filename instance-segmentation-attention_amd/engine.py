@@ -57,7 +57,7 @@ class PendingFin:
             return
         E = self.eng
         E.bn_finalize(self.stats, self.count, self.pre, self._running(), self.scale, self.shift, self.mean, self.invstd,
-                      self.c, self.groups, self.rep, "isa_bn_finalize")
+                      self.c, self.groups, self.rep)
         self.done.add(E.cur)
 
     def inline(self, pro):
@@ -68,7 +68,7 @@ class PendingFin:
         d = L.IsaBnFin(self.stats.data_ptr(), a(P.ptr(self.pre + ".weight")), a(P.ptr(self.pre + ".bias")), a(rm), a(rv),
                        self.scale.data_ptr(), self.shift.data_ptr(), self.mean.data_ptr(), self.invstd.data_ptr(),
                        self.count, E.BN_MOMENTUM, E.BN_EPS, self.rep)
-        pc = L.IsaPro(L.ptr(pro.scale), L.ptr(pro.shift), L.ptr(pro.bscale), pro.act, C.pointer(d))
+        pc = L.IsaPro(L.addr(pro.scale), L.addr(pro.shift), L.addr(pro.bscale), pro.act, C.pointer(d))
         self.keep.append((d, pc))
         self.done.add(E.cur)
         return C.byref(pc)
@@ -81,7 +81,7 @@ class Pro:
 
     def __init__(self, scale=None, shift=None, act=L.ACT_NONE, bscale=None, fin=None):
         self.scale, self.shift, self.act, self.bscale, self.fin = scale, shift, act, bscale, fin
-        self._c = L.IsaPro(L.ptr(scale), L.ptr(shift), L.ptr(bscale), act, None)
+        self._c = L.IsaPro(L.addr(scale), L.addr(shift), L.addr(bscale), act, None)
 
     def c(self):
         if self.fin is not None:
@@ -384,9 +384,8 @@ class Packer:
     def pack(self):
         if self.table is None:
             self.finalize()
-        L.check(L.lib().isa_pack_weights(L.ptr(self.table), len(self.entries), L.ptr(self.kmap_dev),
-                                         L.ptr(self.params.flat), L.ptr(self.buf),
-                                         L.dtype_code(self.dtype), L.stream_ptr()), "isa_pack_weights")
+        L.checked().isa_pack_weights(self.table, len(self.entries), self.kmap_dev, self.params.flat, self.buf,
+                                     L.dtype_code(self.dtype), L.stream_ptr())
 
     def ptr(self, key):
         e = self.index[key]
@@ -513,8 +512,7 @@ class GradBook:
             for lo, hi in merged:
                 a = Act(self.shared[p], lo, hi - lo)
                 acc = self.claim(a, eng)
-                L.check(eng.lib.isa_axpy(Act(side, lo, hi - lo).d(), self.grad_of(a).d(), 1.0, acc, eng.st()),
-                        "isa_axpy(merge shared grad)")
+                eng.lib.isa_axpy(Act(side, lo, hi - lo).d(), self.grad_of(a).d(), 1.0, acc, eng.st())
             self.written[key] = []
 
 
@@ -567,7 +565,7 @@ class Engine:
         self.bn_running_queue: List[tuple] = []
         self.bn_train = False          # batch statistics + running-stat updates
         self.record = False            # build the backward tape
-        self.lib = _ProfiledLib(L.lib(), self)
+        self.lib = _ProfiledLib(L.checked(), self)
         self.ws = torch.empty(16 << 20, dtype=torch.float32, device=device)   # 64 MB reduction workspace
         self.profile = False           # when True every launch is bracketed by HIP events
         self.prof_events = []          # (entry point, start event, end event, algorithmic bytes)
@@ -703,20 +701,19 @@ class Engine:
             for i, (stats, count, pre, c) in enumerate(run):
                 arr[i] = L.IsaBnUpd(stats.data_ptr(), P.ptr(pre + ".running_mean").value, P.ptr(pre + ".running_var").value,
                                     count, c)
-            L.check(self.lib.isa_bn_running_update(arr, len(run), self.BN_MOMENTUM, self.st()), "isa_bn_running_update")
+            self.lib.isa_bn_running_update(arr, len(run), self.BN_MOMENTUM, self.st())
         self.bn_running_queue = []
 
     def running_ptrs(self, pre):
         P = self.params
         return P.ptr(pre + ".running_mean"), P.ptr(pre + ".running_var")
 
-    def bn_finalize(self, stats, count, pre, running, scale, shift, mean, invstd, c, groups, rep, label):
+    def bn_finalize(self, stats, count, pre, running, scale, shift, mean, invstd, c, groups, rep):
         """The stand-alone isa_bn_finalize launch.  stats = None: eval constants (count unread); running = None: leave them."""
         P = self.params
         rm, rv = running or (None, None)
-        L.check(self.lib.isa_bn_finalize(L.ptr(stats), count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"), rm, rv,
-                                         self.BN_MOMENTUM, self.BN_EPS, L.ptr(scale), L.ptr(shift), L.ptr(mean),
-                                         L.ptr(invstd), c, groups, rep, self.st()), label)
+        self.lib.isa_bn_finalize(stats, count, P.ptr(pre + ".weight"), P.ptr(pre + ".bias"), rm, rv, self.BN_MOMENTUM,
+                                 self.BN_EPS, scale, shift, mean, invstd, c, groups, rep, self.st())
 
     def _finalize_train(self, stats, count, pre, c, scale, shift, mean, invstd, groups=1):
         """Train-mode finalize of one BatchNorm.  With inline_fin (default) nothing is launched here: the PendingFin that is
@@ -729,7 +726,7 @@ class Engine:
             fin = PendingFin(self, stats, count, pre, c, scale, shift, mean, invstd, groups, rep, running_taken=defer)
         else:
             self.bn_finalize(stats, count, pre, None if defer else self.running_ptrs(pre), scale, shift, mean, invstd,
-                             c, groups, rep, "isa_bn_finalize")
+                             c, groups, rep)
         if defer:
             self.bn_running_queue.append((stats, count, pre, c))
         self.params.int_buffers[pre + ".num_batches_tracked"] += groups * rep
@@ -755,8 +752,7 @@ class Engine:
     def refresh_eval_bn(self):
         """Recompute the cached eval-mode BN constants in place (same buffers: captured graphs keep reading them)."""
         for pre, consts in self.eval_bn_cache.items():
-            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *consts, consts[0].numel(), 1, 1,
-                             "isa_bn_finalize(eval refresh)")
+            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *consts, consts[0].numel(), 1, 1)
         self.eval_bn_stale = False
 
     def scratch(self, numel) -> torch.Tensor:
@@ -791,15 +787,14 @@ class Engine:
 
     # ------------------------------------------------------------------ tiny helpers
     def fill_zero(self, a: Act):
-        L.check(self.lib.isa_axpy(a.d(), a.d(), 0.0, 0, self.st()), "isa_axpy(zero)")
+        self.lib.isa_axpy(a.d(), a.d(), 0.0, 0, self.st())
 
     def copy(self, src: Act, dst: Act):
-        L.check(self.lib.isa_axpy(src.d(), dst.d(), 1.0, 0, self.st()), "isa_axpy(copy)")
+        self.lib.isa_axpy(src.d(), dst.d(), 1.0, 0, self.st())
         if self.record and src.needs_grad:
             def bwd():
                 acc = self.grads.claim(src, self)
-                L.check(self.lib.isa_axpy(self.grads.grad_of(dst).d(), self.grads.grad_of(src).d(), 1.0, acc,
-                                          self.st()), "isa_axpy(bwd)")
+                self.lib.isa_axpy(self.grads.grad_of(dst).d(), self.grads.grad_of(src).d(), 1.0, acc, self.st())
             self.tape.append(bwd)
 
     # ------------------------------------------------------------------ convolutions
@@ -831,7 +826,7 @@ class Engine:
         if cached is None:
             cached = tuple(torch.empty(c, dtype=torch.float32, device=self.device) for _ in range(4))
             self.eval_bn_cache[pre] = cached
-            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *cached, c, 1, 1, "isa_bn_finalize")
+            self.bn_finalize(None, 1.0, pre, self.running_ptrs(pre), *cached, c, 1, 1)
             self._eval_bn_filled(pre)
         else:
             self._eval_bn_wait(pre)
@@ -849,8 +844,8 @@ class Engine:
             self.next_bytes = (x.n * x.h * x.w * x.c + (1 + (res is not None)) * out.n * out.h * out.w * out.c) * esz
         ep = L.IsaConvEp(L.addr(scale), L.addr(shift), act, C.addressof(res._c) if res is not None else None)
         self._keep_ep = (ep, res)                                  # ctypes argument lifetime: until the call returns
-        L.check(self.lib.isa_conv_gemm_ep(x.d(), x.p(), self.packer.ptr(reg["fwd"]), reg["kp"], None, out.d(),
-                                          L.IN_3X3 if taps == 9 else L.IN_1X1, C.byref(ep), self.st()), "isa_conv_gemm_ep")
+        self.lib.isa_conv_gemm_ep(x.d(), x.p(), self.packer.ptr(reg["fwd"]), reg["kp"], None, out.d(),
+                                  L.IN_3X3 if taps == 9 else L.IN_1X1, C.byref(ep), self.st())
         return out
 
     def block_v1_eval_fusable(self, x: Act, cout):
@@ -872,8 +867,8 @@ class Engine:
             self.next_bytes = (x.n * x.h * x.w * x.c + (1 + (res is not None)) * out.n * out.h * out.w * out.c) * esz
         ep = L.IsaConvEp(L.addr(s2), L.addr(h2), L.ACT_NONE, C.addressof(res._c) if res is not None else None)
         self._keep_ep = (ep, res)
-        L.check(self.lib.isa_dwpw_eval(x.d(), self.packer.ptr(rd["fwd"]), L.ptr(s1), L.ptr(h1), self.packer.ptr(rc["fwd"]),
-                                       rc["kp"], C.byref(ep), out.d(), self.st()), "isa_dwpw_eval")
+        self.lib.isa_dwpw_eval(x.d(), self.packer.ptr(rd["fwd"]), s1, h1, self.packer.ptr(rc["fwd"]), rc["kp"], C.byref(ep),
+                               out.d(), self.st())
         return out
 
     def conv(self, x: Act, wname, out: Act, *, taps=1, bias=None, stats=False, kmap=None,
@@ -907,23 +902,20 @@ class Engine:
                 pk = self.packer
                 if self.profile and not transposed:
                     self.next_bytes = (x.n * x.h * x.w * x.c + dy.n * dy.h * dy.w * dy.c) * x.buf.element_size()
-                L.check(self.lib.isa_conv_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
-                                                self.params.gptr(bias) if bias else None, wg_in, out_mode,
-                                                pk.kmap_ptr(reg["fwd"]), ksrc, L.ptr(self.ws), self.ws.numel(),
-                                                self.defer_handle(), self.st()), "isa_conv_wgrad")
+                self.lib.isa_conv_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
+                                        self.params.gptr(bias) if bias else None, wg_in, out_mode, pk.kmap_ptr(reg["fwd"]),
+                                        ksrc, self.ws, self.ws.numel(), self.defer_handle(), self.st())
                 if x.needs_grad:
                     acc = self.grads.claim(x, self)
                     dx = self.grads.grad_of(x)
                     if transposed:
-                        L.check(self.lib.isa_conv_gemm(dy.d(), None, pk.ptr(reg["dgrad"]), reg["kp_d"], None,
-                                                       dx.d(), L.IN_GATHER2, L.OUT_PLAIN, None, acc, self.st()),
-                                "isa_conv_gemm(dgradT)")
+                        self.lib.isa_conv_gemm(dy.d(), None, pk.ptr(reg["dgrad"]), reg["kp_d"], None, dx.d(), L.IN_GATHER2,
+                                               L.OUT_PLAIN, None, acc, self.st())
                     else:
                         if self.profile:
                             self.next_bytes = (dy.n * dy.h * dy.w * dy.c + dx.n * dx.h * dx.w * dx.c) * dy.buf.element_size()
-                        L.check(self.lib.isa_conv_gemm(dy.d(), None, pk.ptr(reg["dgrad"]), reg["kp_d"], None,
-                                                       dx.d(), in_mode, L.OUT_PLAIN, None, acc, self.st()),
-                                "isa_conv_gemm(dgrad)")
+                        self.lib.isa_conv_gemm(dy.d(), None, pk.ptr(reg["dgrad"]), reg["kp_d"], None, dx.d(), in_mode,
+                                               L.OUT_PLAIN, None, acc, self.st())
             self.tape.append(bwd)
         return out, st
 
@@ -955,8 +947,7 @@ class Engine:
         """Deferred residual gradient, conv ended up unfused after all: add it to dx."""
         if rec.addend is not None:
             acc = self.grads.claim(x, self)
-            L.check(self.lib.isa_axpy(rec.addend.d(), self.grads.grad_of(x).d(), 1.0, acc, self.st()),
-                    "isa_axpy(res, deferred)")
+            self.lib.isa_axpy(rec.addend.d(), self.grads.grad_of(x).d(), 1.0, acc, self.st())
 
     def _fused_pw_backward(self, x: Act, wname, rec):
         """BN-apply of the conv's output BN + weight gradient + data gradient (+ reduce of the BN that
@@ -966,11 +957,11 @@ class Engine:
         g = rec.g
         if self.profile:
             self.next_bytes = x.n * x.h * x.w * (2 * g.c + 2 * x.c) * x.buf.element_size()
-        L.check(self.lib.isa_conv1x1_bn_backward(
-            g.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(), C.byref(xdesc) if xdesc is not None else None,
-            self.params.ptr(wname), self.params.gptr(wname), self.grads.grad_of(x).d(), acc,
-            rec.addend.d() if rec.addend is not None else None,
-            L.ptr(self.ws), self.ws.numel(), self.defer_handle(), self.st()), "isa_conv1x1_bn_backward")
+        self.lib.isa_conv1x1_bn_backward(g.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
+                                         C.byref(xdesc) if xdesc is not None else None, self.params.ptr(wname),
+                                         self.params.gptr(wname), self.grads.grad_of(x).d(), acc,
+                                         rec.addend.d() if rec.addend is not None else None, self.ws, self.ws.numel(),
+                                         self.defer_handle(), self.st())
 
     def _launch_conv(self, x, reg, bias, out, in_mode, out_mode, st):
         if self.packer.table is None:
@@ -978,9 +969,8 @@ class Engine:
         if self.profile:     # algorithmic bytes: input read once + output written once
             esz = x.buf.element_size()
             self.next_bytes = (x.n * x.h * x.w * x.c + out.n * out.h * out.w * out.c) * esz
-        L.check(self.lib.isa_conv_gemm(x.d(), x.p_fin(), self.packer.ptr(reg["fwd"]), reg["kp"],
-                                       self.params.ptr(bias) if bias else None, out.d(), in_mode, out_mode,
-                                       L.ptr(st), 0, self.st()), "isa_conv_gemm")
+        self.lib.isa_conv_gemm(x.d(), x.p_fin(), self.packer.ptr(reg["fwd"]), reg["kp"],
+                               self.params.ptr(bias) if bias else None, out.d(), in_mode, out_mode, st, 0, self.st())
 
     def reg_dw(self, wname, kmap=None):
         c = self.params.shapes[wname][0]
@@ -996,9 +986,8 @@ class Engine:
         st = self.scratch(2 * out.c * STAT_R * out.groups) if stats else None
         if self.profile:
             self.next_bytes = 2 * x.n * x.h * x.w * x.c * x.buf.element_size()
-        L.check(self.lib.isa_dwconv3x3(x.d(), x.p_fin(), self.packer.ptr(reg["fwd"]),
-                                       self.params.ptr(bias) if bias else None, out.d(), L.ptr(st), self.st()),
-                "isa_dwconv3x3")
+        self.lib.isa_dwconv3x3(x.d(), x.p_fin(), self.packer.ptr(reg["fwd"]), self.params.ptr(bias) if bias else None,
+                               out.d(), st, self.st())
         if self.record:
             rec = None
             if self.fuse_dw_bn and self.bn_train and x.c % 8 == 0 and bias is None and x.needs_grad \
@@ -1019,27 +1008,25 @@ class Engine:
                         acc = self.grads.claim(x, self)
                         if self.profile:
                             self.next_bytes = 4 * nb
-                        L.check(self.lib.isa_dwconv3x3_bn_backward(
-                            dy.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
-                            C.byref(xdesc) if xdesc is not None else None, self.packer.ptr(reg["dgrad"]),
-                            self.params.gptr(wname), self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
-                            rec.addend.d() if rec.addend is not None else None,
-                            L.ptr(self.ws), self.ws.numel(), self.defer_handle(), self.st()), "isa_dwconv3x3_bn_backward")
+                        self.lib.isa_dwconv3x3_bn_backward(dy.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
+                                                           C.byref(xdesc) if xdesc is not None else None,
+                                                           self.packer.ptr(reg["dgrad"]), self.params.gptr(wname),
+                                                           self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
+                                                           rec.addend.d() if rec.addend is not None else None, self.ws,
+                                                           self.ws.numel(), self.defer_handle(), self.st())
                         return
                     self._flush_addend(x, rec)
                 if self.profile:
                     self.next_bytes = 2 * nb
-                L.check(self.lib.isa_dwconv3x3_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
-                                                     self.params.gptr(bias) if bias else None,
-                                                     self.params.shapes[wname][0], L.ptr(self.ws), self.ws.numel(),
-                                                     self.defer_handle(), self.st()), "isa_dwconv3x3_wgrad")
+                self.lib.isa_dwconv3x3_wgrad(x.d(), x.p(), dy.d(), self.params.gptr(wname),
+                                             self.params.gptr(bias) if bias else None, self.params.shapes[wname][0],
+                                             self.ws, self.ws.numel(), self.defer_handle(), self.st())
                 if x.needs_grad:
                     acc = self.grads.claim(x, self)
                     if self.profile:
                         self.next_bytes = 2 * nb
-                    L.check(self.lib.isa_dwconv3x3_dgrad(dy.d(), self.packer.ptr(reg["dgrad"]),
-                                                         self.grads.grad_of(x).d(), acc, self.st()),
-                            "isa_dwconv3x3_dgrad")
+                    self.lib.isa_dwconv3x3_dgrad(dy.d(), self.packer.ptr(reg["dgrad"]), self.grads.grad_of(x).d(), acc,
+                                                 self.st())
             self.tape.append(bwd)
         return out, st
 
@@ -1096,17 +1083,14 @@ class Engine:
             red = self.scratch(2 * lazy.c * STAT_R * lazy.groups)
             if self.profile:
                 self.next_bytes = 2 * nb
-            L.check(self.lib.isa_bn_bwd_reduce(dt.d(), b.raw.d(), L.ptr(b.scale), L.ptr(b.shift), L.ptr(b.mean),
-                                               L.ptr(b.invstd), b.act, L.ptr(bscale), L.ptr(red), self.st()),
-                    "isa_bn_bwd_reduce")
+            self.lib.isa_bn_bwd_reduce(dt.d(), b.raw.d(), b.scale, b.shift, b.mean, b.invstd, b.act, bscale, red, self.st())
         if not do_apply:
             return red
         if self.profile:
             self.next_bytes = 3 * nb
-        L.check(self.lib.isa_bn_bwd_apply(dt.d(), b.raw.d(), L.ptr(b.scale), L.ptr(b.shift), L.ptr(b.mean), L.ptr(b.invstd),
-                                          b.act, L.ptr(bscale), P.ptr(b.pre + ".weight"), L.ptr(red), b.count,
-                                          1 if b.train else 0, dy.d(), P.gptr(b.pre + ".weight"), P.gptr(b.pre + ".bias"),
-                                          self.st()), "isa_bn_bwd_apply")
+        self.lib.isa_bn_bwd_apply(dt.d(), b.raw.d(), b.scale, b.shift, b.mean, b.invstd, b.act, bscale,
+                                  P.ptr(b.pre + ".weight"), red, b.count, 1 if b.train else 0, dy.d(),
+                                  P.gptr(b.pre + ".weight"), P.gptr(b.pre + ".bias"), self.st())
         return red
 
     def bn_out(self, raw: Act, stats, pre, act, out: Act, res: Optional[Act] = None, bscale=None,
@@ -1119,9 +1103,8 @@ class Engine:
         lazy.bn = b
         if self.profile:
             self.next_bytes = (2 + (res is not None) + (res2 is not None)) * raw.n * raw.h * raw.w * raw.c * raw.buf.element_size()
-        L.check(self.lib.isa_affine_act_res(lazy.d(), lazy.p_fin(), res.d() if res is not None else None,
-                                            res2.d() if res2 is not None else None, L.ptr(oscale), out.d(),
-                                            self.st()), "isa_affine_act_res")
+        self.lib.isa_affine_act_res(lazy.d(), lazy.p_fin(), res.d() if res is not None else None,
+                                    res2.d() if res2 is not None else None, oscale, out.d(), self.st())
         if self.record:
             pw = self._pw_out.get(self._key(raw)) if (b.train and bscale is None) else None
 
@@ -1133,7 +1116,7 @@ class Engine:
                 dsum = dout
                 if oscale is not None:           # d(sum) = dout * dropout mask (summed over the groups of a broadcast)
                     dsum = self.like(raw, out.c)
-                    L.check(self.lib.isa_scale_bc(dout.d(), L.ptr(oscale), dsum.d(), 0, self.st()), "isa_scale_bc")
+                    self.lib.isa_scale_bc(dout.d(), oscale, dsum.d(), 0, self.st())
                 for r in (res, res2):
                     if r is not None and r.needs_grad:
                         pin = self._pw_in.get(self._key(r))
@@ -1141,8 +1124,7 @@ class Engine:
                             pin.addend = dsum             # the consuming conv's backward adds it to dx itself
                             continue
                         acc = self.grads.claim(r, self)
-                        L.check(self.lib.isa_axpy(dsum.d(), self.grads.grad_of(r).d(), 1.0, acc, self.st()),
-                                "isa_axpy(res)")
+                        self.lib.isa_axpy(dsum.d(), self.grads.grad_of(r).d(), 1.0, acc, self.st())
                 if pw is not None:                # the producing 1x1 conv's backward applies this BN on the fly
                     pw.ybn, pw.yred, pw.g = b, self._bn_backward(lazy, dsum, None, None, do_apply=False), dsum
                     return
@@ -1158,8 +1140,8 @@ class Engine:
         if self.record:
             def bwd():
                 g = self.grads.grad_of(raw)
-                L.check(self.lib.isa_bn_bwd_apply(g.d(), raw.d(), None, None, None, None, act, None, None, None, 1.0,
-                                                  0, g.d(), None, None, self.st()), "isa_bn_bwd_apply(act)")
+                self.lib.isa_bn_bwd_apply(g.d(), raw.d(), None, None, None, None, act, None, None, None, 1.0, 0, g.d(),
+                                          None, None, self.st())
             self.tape.append(bwd)
         return lazy
 
@@ -1167,33 +1149,29 @@ class Engine:
         """Materialised activation out = act(raw) for consumers that would re-evaluate a lazy prologue many
         times (a 3x3 conv applies it once per tap: tanh ahead of attend_fc cost 9 tanhf per element)."""
         lazy = raw.with_pro(Pro(act=act))
-        L.check(self.lib.isa_affine_act_res(lazy.d(), lazy.p(), None, None, None, out.d(), self.st()),
-                "isa_affine_act_res(act)")
+        self.lib.isa_affine_act_res(lazy.d(), lazy.p(), None, None, None, out.d(), self.st())
         if self.record:
             def bwd():
                 acc = self.grads.claim(raw, self)
                 assert acc == 0, "act_out expects to be the only consumer of its input"
-                L.check(self.lib.isa_bn_bwd_apply(self.grads.grad_of(out).d(), raw.d(), None, None, None, None, act,
-                                                  None, None, None, 1.0, 0, self.grads.grad_of(raw).d(), None, None,
-                                                  self.st()), "isa_bn_bwd_apply(act_out)")
+                self.lib.isa_bn_bwd_apply(self.grads.grad_of(out).d(), raw.d(), None, None, None, None, act, None, None,
+                                          None, 1.0, 0, self.grads.grad_of(raw).d(), None, None, self.st())
             self.tape.append(bwd)
         return out
 
     def materialize(self, x: Act, out: Act, res: Optional[Act] = None):
         """out = pro(x) (+res) for a lazy x that is NOT a BN output (bias+act convs)."""
-        L.check(self.lib.isa_affine_act_res(x.d(), x.p(), res.d() if res is not None else None, None, None,
-                                            out.d(), self.st()), "isa_affine_act_res")
+        self.lib.isa_affine_act_res(x.d(), x.p(), res.d() if res is not None else None, None, None, out.d(), self.st())
         assert not self.record, "use bn_out / lazy consumers on the training path"
         return out
 
     # ------------------------------------------------------------------ pooling
     def avgpool2(self, x: Act, out: Act):
-        L.check(self.lib.isa_avgpool2(x.d(), out.d(), self.st()), "isa_avgpool2")
+        self.lib.isa_avgpool2(x.d(), out.d(), self.st())
         if self.record and x.needs_grad:
             def bwd():
                 acc = self.grads.claim(x, self)
-                L.check(self.lib.isa_avgpool2_bwd(self.grads.grad_of(out).d(), self.grads.grad_of(x).d(), acc,
-                                                  self.st()), "isa_avgpool2_bwd")
+                self.lib.isa_avgpool2_bwd(self.grads.grad_of(out).d(), self.grads.grad_of(x).d(), acc, self.st())
             self.tape.append(bwd)
         return out
 
@@ -1217,10 +1195,9 @@ class Engine:
                 self.fold_arena = torch.empty(int(os.environ.get("ISA_FOLD_ARENA_MB", "2048")) << 18,
                                               dtype=torch.float32, device=self.device)
             h = C.c_void_p()
-            L.check(self.lib.isa_slab_arena_create(L.ptr(self.fold_arena), self.fold_arena.numel(), C.byref(h)),
-                    "isa_slab_arena_create")
+            self.lib.isa_slab_arena_create(self.fold_arena, self.fold_arena.numel(), C.byref(h))
             self.slab = h
-        L.check(self.lib.isa_slab_arena_begin(self.slab), "isa_slab_arena_begin")
+        self.lib.isa_slab_arena_begin(self.slab)
         if POISON:
             self.fold_arena.view(torch.uint8).fill_(0xFF)
         self._deferring = True
@@ -1235,7 +1212,6 @@ class Engine:
         finally:
             self._deferring = False
             nf, used = C.c_int32(0), C.c_int64(0)
-            L.check(self.lib.isa_slab_arena_flush(self.slab, self.st(), C.byref(nf), C.byref(used)),
-                    "isa_slab_arena_flush")
+            self.lib.isa_slab_arena_flush(self.slab, self.st(), C.byref(nf), C.byref(used))
             self.fold_stats = (nf.value, used.value)
         self.tape = Tape(self)

@@ -80,37 +80,31 @@ class InstanceHead:
         n, c, Lp = x.n, x.c, x.h * x.w
         pre = "decoder.s_sp"
         dot, chansum = E.scratch(n * Lp), E.scratch(n * c)
-        L.check(E.lib.isa_mask_dot(x.d(), L.ptr(sem), P.ptr(pre + ".l_v.weight"), P.ptr(pre + ".l_v.bias"),
-                                   L.ptr(dot), L.ptr(chansum), E.st()), "isa_mask_dot")
+        E.lib.isa_mask_dot(x.d(), sem, P.ptr(pre + ".l_v.weight"), P.ptr(pre + ".l_v.bias"), dot, chansum, E.st())
         beta, rowstat = E.f32(n * Lp), E.f32(n * 4)
-        L.check(E.lib.isa_sp_softmax(L.ptr(dot), L.ptr(sem), L.ptr(chansum), P.ptr(pre + ".l_h.weight"),
-                                     P.ptr(pre + ".spatial_fc.1.weight"), P.ptr(pre + ".spatial_fc.1.bias"),
-                                     n, c, Lp, L.ptr(beta), L.ptr(rowstat), L.ptr(E.f32(n * ROW_PART)), E.st()),
-                "isa_sp_softmax")
+        E.lib.isa_sp_softmax(dot, sem, chansum, P.ptr(pre + ".l_h.weight"), P.ptr(pre + ".spatial_fc.1.weight"),
+                             P.ptr(pre + ".spatial_fc.1.bias"), n, c, Lp, beta, rowstat, E.f32(n * ROW_PART), E.st())
         scale, shift, mean, invstd = (E.f32(c) for _ in range(4))
         stats = E.scratch(2 * c * 8)
         if E.bn_train:
-            L.check(E.lib.isa_scaled_stats(x.d(), L.ptr(beta), L.ptr(stats), E.st()), "isa_scaled_stats")
+            E.lib.isa_scaled_stats(x.d(), beta, stats, E.st())
             P.int_buffers[pre + ".bn.num_batches_tracked"] += 1
         E.bn_finalize(stats if E.bn_train else None, float(n * Lp), pre + ".bn", E.running_ptrs(pre + ".bn"), scale, shift,
-                      mean, invstd, c, 1, 1, "isa_bn_finalize")
+                      mean, invstd, c, 1, 1)
         out = E.new_act(n, x.h, x.w, c)
-        L.check(E.lib.isa_sp_apply(x.d(), L.ptr(beta), L.ptr(sem), L.ptr(scale), L.ptr(shift), out.d(), E.st()),
-                "isa_sp_apply")
+        E.lib.isa_sp_apply(x.d(), beta, sem, scale, shift, out.d(), E.st())
         if E.record:
             train = 1 if E.bn_train else 0
 
             def bwd():
                 scr = E.scratch(3 * c + 2 * ((n + 3) // 4 * 4) + 2 * n * Lp)
                 acc = E.grads.claim(x, E)
-                L.check(E.lib.isa_sp_bwd(E.grads.grad_of(out).d(), x.d(), L.ptr(beta), L.ptr(sem), L.ptr(dot),
-                                         L.ptr(rowstat), L.ptr(chansum), L.ptr(scale), L.ptr(mean), L.ptr(invstd),
-                                         P.ptr(pre + ".l_v.weight"), P.ptr(pre + ".l_h.weight"),
-                                         P.ptr(pre + ".spatial_fc.1.weight"), float(n * Lp), train, L.ptr(scr),
-                                         E.grads.grad_of(x).d(), acc, P.gptr(pre + ".bn.weight"), P.gptr(pre + ".bn.bias"),
-                                         P.gptr(pre + ".l_v.weight"), P.gptr(pre + ".l_v.bias"), P.gptr(pre + ".l_h.weight"),
-                                         P.gptr(pre + ".spatial_fc.1.weight"), P.gptr(pre + ".spatial_fc.1.bias"),
-                                         E.st()), "isa_sp_bwd")
+                E.lib.isa_sp_bwd(E.grads.grad_of(out).d(), x.d(), beta, sem, dot, rowstat, chansum, scale, mean, invstd,
+                                 P.ptr(pre + ".l_v.weight"), P.ptr(pre + ".l_h.weight"),
+                                 P.ptr(pre + ".spatial_fc.1.weight"), float(n * Lp), train, scr, E.grads.grad_of(x).d(),
+                                 acc, P.gptr(pre + ".bn.weight"), P.gptr(pre + ".bn.bias"), P.gptr(pre + ".l_v.weight"),
+                                 P.gptr(pre + ".l_v.bias"), P.gptr(pre + ".l_h.weight"),
+                                 P.gptr(pre + ".spatial_fc.1.weight"), P.gptr(pre + ".spatial_fc.1.bias"), E.st())
             E.tape.append(bwd)
         return out
 
@@ -121,12 +115,11 @@ class InstanceHead:
         n, h, w = s.n, s.h, s.w
         pre = "decoder.attend"
         sp = E.new_act(n, h, w, s.c)
-        L.check(E.lib.isa_avgpool3(s.d(), None, sp.d(), 0, E.st()), "isa_avgpool3")
+        E.lib.isa_avgpool3(s.d(), None, sp.d(), 0, E.st())
         if E.record:
             def bwd_pool():      # 3x3 mean with zero padding is self-adjoint
                 acc = E.grads.claim(s, E)
-                L.check(E.lib.isa_avgpool3(E.grads.grad_of(sp).d(), None, E.grads.grad_of(s).d(), acc, E.st()),
-                        "isa_avgpool3(bwd)")
+                E.lib.isa_avgpool3(E.grads.grad_of(sp).d(), None, E.grads.grad_of(s).d(), acc, E.st())
             E.tape.append(bwd_pool)
         e1 = E.new_act(n, h, w, 12)
         E.conv(sp, pre + ".l1.weight", e1, bias=pre + ".l1.bias")
@@ -137,18 +130,15 @@ class InstanceHead:
         train = 1 if E.bn_train else 0
         rm, rv = P.ptr(pre + ".bn.running_mean"), P.ptr(pre + ".bn.running_var")
         if train:
-            L.check(E.lib.isa_maskbn_stats(e2.d(), L.ptr(sem), None, L.ptr(am), E.st()), "isa_maskbn_stats")
-        L.check(E.lib.isa_maskbn_finalize(L.ptr(am), L.ptr(v), n, 0, L.ptr(mean_var), rm, rv, E.BN_MOMENTUM, train,
-                                          E.st()), "isa_maskbn_finalize")
+            E.lib.isa_maskbn_stats(e2.d(), sem, None, am, E.st())
+        E.lib.isa_maskbn_finalize(am, v, n, 0, mean_var, rm, rv, E.BN_MOMENTUM, train, E.st())
         if train:
-            L.check(E.lib.isa_maskbn_stats(e2.d(), L.ptr(sem), L.ptr(mean_var), L.ptr(v), E.st()), "isa_maskbn_stats")
-            L.check(E.lib.isa_maskbn_finalize(L.ptr(am), L.ptr(v), n, 1, L.ptr(mean_var), rm, rv, E.BN_MOMENTUM, 1,
-                                              E.st()), "isa_maskbn_finalize")
+            E.lib.isa_maskbn_stats(e2.d(), sem, mean_var, v, E.st())
+            E.lib.isa_maskbn_finalize(am, v, n, 1, mean_var, rm, rv, E.BN_MOMENTUM, 1, E.st())
             P.int_buffers[pre + ".bn.num_batches_tracked"] += 1
         merge = E.f32(n * h * w)
-        L.check(E.lib.isa_maskbn_apply_pool(e2.d(), L.ptr(sem), L.ptr(mean_var), P.ptr(pre + ".bn.weight"),
-                                            P.ptr(pre + ".bn.bias"), E.BN_EPS, L.ptr(merge), E.st()),
-                "isa_maskbn_apply_pool")
+        E.lib.isa_maskbn_apply_pool(e2.d(), sem, mean_var, P.ptr(pre + ".bn.weight"), P.ptr(pre + ".bn.bias"), E.BN_EPS,
+                                    merge, E.st())
         self.dmerge = None
         if E.record:
             dmerge = E.scratch(n * h * w)       # zero at step start; filled by the per-iteration closures
@@ -157,10 +147,9 @@ class InstanceHead:
             def bwd_bn():
                 red4, k2 = E.scratch(4), E.f32(2)
                 acc = E.grads.claim(e2, E)
-                L.check(E.lib.isa_maskbn_bwd(e2.d(), L.ptr(sem), L.ptr(dmerge), L.ptr(mean_var), P.ptr(pre + ".bn.weight"),
-                                             E.BN_EPS, L.ptr(am), train, L.ptr(red4), L.ptr(k2), P.gptr(pre + ".bn.weight"),
-                                             P.gptr(pre + ".bn.bias"), E.grads.grad_of(e2).d(), acc, E.st()),
-                        "isa_maskbn_bwd")
+                E.lib.isa_maskbn_bwd(e2.d(), sem, dmerge, mean_var, P.ptr(pre + ".bn.weight"), E.BN_EPS, am, train, red4,
+                                     k2, P.gptr(pre + ".bn.weight"), P.gptr(pre + ".bn.bias"), E.grads.grad_of(e2).d(), acc,
+                                     E.st())
             E.tape.append(bwd_bn)
         return merge
 
@@ -175,7 +164,7 @@ class InstanceHead:
         keep = 1.0 - self.drop_rate
         u = torch.rand(total, device=self.E.device)          # torch supplies the random numbers (graph-safe generator)
         self._mask_pool = torch.empty_like(u)
-        L.check(self.E.lib.isa_dropout_mask(L.ptr(u), total, keep, L.ptr(self._mask_pool), self.E.st()), "isa_dropout_mask")
+        self.E.lib.isa_dropout_mask(u, total, keep, self._mask_pool, self.E.st())
 
     def _masks_batched(self, n, G, training):
         """Dropout2d masks of a pass that batches the G iterations: per level {cross, d1, d2} as [G*n, C] arrays
@@ -192,7 +181,7 @@ class InstanceHead:
             total = sum((int(act_cross) + 2 * int(act_d)) * G * n * oc for oc in OUT_CH)
             u = torch.rand(total, device=E.device)
             pool = torch.empty_like(u)
-            L.check(E.lib.isa_dropout_mask(L.ptr(u), total, keep, L.ptr(pool), E.st()), "isa_dropout_mask")
+            E.lib.isa_dropout_mask(u, total, keep, pool, E.st())
 
         def take(lvl, kind, oc):
             nonlocal cur
@@ -271,19 +260,17 @@ class InstanceHead:
             E.conv(x_prev, ua + ".up.weight", up, bias=ua + ".up.bias", transposed=True)
             gated = cat.slice(0, out_ch)
             gmap = E.f32(n * h * w) if E.record else None
-            L.check(E.lib.isa_gate(up.d(), pred_prev.d(), gated.d(), L.ptr(gmap), E.st()), "isa_gate")
+            E.lib.isa_gate(up.d(), pred_prev.d(), gated.d(), gmap, E.st())
             if E.record:
                 def bwd_gate(up=up, pred_prev=pred_prev, gated=gated, gmap=gmap):
                     du = E.scratch(n * h * w)
                     acc_up = E.grads.claim(up, E)
                     acc_pred = E.grads.claim(pred_prev, E)
-                    L.check(E.lib.isa_gate_bwd(E.grads.grad_of(gated).d(), up.d(), L.ptr(gmap), E.grads.grad_of(up).d(),
-                                               acc_up, L.ptr(du), E.grads.grad_of(pred_prev).d(), acc_pred, E.st()),
-                            "isa_gate_bwd")
+                    E.lib.isa_gate_bwd(E.grads.grad_of(gated).d(), up.d(), gmap, E.grads.grad_of(up).d(), acc_up, du,
+                                       E.grads.grad_of(pred_prev).d(), acc_pred, E.st())
                 E.tape.append(bwd_gate)
         aux = cat.slice(cross_off + ccross, naux)
-        L.check(E.lib.isa_concat_aux(aux.d(), L.ptr(mask_all), L.ptr(s_t), W_full, f, nb, n // cat.groups, E.st()),
-                "isa_concat_aux")
+        E.lib.isa_concat_aux(aux.d(), mask_all, s_t, W_full, f, nb, n // cat.groups, E.st())
         if lvl == 0:
             kmap = None
         else:   # physical [gated(out) | cross(ccross) | aux] -> source [cross | gated | aux]
@@ -335,8 +322,7 @@ class InstanceHead:
         n, k, Lp = ins.shape[0], ins.shape[1], x_enc.h * x_enc.w
         assert ins.dtype == torch.int64 and 1 <= k <= L.DISC_MAX_K, "instance planes: int64 [n,K,h,w], K <= 32"
         labels = E.arena.alloc((n, Lp), torch.uint8)
-        L.check(E.lib.isa_labels_from_planes(L.ptr(ins), L.PLANES_I64_NKHW, n, k, Lp, L.ptr(labels), E.st()),
-                "isa_labels_from_planes")
+        E.lib.isa_labels_from_planes(ins, L.PLANES_I64_NKHW, n, k, Lp, labels, E.st())
         scal, _, grad = net.disc_loss(x_enc, labels, k, n_obj, net.disc.cfg, net.disc.norm)
         if E.record:
             def bwd_disc():
@@ -370,8 +356,7 @@ class InstanceHead:
                 mask_all.append(sem_map)
             else:
                 m = E.f32(n * (H // f) * (W // f))
-                L.check(E.lib.isa_pool_target(None, None, L.ptr(sem_map), nobj, n, H, W, f, L.ptr(m), n, E.st()),
-                        "isa_pool_target(sem)")
+                E.lib.isa_pool_target(None, None, sem_map, nobj, n, H, W, f, m, n, E.st())
                 mask_all.append(m)
         if idx_dev is None:          # [max_iter, n] int32 instance order; pre-staged by the graph-captured step
             idx_dev = self.order_tensor(selected_idx, max_iter, n).to(E.device)
@@ -391,8 +376,7 @@ class InstanceHead:
         for it in range(max_iter):
             idx = idx_dev[it]
             alpha, rowstat = E.f32(n * Lp), E.f32(2 * n)
-            L.check(E.lib.isa_ins_softmax(L.ptr(merge), L.ptr(ins), L.ptr(idx), n, nobj, Lp, L.ptr(alpha),
-                                          L.ptr(rowstat), n, L.ptr(E.f32(n * ROW_PART)), E.st()), "isa_ins_softmax")
+            E.lib.isa_ins_softmax(merge, ins, idx, n, nobj, Lp, alpha, rowstat, n, E.f32(n * ROW_PART), E.st())
             if injected_s_t is not None:
                 s_t = injected_s_t[it]
             else:
@@ -403,12 +387,11 @@ class InstanceHead:
                 if training and self.sample_in_training:
                     race = torch.empty(n, Lp, dtype=torch.float32, device=alpha.device).exponential_(1.0)
                 s_t = E.arena.alloc((n,), torch.int32)
-                L.check(E.lib.isa_row_argmax(L.ptr(alpha), L.ptr(race), n, Lp, L.ptr(s_t), E.st()), "isa_row_argmax")
+                E.lib.isa_row_argmax(alpha, race, n, Lp, s_t, E.st())
             targets = []
             for f in FACTORS:
                 t = E.f32(n * (H // f) * (W // f))
-                L.check(E.lib.isa_pool_target(L.ptr(ins), L.ptr(idx), None, nobj, n, H, W, f, L.ptr(t), n, E.st()),
-                        "isa_pool_target")
+                E.lib.isa_pool_target(ins, idx, None, nobj, n, H, W, f, t, n, E.st())
                 targets.append(t)
             sums_all = E.scratch(5 * 8 * n)                 # [level][image][8], contiguous for isa_head_loss
             pre.append((idx, alpha, s_t, targets, sums_all))
@@ -466,9 +449,7 @@ class InstanceHead:
                 E.sync(sc, sm)
                 with E.on(sm):
                     x, pred = self.level_main(lvl, cat, st_["x"], st_["pred"], mask_all[lvl], s_t, W, training, masks)
-                    L.check(E.lib.isa_mask_loss_sums(pred.d(), L.ptr(targets[lvl]), None,
-                                                     L.ptr(sums_all[lvl * 8 * n:(lvl + 1) * 8 * n]), E.st()),
-                            "isa_mask_loss_sums")
+                    E.lib.isa_mask_loss_sums(pred.d(), targets[lvl], None, sums_all[lvl * 8 * n:(lvl + 1) * 8 * n], E.st())
                 st_["x"], st_["pred"] = x, pred
                 st_["preds"].append(pred)
                 if capture is not None:
@@ -483,18 +464,15 @@ class InstanceHead:
             idx, alpha, s_t, targets, sums_all = pre[it]
             preds, sums = recs[it]
             coef, adv = E.f32(5 * 4 * n), E.f32(n)
-            L.check(E.lib.isa_head_loss(L.ptr(sums_all), L.ptr(alpha), L.ptr(s_t), Lp, n, self._level_w, CE_WEIGHT,
-                                        LAMBDA_L, LAMBDA_R, 1.0 / max_iter, L.ptr(self.baseline), 1 if training else 0,
-                                        L.ptr(coef), L.ptr(adv), L.ptr(scal), 1, E.st()), "isa_head_loss")
+            E.lib.isa_head_loss(sums_all, alpha, s_t, Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L, LAMBDA_R, 1.0 / max_iter,
+                                self.baseline, 1 if training else 0, coef, adv, scal, 1, E.st())
             if E.record:
                 def bwd_losses(preds=preds, targets=targets, coef=coef, alpha=alpha, idx=idx, s_t=s_t, adv=adv):
                     for lvl in range(5):
                         acc = E.grads.claim(preds[lvl], E)
-                        L.check(E.lib.isa_mask_loss_grad(preds[lvl].d(), L.ptr(targets[lvl]), None,
-                                                         L.ptr(coef[lvl * 4 * n:(lvl + 1) * 4 * n]),
-                                                         E.grads.grad_of(preds[lvl]).d(), acc, E.st()), "isa_mask_loss_grad")
-                    L.check(E.lib.isa_ins_softmax_bwd(L.ptr(alpha), L.ptr(ins), L.ptr(idx), L.ptr(s_t), L.ptr(adv), n, nobj,
-                                                      Lp, L.ptr(self.dmerge), n, E.st()), "isa_ins_softmax_bwd")
+                        E.lib.isa_mask_loss_grad(preds[lvl].d(), targets[lvl], None, coef[lvl * 4 * n:(lvl + 1) * 4 * n],
+                                                 E.grads.grad_of(preds[lvl]).d(), acc, E.st())
+                    E.lib.isa_ins_softmax_bwd(alpha, ins, idx, s_t, adv, n, nobj, Lp, self.dmerge, n, E.st())
                 E.tape.append(bwd_losses)
             iters.append(dict(idx=idx, alpha=alpha, s_t=s_t, targets=targets, preds=preds, sums=sums))
         return dict(iters=iters, max_iter=max_iter, merge=merge, x_enc=x_enc, scal=scal)
@@ -510,8 +488,7 @@ class InstanceHead:
         Lp, R = H * W, G * n
         idx_flat = idx_dev.reshape(-1).contiguous()          # [G*n]
         alpha, rowstat = E.f32(R * Lp), E.f32(2 * R)
-        L.check(E.lib.isa_ins_softmax(L.ptr(merge), L.ptr(ins), L.ptr(idx_flat), R, nobj, Lp, L.ptr(alpha), L.ptr(rowstat), n,
-                                      L.ptr(E.f32(R * ROW_PART)), E.st()), "isa_ins_softmax")
+        E.lib.isa_ins_softmax(merge, ins, idx_flat, R, nobj, Lp, alpha, rowstat, n, E.f32(R * ROW_PART), E.st())
         s_t = E.arena.alloc((R,), torch.int32)
         if injected_s_t is not None:
             for it in range(G):
@@ -520,12 +497,11 @@ class InstanceHead:
             race = None                                      # attenet2.py:304-321 `sample`, see the per-iteration path
             if training and self.sample_in_training:
                 race = torch.empty(R, Lp, dtype=torch.float32, device=alpha.device).exponential_(1.0)
-            L.check(E.lib.isa_row_argmax(L.ptr(alpha), L.ptr(race), R, Lp, L.ptr(s_t), E.st()), "isa_row_argmax")
+            E.lib.isa_row_argmax(alpha, race, R, Lp, s_t, E.st())
         targets = []
         for f in FACTORS:
             t = E.f32(R * (H // f) * (W // f))
-            L.check(E.lib.isa_pool_target(L.ptr(ins), L.ptr(idx_flat), None, nobj, R, H, W, f, L.ptr(t), n, E.st()),
-                    "isa_pool_target")
+            E.lib.isa_pool_target(ins, idx_flat, None, nobj, R, H, W, f, t, n, E.st())
             targets.append(t)
         sums_all = E.scratch(5 * 8 * R)                      # [level][iteration][image][8]
         masks = self._masks_batched(n, G, training)
@@ -543,26 +519,22 @@ class InstanceHead:
                 cat = self.level_cross(lvl, skips[lvl], masks[lvl], G)
             E.sync(sc, 0)
             x, pred = self.level_main(lvl, cat, x, pred, mask_all[lvl], s_t, W, training, masks[lvl])
-            L.check(E.lib.isa_mask_loss_sums(pred.d(), L.ptr(targets[lvl]), None, L.ptr(sums_all[lvl * 8 * R:(lvl + 1) * 8 * R]),
-                                             E.st()), "isa_mask_loss_sums")
+            E.lib.isa_mask_loss_sums(pred.d(), targets[lvl], None, sums_all[lvl * 8 * R:(lvl + 1) * 8 * R], E.st())
             preds.append(pred)
             if capture is not None:
                 for it in range(G):
                     capture["it%d.L%d.x" % (it, lvl)] = x.images(it * n, n)
                     capture["it%d.L%d.pred" % (it, lvl)] = pred.images(it * n, n)
         coef, adv = E.f32(5 * 4 * R), E.f32(R)
-        L.check(E.lib.isa_head_loss(L.ptr(sums_all), L.ptr(alpha), L.ptr(s_t), Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L,
-                                    LAMBDA_R, 1.0 / G, L.ptr(self.baseline), 1 if training else 0, L.ptr(coef), L.ptr(adv),
-                                    L.ptr(scal), G, E.st()), "isa_head_loss")
+        E.lib.isa_head_loss(sums_all, alpha, s_t, Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L, LAMBDA_R, 1.0 / G,
+                            self.baseline, 1 if training else 0, coef, adv, scal, G, E.st())
         if E.record:
             def bwd_losses():
                 for lvl in range(5):
                     acc = E.grads.claim(preds[lvl], E)
-                    L.check(E.lib.isa_mask_loss_grad(preds[lvl].d(), L.ptr(targets[lvl]), None,
-                                                     L.ptr(coef[lvl * 4 * R:(lvl + 1) * 4 * R]), E.grads.grad_of(preds[lvl]).d(),
-                                                     acc, E.st()), "isa_mask_loss_grad")
-                L.check(E.lib.isa_ins_softmax_bwd(L.ptr(alpha), L.ptr(ins), L.ptr(idx_flat), L.ptr(s_t), L.ptr(adv), R, nobj, Lp,
-                                                  L.ptr(self.dmerge), n, E.st()), "isa_ins_softmax_bwd")
+                    E.lib.isa_mask_loss_grad(preds[lvl].d(), targets[lvl], None, coef[lvl * 4 * R:(lvl + 1) * 4 * R],
+                                             E.grads.grad_of(preds[lvl]).d(), acc, E.st())
+                E.lib.isa_ins_softmax_bwd(alpha, ins, idx_flat, s_t, adv, R, nobj, Lp, self.dmerge, n, E.st())
             E.tape.append(bwd_losses)
         iters = []
         for it in range(G):                                  # per-iteration views, as the one-pass-per-iteration path returns them
@@ -601,8 +573,7 @@ class InstanceHead:
                 mask_all.append(sem_map)
             else:
                 m = E.f32(n * (H // f) * (W // f))
-                L.check(E.lib.isa_pool_target(None, None, L.ptr(sem_map), 1, n, H, W, f, L.ptr(m), n, E.st()),
-                        "isa_pool_target(sem)")
+                E.lib.isa_pool_target(None, None, sem_map, 1, n, H, W, f, m, n, E.st())
                 mask_all.append(m)
         if capture is not None:
             capture.update(x_enc=x_enc, s_sp=s, merge=merge)
@@ -612,8 +583,7 @@ class InstanceHead:
         ints = E.arena.alloc((3 * n + 4,), torch.int32)          # count | active | s_t | the "any image active" word
         count, active, s_t, any_dev = ints[:n], ints[n:2 * n], ints[2 * n:3 * n], ints[3 * n:3 * n + 1]
         part = E.f32(n * SEG_PART)
-        L.check(E.lib.isa_seg_begin(L.ptr(sem_map), L.ptr(merge), n, Lp, L.ptr(labels), L.ptr(count), L.ptr(s_t),
-                                    L.ptr(active), L.ptr(any_dev), L.ptr(part), E.st()), "isa_seg_begin")
+        E.lib.isa_seg_begin(sem_map, merge, n, Lp, labels, count, s_t, active, any_dev, part, E.st())
         iters = max_objects if injected_s_t is None else len(injected_s_t)
         assert iters <= 255
         flags = self._seg_flags(iters + 1) if injected_s_t is None else None
@@ -633,8 +603,7 @@ class InstanceHead:
                     capture["it%d.L%d.pred" % (t, lvl)] = Act(pred.buf.clone(), pred.c0, pred.c)
             if capture is not None:
                 capture["it%d.s_t" % t] = pt.clone()
-            L.check(E.lib.isa_seg_claim(pred.d(), L.ptr(sem_map), L.ptr(merge), L.ptr(pt), L.ptr(labels), L.ptr(count),
-                                        L.ptr(active), L.ptr(s_t), L.ptr(any_dev), L.ptr(part), E.st()), "isa_seg_claim")
+            E.lib.isa_seg_claim(pred.d(), sem_map, merge, pt, labels, count, active, s_t, any_dev, part, E.st())
             if flags is not None:
                 self._seg_flag_read(flags, t + 1, any_dev)
             done = t + 1

@@ -2,6 +2,10 @@
 
 There is deliberately NO fallback: if the HIP library is missing or a symbol is absent, importing
 the product path raises.  The CPU oracle under oracle/ is never consulted from here.
+
+Two handles onto the same symbols.  lib() is raw: every entry point returns its status (ABI tests, scripts).  checked() is
+the product's: a non-zero status raises IsaError naming the symbol, so no call site wraps or checks.  On either handle a
+data pointer (VP) takes a torch tensor as it is, so a call reads like its declaration in the header, stream last.
 """
 import ctypes as C
 import os
@@ -130,7 +134,20 @@ class IsaPhotoProg(C.Structure):
                 ("lut", C.c_uint8 * 256)]
 
 
-P_T, P_PRO, VP, I32, F = C.POINTER(IsaTensor), C.POINTER(IsaPro), C.c_void_p, C.c_int32, C.c_float
+_plain = C.c_void_p.from_param          # looked up once: VP.from_param runs for every pointer argument of every launch
+
+
+class VP(C.c_void_p):
+    """A data pointer argument.  Takes what c_void_p takes (None, an int, a c_void_p, a ctypes array, byref(...)) and
+    anything with a data_ptr(): a torch tensor passes as its device address, a view as the address of its first element."""
+
+    @classmethod
+    def from_param(cls, v):
+        dp = getattr(v, "data_ptr", None)
+        return _plain(v if dp is None else dp())
+
+
+P_T, P_PRO, I32, F = C.POINTER(IsaTensor), C.POINTER(IsaPro), C.c_int32, C.c_float
 I64 = C.c_int64
 F64 = C.c_double
 P_BN = C.POINTER(IsaBnBwd)
@@ -296,6 +313,36 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise IsaError("%s failed: %s" % (what, _ERR.get(rc, rc)))
+
+
+def _errcheck(rc, fn, args):
+    if rc != 0:
+        check(rc, fn.__name__)
+    return rc
+
+
+class _Checked:
+    """The entry points of one loaded library as function objects of their own whose status is checked."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        for name, argtypes in SIGNATURES.items():
+            fn = raw[name]                   # a fresh function object: raw.<name> keeps returning the status
+            fn.argtypes, fn.restype, fn.errcheck = argtypes, C.c_int, _errcheck
+            setattr(self, name, fn)
+        self.isa_resize_bilinear_ws_bytes = raw.isa_resize_bilinear_ws_bytes      # a size, not a status
+
+
+_checked = None
+
+
+def checked():
+    """The product's handle: lib()'s entry points, raising IsaError("<symbol> failed: <ISA_E...>") on a non-zero status."""
+    global _checked
+    raw = lib()
+    if _checked is None or _checked.raw is not raw:
+        _checked = _Checked(raw)
+    return _checked
 
 
 def dtype_code(dt):

@@ -247,11 +247,10 @@ class Network:
         P = E.params
         n, c = x_dec.n, x_dec.c
         mean = E.scratch(n * c)
-        L.check(E.lib.isa_chan_mean(x_dec.d(), None, L.ptr(mean), E.st()), "isa_chan_mean")
+        E.lib.isa_chan_mean(x_dec.d(), None, mean, E.st())
         hid, gate = E.f32(n * 16), E.f32(n * c)
-        L.check(E.lib.isa_se_fc(L.ptr(mean), P.ptr("channelAttend.fc.0.weight"), P.ptr("channelAttend.fc.0.bias"),
-                                P.ptr("channelAttend.fc.2.weight"), P.ptr("channelAttend.fc.2.bias"), n, c, 16,
-                                L.ptr(hid), L.ptr(gate), E.st()), "isa_se_fc")
+        E.lib.isa_se_fc(mean, P.ptr("channelAttend.fc.0.weight"), P.ptr("channelAttend.fc.0.bias"),
+                        P.ptr("channelAttend.fc.2.weight"), P.ptr("channelAttend.fc.2.bias"), n, c, 16, hid, gate, E.st())
         gated = x_dec.with_pro(Pro(bscale=gate))
         sem = E.new_act(n, x_dec.h, x_dec.w, self.n_classes)
         E.conv(gated, "sem_seg_output.weight", sem, bias="sem_seg_output.bias", record_bwd=False)
@@ -260,21 +259,18 @@ class Network:
             def bwd():
                 # sem conv: weight/bias grads see x*gate; its data gradient is w.r.t. x*gate (dxa)
                 dy = E.grads.grad_of(sem)
-                L.check(E.lib.isa_conv_wgrad(gated.d(), gated.p(), dy.d(), P.gptr("sem_seg_output.weight"),
-                                             P.gptr("sem_seg_output.bias"), L.IN_1X1, L.OUT_PLAIN, None, c,
-                                             L.ptr(E.ws), E.ws.numel(), E.defer_handle(), E.st()),
-                        "isa_conv_wgrad(sem)")
+                E.lib.isa_conv_wgrad(gated.d(), gated.p(), dy.d(), P.gptr("sem_seg_output.weight"),
+                                     P.gptr("sem_seg_output.bias"), L.IN_1X1, L.OUT_PLAIN, None, c, E.ws, E.ws.numel(),
+                                     E.defer_handle(), E.st())
                 dxa = E.new_act(n, x_dec.h, x_dec.w, c)
-                L.check(E.lib.isa_conv_gemm(dy.d(), None, E.packer.ptr(reg["dgrad"]), reg["kp_d"], None, dxa.d(),
-                                            L.IN_1X1, L.OUT_PLAIN, None, 0, E.st()), "isa_conv_gemm(dgrad sem)")
+                E.lib.isa_conv_gemm(dy.d(), None, E.packer.ptr(reg["dgrad"]), reg["kp_d"], None, dxa.d(), L.IN_1X1,
+                                    L.OUT_PLAIN, None, 0, E.st())
                 dg, dmean = E.scratch(n * c), E.f32(n * c)
                 acc = E.grads.claim(x_dec, E)
-                L.check(E.lib.isa_se_bwd(dxa.d(), x_dec.d(), L.ptr(gate), L.ptr(hid), L.ptr(mean),
-                                         P.ptr("channelAttend.fc.0.weight"), P.ptr("channelAttend.fc.2.weight"), 16,
-                                         L.ptr(dg), L.ptr(dmean), P.gptr("channelAttend.fc.0.weight"),
-                                         P.gptr("channelAttend.fc.0.bias"), P.gptr("channelAttend.fc.2.weight"),
-                                         P.gptr("channelAttend.fc.2.bias"), E.grads.grad_of(x_dec).d(), acc, E.st()),
-                        "isa_se_bwd")
+                E.lib.isa_se_bwd(dxa.d(), x_dec.d(), gate, hid, mean, P.ptr("channelAttend.fc.0.weight"),
+                                 P.ptr("channelAttend.fc.2.weight"), 16, dg, dmean, P.gptr("channelAttend.fc.0.weight"),
+                                 P.gptr("channelAttend.fc.0.bias"), P.gptr("channelAttend.fc.2.weight"),
+                                 P.gptr("channelAttend.fc.2.bias"), E.grads.grad_of(x_dec).d(), acc, E.st())
             E.tape.append(bwd)
         return sem
 
@@ -290,8 +286,7 @@ class Network:
         d2 = alloc((n, h, w), torch.int32) if want[1] else None
         near = alloc((n, h, w), torch.uint8) if want[2] else None
         scratch = alloc((L.edt_scratch_bytes(n, h, w),), torch.uint8)
-        L.check(E.lib.isa_edt2_u8(L.ptr(labels), n, h, w, L.ptr(d1), L.ptr(d2), L.ptr(near), L.ptr(scratch), scratch.numel(),
-                                  E.st()), "isa_edt2_u8")
+        E.lib.isa_edt2_u8(labels, n, h, w, d1, d2, near, scratch, scratch.numel(), E.st())
         return d1, d2, near
 
     def border_weights(self, labels: torch.Tensor, cfg: torch.Tensor, alloc=None):
@@ -302,8 +297,7 @@ class Network:
         alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=labels.device))
         d1, d2, _ = self.distance_transform(labels, (True, True, False), alloc)
         out = alloc((n, h, w), torch.float32)
-        L.check(E.lib.isa_border_weights(L.ptr(labels), L.ptr(d1), L.ptr(d2), L.ptr(cfg), n, h * w, L.ptr(out), E.st()),
-                "isa_border_weights")
+        E.lib.isa_border_weights(labels, d1, d2, cfg, n, h * w, out, E.st())
         return out
 
     def fill_labels(self, labels: torch.Tensor, fg: torch.Tensor, max_dist_sq=-1):
@@ -315,24 +309,40 @@ class Network:
         d1, _, near = self.distance_transform(labels, (True, False, True))
         out = torch.empty_like(labels)
         filled = torch.empty((n,), dtype=torch.int32, device=labels.device)
-        L.check(E.lib.isa_fill_labels(L.ptr(labels), L.ptr(fg), L.ptr(near), L.ptr(d1), int(max_dist_sq), n, h * w, L.ptr(out),
-                                      L.ptr(filled), E.st()), "isa_fill_labels")
+        E.lib.isa_fill_labels(labels, fg, near, d1, int(max_dist_sq), n, h * w, out, filled, E.st())
         return out, filled
+
+    def labels_from_planes(self, planes: torch.Tensor, what, alloc):
+        """(uint8 label map [n,h,w], k) of k instance planes in any form forward() takes: uint8 [n,h,w,k], int64 or fp32
+        [n,k,h,w]; 0 = background, i + 1 = plane i, the first plane gets an overlap (isa_labels_from_planes).
+        alloc(shape, dtype): where the map comes from; what: the argument's name in the error text."""
+        E = self.E
+        form = {torch.uint8: L.PLANES_U8_NHWK, torch.int64: L.PLANES_I64_NKHW,
+                torch.float32: L.PLANES_F32_NKHW}.get(planes.dtype)
+        if form is None:
+            raise TypeError("%s: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % (what, planes.dtype))
+        n, h, w, k = planes.shape if form == L.PLANES_U8_NHWK else (planes.shape[i] for i in (0, 2, 3, 1))
+        assert planes.is_contiguous(), "%s must be contiguous" % what
+        lab = alloc((n, h, w), torch.uint8)
+        E.lib.isa_labels_from_planes(planes, form, n, k, h * w, lab, E.st())
+        return lab, k
+
+    def labels_from_onehot(self, onehot: torch.Tensor, alloc):
+        """uint8 label map [n,h,w] of a one-hot int64 [n,K,h,w] (isa_labels_from_onehot); alloc(shape, dtype): where from."""
+        E = self.E
+        n, K, h, w = onehot.shape
+        labels = alloc((n, h, w), torch.uint8)
+        E.lib.isa_labels_from_onehot(onehot, n, K, h * w, labels, None, E.st())
+        return labels
 
     def _border_map(self, sem: Act, ins: torch.Tensor):
         """The step's border weight map fp32 [n,h,w] from its instance planes (either form forward() takes), in the arena."""
         E = self.E
         if ins is None or ins.dim() != 4 or ins.numel() == 0:
             raise ValueError("the border weight is on: the step needs the batch's instance planes")
-        form = {torch.uint8: L.PLANES_U8_NHWK, torch.int64: L.PLANES_I64_NKHW, torch.float32: L.PLANES_F32_NKHW}.get(ins.dtype)
-        if form is None:
-            raise TypeError("instance planes: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % ins.dtype)
-        n, h, w = sem.n, sem.h, sem.w
-        k = ins.shape[3] if form == L.PLANES_U8_NHWK else ins.shape[1]
-        assert ins.is_contiguous() and ins.numel() == n * h * w * k, "instance planes do not match the logits"
-        lab = E.arena.alloc((n, h, w), torch.uint8)
-        L.check(E.lib.isa_labels_from_planes(L.ptr(ins), form, n, k, h * w, L.ptr(lab), E.st()), "isa_labels_from_planes")
-        return self.border_weights(lab, self.crit.border, E.arena.alloc)
+        lab, _ = self.labels_from_planes(ins, "instance planes", E.arena.alloc)
+        assert lab.numel() == sem.n * sem.h * sem.w, "instance planes do not match the logits"
+        return self.border_weights(lab.view(sem.n, sem.h, sem.w), self.crit.border, E.arena.alloc)
 
     def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None, ins: torch.Tensor = None):
         """Trainer-side semantic criterion on the logits (model.py:255-269), per self.crit: CE (weighted) and / or
@@ -344,22 +354,19 @@ class Network:
         n = sem.n
         if self.crit.legacy:             # the shipped criterion: its pinned 2-class kernels
             sums = E.scratch(8 * n)
-            L.check(E.lib.isa_mask_loss_sums(sem.d(), None, L.ptr(sem_onehot), L.ptr(sums), E.st()), "isa_mask_loss_sums")
+            E.lib.isa_mask_loss_sums(sem.d(), None, sem_onehot, sums, E.st())
             coef, scal = E.f32(4 * n), E.f32(2)
-            L.check(E.lib.isa_sem_loss(L.ptr(sums), n, L.ptr(coef), L.ptr(scal), E.st()), "isa_sem_loss")
+            E.lib.isa_sem_loss(sums, n, coef, scal, E.st())
             if E.record:
                 def bwd():
                     acc = E.grads.claim(sem, E)
-                    L.check(E.lib.isa_mask_loss_grad(sem.d(), None, L.ptr(sem_onehot), L.ptr(coef),
-                                                     E.grads.grad_of(sem).d(), acc, E.st()), "isa_mask_loss_grad(sem)")
+                    E.lib.isa_mask_loss_grad(sem.d(), None, sem_onehot, coef, E.grads.grad_of(sem).d(), acc, E.st())
                 E.tape.append(bwd)
             return scal
         K, cfg = sem.c, self.crit.cfg
         if labels is None:
             assert sem_onehot.dtype == torch.int64 and tuple(sem_onehot.shape) == (n, K, sem.h, sem.w)
-            labels = E.arena.alloc((n, sem.h, sem.w), torch.uint8)
-            L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, K, sem.h * sem.w, L.ptr(labels), None, E.st()),
-                    "isa_labels_from_onehot")
+            labels = self.labels_from_onehot(sem_onehot, E.arena.alloc)
         assert labels.dtype == torch.uint8 and tuple(labels.shape) == (n, sem.h, sem.w)
         pixw = self._border_map(sem, ins) if self.crit.border_on else None
         if self.crit.lovasz:
@@ -367,8 +374,7 @@ class Network:
         sums = E.scratch(3 * n * K + 2)
         self._k_sums(sem, labels, pixw, sums)
         coef, scal = E.f32(3 * n * K + 1), E.f32(2)
-        L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
-                "isa_sem_loss_k_assemble")
+        E.lib.isa_sem_loss_k_assemble(sums, cfg, n, K, coef, scal, E.st())
         if E.record:
             def bwd():
                 acc = E.grads.claim(sem, E)
@@ -379,19 +385,16 @@ class Network:
     def _k_sums(self, sem, labels, pixw, sums):
         E, cfg = self.E, self.crit.cfg
         if pixw is None:
-            L.check(E.lib.isa_sem_loss_k_sums(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(sums), E.st()), "isa_sem_loss_k_sums")
+            E.lib.isa_sem_loss_k_sums(sem.d(), labels, cfg, sums, E.st())
         else:
-            L.check(E.lib.isa_sem_loss_k_sums_pw(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(pixw), L.ptr(sums), E.st()),
-                    "isa_sem_loss_k_sums_pw")
+            E.lib.isa_sem_loss_k_sums_pw(sem.d(), labels, cfg, pixw, sums, E.st())
 
     def _k_grad(self, sem, labels, pixw, coef, dsem, acc):
         E, cfg = self.E, self.crit.cfg
         if pixw is None:
-            L.check(E.lib.isa_sem_loss_k_grad(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), dsem, acc, E.st()),
-                    "isa_sem_loss_k_grad")
+            E.lib.isa_sem_loss_k_grad(sem.d(), labels, cfg, coef, dsem, acc, E.st())
         else:
-            L.check(E.lib.isa_sem_loss_k_grad_pw(sem.d(), L.ptr(labels), L.ptr(cfg), L.ptr(coef), L.ptr(pixw), dsem, acc,
-                                                 E.st()), "isa_sem_loss_k_grad_pw")
+            E.lib.isa_sem_loss_k_grad_pw(sem.d(), labels, cfg, coef, pixw, dsem, acc, E.st())
 
     def _lovasz_loss(self, sem: Act, labels: torch.Tensor, pixw: torch.Tensor = None):
         """CELovasz: the CE term from the K-class kernels as they are, then the Lovasz-Softmax launches (keys, segmented
@@ -412,8 +415,7 @@ class Network:
             sums = E.scratch(3 * n * K + 2)
             self._k_sums(sem, labels, pixw, sums)
             coef = E.f32(3 * n * K + 1)
-            L.check(E.lib.isa_sem_loss_k_assemble(L.ptr(sums), L.ptr(cfg), n, K, L.ptr(coef), L.ptr(scal), E.st()),
-                    "isa_sem_loss_k_assemble")
+            E.lib.isa_sem_loss_k_assemble(sums, cfg, n, K, coef, scal, E.st())
         record = E.record
         G = E.scratch(K * nimg).view(torch.int32)                       # zero at step start: the keys kernel adds to it
         partial = E.arena.alloc((K * nimg * ntiles,), torch.float64)
@@ -426,18 +428,14 @@ class Network:
         for c0 in range(0, K, kg):
             nc = min(kg, K - c0)
             s0 = c0 * nimg
-            L.check(E.lib.isa_lovasz_keys(sem.d(), L.ptr(labels), c0, nc, per_image, L.ptr(k_in), L.ptr(v_in),
-                                          L.ptr(G[s0:]), E.st()), "isa_lovasz_keys")
-            L.check(E.lib.isa_segsort_kv_u32(L.ptr(k_in), L.ptr(v_in), L.ptr(k_out), L.ptr(v_out), nc * nimg, seglen, 0, 30,
-                                             L.ptr(k_tmp), L.ptr(v_tmp), L.ptr(table), table.numel(), E.st()),
-                    "isa_segsort_kv_u32")
-            L.check(E.lib.isa_lovasz_coef(L.ptr(k_out), L.ptr(v_out), L.ptr(G[s0:]), nc * nimg, seglen, L.ptr(tcnt),
-                                          L.ptr(partial[s0 * ntiles:]), L.ptr(gpix[s0 * seglen:]) if record else None,
-                                          E.st()), "isa_lovasz_coef")
+            E.lib.isa_lovasz_keys(sem.d(), labels, c0, nc, per_image, k_in, v_in, G[s0:], E.st())
+            E.lib.isa_segsort_kv_u32(k_in, v_in, k_out, v_out, nc * nimg, seglen, 0, 30, k_tmp, v_tmp, table, table.numel(),
+                                     E.st())
+            E.lib.isa_lovasz_coef(k_out, v_out, G[s0:], nc * nimg, seglen, tcnt, partial[s0 * ntiles:],
+                                  gpix[s0 * seglen:] if record else None, E.st())
         segloss = E.arena.alloc((K * nimg,), torch.float64)
         scale = E.f32(K * nimg)
-        L.check(E.lib.isa_lovasz_assemble(L.ptr(partial), L.ptr(G), L.ptr(cfg), n, K, per_image, hw, L.ptr(segloss),
-                                          L.ptr(scale), L.ptr(scal[2:]), E.st()), "isa_lovasz_assemble")
+        E.lib.isa_lovasz_assemble(partial, G, cfg, n, K, per_image, hw, segloss, scale, scal[2:], E.st())
         if record:
             def bwd():
                 acc = E.grads.claim(sem, E)
@@ -445,8 +443,7 @@ class Network:
                 if coef is not None:
                     self._k_grad(sem, labels, pixw, coef, dsem, acc)
                     acc = 1
-                L.check(E.lib.isa_lovasz_grad(sem.d(), L.ptr(gpix), L.ptr(scale), per_image, dsem, acc, E.st()),
-                        "isa_lovasz_grad")
+                E.lib.isa_lovasz_grad(sem.d(), gpix, scale, per_image, dsem, acc, E.st())
             E.tape.append(bwd)
         return scal
 
@@ -466,19 +463,13 @@ class Network:
         mnorm, cnt = alloc((n * 32,), f32), alloc((n * L.DISC_CNT_STRIDE,), i32)
         partial, img = alloc((n * ch * 2,), torch.float64), alloc((n * 8,), torch.float64)
         coef, scal = alloc((n + 1,), f32), alloc((8,), f32)
-        lp, np_, cp = L.ptr(labels), L.ptr(n_obj), L.ptr(cfg)
-        L.check(E.lib.isa_disc_sums(emb.d(), lp, k, L.ptr(slab), L.ptr(cslab), E.st()), "isa_disc_sums")
-        L.check(E.lib.isa_disc_means(L.ptr(slab), L.ptr(cslab), np_, cp, n, hw, L.ptr(mu), L.ptr(m), L.ptr(mnorm), L.ptr(cnt),
-                                     E.st()), "isa_disc_means")
-        L.check(E.lib.isa_disc_hinge(emb.d(), lp, k, np_, L.ptr(mu), cp, norm, L.ptr(hslab), L.ptr(partial), E.st()),
-                "isa_disc_hinge")
-        L.check(E.lib.isa_disc_assemble(L.ptr(hslab), L.ptr(partial), L.ptr(mu), L.ptr(mnorm), L.ptr(cnt), np_, cp, norm, n, hw,
-                                        L.ptr(gconst), L.ptr(coef), L.ptr(img), L.ptr(scal), E.st()), "isa_disc_assemble")
+        E.lib.isa_disc_sums(emb.d(), labels, k, slab, cslab, E.st())
+        E.lib.isa_disc_means(slab, cslab, n_obj, cfg, n, hw, mu, m, mnorm, cnt, E.st())
+        E.lib.isa_disc_hinge(emb.d(), labels, k, n_obj, mu, cfg, norm, hslab, partial, E.st())
+        E.lib.isa_disc_assemble(hslab, partial, mu, mnorm, cnt, n_obj, cfg, norm, n, hw, gconst, coef, img, scal, E.st())
 
         def grad(demb: Act, accumulate):
-            L.check(E.lib.isa_disc_grad(emb.d(), lp, k, np_, L.ptr(mu), L.ptr(gconst), L.ptr(coef), cp, norm, demb.d(),
-                                        int(accumulate), E.st()), "isa_disc_grad")
-        grad.keep = (labels, n_obj, cfg)
+            E.lib.isa_disc_grad(emb.d(), labels, k, n_obj, mu, gconst, coef, cfg, norm, demb.d(), int(accumulate), E.st())
         return scal, mu, grad
 
     def cluster(self, emb: Act, fg: torch.Tensor, method, *, bandwidth=1.5, shifts=3, max_objects=32, max_rounds=None,
@@ -496,18 +487,16 @@ class Network:
         centres = torch.empty((n, 32, 32), dtype=torch.float32, device=dev)
         sizes = torch.empty((n, 32), dtype=torch.int32, device=dev)
         scratch = torch.empty((L.cluster_scratch_bytes(n, hw),), dtype=torch.uint8, device=dev)
-        outs = (L.ptr(labels), L.ptr(n_out), L.ptr(centres), L.ptr(sizes), L.ptr(moved), L.ptr(scratch), E.st())
+        outs = (labels, n_out, centres, sizes, moved, scratch, E.st())
         if method == 'meanshift':
             rounds = int(max_objects if max_rounds is None else max_rounds)
-            L.check(E.lib.isa_cluster_meanshift(emb.d(), L.ptr(fg), float(bandwidth), int(shifts), int(max_objects), rounds,
-                                                int(min_pixels), int(bool(assign_rest)), *outs), "isa_cluster_meanshift")
+            E.lib.isa_cluster_meanshift(emb.d(), fg, float(bandwidth), int(shifts), int(max_objects), rounds,
+                                        int(min_pixels), int(bool(assign_rest)), *outs)
             if refine > 0:
                 n_in, init = n_out.clone(), centres.clone()
-                L.check(E.lib.isa_cluster_kmeans(emb.d(), L.ptr(fg), L.ptr(n_in), L.ptr(init), 32, int(refine), *outs),
-                        "isa_cluster_kmeans")
+                E.lib.isa_cluster_kmeans(emb.d(), fg, n_in, init, 32, int(refine), *outs)
         else:
-            L.check(E.lib.isa_cluster_kmeans(emb.d(), L.ptr(fg), L.ptr(n_objects), L.ptr(init), int(max_objects), int(iters),
-                                             *outs), "isa_cluster_kmeans")
+            E.lib.isa_cluster_kmeans(emb.d(), fg, n_objects, init, int(max_objects), int(iters), *outs)
         return labels, n_out, centres, sizes, moved
 
     def onehot_map(self, sem_onehot: torch.Tensor) -> torch.Tensor:
@@ -517,21 +506,20 @@ class Network:
         assert c == self.n_classes and sem_onehot.dtype == torch.int64
         out = E.f32(n, h * w)
         if c == 2:
-            L.check(E.lib.isa_onehot_map(L.ptr(sem_onehot), n, h * w, L.ptr(out), E.st()), "isa_onehot_map")
+            E.lib.isa_onehot_map(sem_onehot, n, h * w, out, E.st())
         else:
-            L.check(E.lib.isa_labels_from_onehot(L.ptr(sem_onehot), n, c, h * w, None, L.ptr(out), E.st()),
-                    "isa_labels_from_onehot")
+            E.lib.isa_labels_from_onehot(sem_onehot, n, c, h * w, None, out, E.st())
         return out
 
     def softmax_nchw(self, logits: Act) -> torch.Tensor:
         out = torch.empty((logits.n, logits.c, logits.h, logits.w), dtype=torch.float32, device=logits.buf.device)
-        L.check(self.E.lib.isa_softmax_nchw(logits.d(), L.ptr(out), self.E.st()), "isa_softmax_nchw")
+        self.E.lib.isa_softmax_nchw(logits.d(), out, self.E.st())
         return out
 
     def argmax_map(self, logits: Act):
         E = self.E
         out = E.new_act(logits.n, logits.h, logits.w, 1)
-        L.check(E.lib.isa_chan_argmax(logits.d(), out.d(), E.st()), "isa_chan_argmax")
+        E.lib.isa_chan_argmax(logits.d(), out.d(), E.st())
         return out
 
     def class_map(self, sem: Act) -> torch.Tensor:
@@ -539,7 +527,7 @@ class Network:
         the K channels, first maximum wins, NaN is the maximum.  A new tensor, not arena memory."""
         E = self.E
         out = torch.empty((sem.n, sem.h, sem.w), dtype=torch.uint8, device=sem.buf.device)
-        L.check(E.lib.isa_sem_confusion(sem.d(), None, sem.c, None, None, L.ptr(out), E.st()), "isa_sem_confusion")
+        E.lib.isa_sem_confusion(sem.d(), None, sem.c, None, None, out, E.st())
         return out
 
     def sem_confusion(self, sem: Act, labels: torch.Tensor):
@@ -550,8 +538,7 @@ class Network:
         assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == sem.n * sem.h * sem.w
         conf = torch.empty((sem.n, K, K), dtype=torch.int64, device=sem.buf.device)
         oob = torch.empty((sem.n,), dtype=torch.int32, device=sem.buf.device)
-        L.check(E.lib.isa_sem_confusion(sem.d(), L.ptr(labels), K, L.ptr(conf), L.ptr(oob), None, E.st()),
-                "isa_sem_confusion")
+        E.lib.isa_sem_confusion(sem.d(), labels, K, conf, oob, None, E.st())
         return conf, oob
 
     def sem_scores(self, conf: torch.Tensor) -> torch.Tensor:
@@ -560,7 +547,7 @@ class Network:
         E = self.E
         n, K = conf.shape[0], conf.shape[1]
         out = torch.empty((n, 4 + 2 * K), dtype=torch.float64, device=conf.device)
-        L.check(E.lib.isa_sem_scores(L.ptr(conf), n, K, L.ptr(out), E.st()), "isa_sem_scores")
+        E.lib.isa_sem_scores(conf, n, K, out, E.st())
         return out
 
     def cc_label(self, maps: torch.Tensor, connectivity=8):
@@ -572,8 +559,7 @@ class Network:
         comp = torch.empty((n, h, w), dtype=torch.int32, device=maps.device)
         n_comp = torch.empty((n,), dtype=torch.int32, device=maps.device)
         scratch = torch.empty((L.cc_label_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
-        L.check(E.lib.isa_cc_label(L.ptr(maps), n, h, w, int(connectivity), L.ptr(comp), L.ptr(n_comp), L.ptr(scratch),
-                                   scratch.numel(), E.st()), "isa_cc_label")
+        E.lib.isa_cc_label(maps, n, h, w, int(connectivity), comp, n_comp, scratch, scratch.numel(), E.st())
         return comp, n_comp
 
     def cc_select(self, maps: torch.Tensor, comp: torch.Tensor, mode, min_area=1, max_objects=255):
@@ -587,8 +573,8 @@ class Network:
         count = torch.empty((n,), dtype=torch.int32, device=maps.device)
         dropped = torch.empty((n,), dtype=torch.int32, device=maps.device)
         scratch = torch.empty((L.cc_select_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
-        L.check(E.lib.isa_cc_select(L.ptr(maps), L.ptr(comp), n, h, w, int(mode), int(min_area), int(max_objects), L.ptr(out),
-                                    L.ptr(count), L.ptr(dropped), L.ptr(scratch), scratch.numel(), E.st()), "isa_cc_select")
+        E.lib.isa_cc_select(maps, comp, n, h, w, int(mode), int(min_area), int(max_objects), out, count, dropped, scratch,
+                            scratch.numel(), E.st())
         return out, count, dropped
 
     # ------------------------------------------------------------------ boundary
@@ -600,7 +586,7 @@ class Network:
         dst = E.new_act(n, h, w, c, ld=rup(c, 8))
         dst.needs_grad = False
         self._keep = x
-        L.check(E.lib.isa_nchw_to_nhwc(L.ptr(x), c, dst.d(), E.st()), "isa_nchw_to_nhwc")
+        E.lib.isa_nchw_to_nhwc(x, c, dst.d(), E.st())
         return dst
 
     def image_ex(self, rgb: torch.Tensor) -> Act:
@@ -614,7 +600,7 @@ class Network:
         dst = E.new_act(n, h, w, 21, ld=24)
         dst.needs_grad = False
         self._keep = rgb
-        L.check(E.lib.isa_image_ex(L.ptr(rgb), dst.d(), E.st()), "isa_image_ex")
+        E.lib.isa_image_ex(rgb, dst.d(), E.st())
         return dst
 
     def input_view(self, x: torch.Tensor) -> Act:
@@ -638,16 +624,14 @@ class Network:
         ins_out = E.arena.alloc((n, k, h, w), torch.int64)
         sem_out = E.arena.alloc((n, C, h, w), torch.int64) if onehot or not labels else None
         if C == 2 and not labels:
-            L.check(E.lib.isa_collate_targets(L.ptr(ins), L.ptr(sem), n, h, w, k, L.ptr(ins_out), L.ptr(sem_out), E.st()),
-                    "isa_collate_targets")
+            E.lib.isa_collate_targets(ins, sem, n, h, w, k, ins_out, sem_out, E.st())
             return sem_out, ins_out
         lab = E.arena.alloc((n, h, w), torch.uint8) if labels else None
-        L.check(E.lib.isa_collate_targets_k(L.ptr(ins), L.ptr(sem), n, h, w, k, C, L.ptr(ins_out), L.ptr(sem_out),
-                                            L.ptr(lab), E.st()), "isa_collate_targets_k")
+        E.lib.isa_collate_targets_k(ins, sem, n, h, w, k, C, ins_out, sem_out, lab, E.st())
         return (sem_out, ins_out, lab) if labels else (sem_out, ins_out)
 
     def to_nchw(self, a: Act) -> torch.Tensor:
         E = self.E
         out = torch.empty((a.n, a.c, a.h, a.w), dtype=torch.float32, device=a.buf.device)
-        L.check(E.lib.isa_nhwc_to_nchw(a.d(), L.ptr(out), E.st()), "isa_nhwc_to_nchw")
+        E.lib.isa_nhwc_to_nchw(a.d(), out, E.st())
         return out

@@ -252,10 +252,8 @@ class RecordLoader(object):
         rgb2 = D.resize_bilinear(rgb, (self.h, self.w), dev)
         p2 = torch.empty((1, self.h, self.w, self.k), dtype=torch.uint8, device=dev)
         s2 = torch.empty((1, self.h, self.w, 1), dtype=torch.uint8, device=dev)
-        L.check(L.lib().isa_resize_nearest_u8(L.ptr(planes), 1, h1, w1, self.k, L.ptr(p2), self.h, self.w, L.stream_ptr()),
-                "isa_resize_nearest_u8")
-        L.check(L.lib().isa_resize_nearest_u8(L.ptr(semt.contiguous()), 1, h1, w1, 1, L.ptr(s2), self.h, self.w, L.stream_ptr()),
-                "isa_resize_nearest_u8")
+        L.checked().isa_resize_nearest_u8(planes, 1, h1, w1, self.k, p2, self.h, self.w, L.stream_ptr())
+        L.checked().isa_resize_nearest_u8(semt.contiguous(), 1, h1, w1, 1, s2, self.h, self.w, L.stream_ptr())
         return rgb2, s2[..., 0], p2, n_obj
 
     def __iter__(self):

@@ -250,20 +250,14 @@ class ReSeg(nn.Module):
     # ------------------------------------------------------------------ scoring instance predictions on the device
     def _label_map(self, planes, what):
         """uint8 label map [B, H*W] of ground-truth planes in either form forward() takes (isa_labels_from_planes)."""
-        E = self.engine
         t = planes.to(self.store.device).contiguous()
         assert t.dim() == 4, "%s must be uint8 [B,H,W,K] or int64 [B,K,H,W]" % what
-        if t.dtype == torch.uint8:
-            (n, h, w, k), form = t.shape, L.PLANES_U8_NHWK
-        elif t.dtype == torch.int64:
-            (n, k, h, w), form = t.shape, L.PLANES_I64_NKHW
-        elif t.dtype == torch.float32:
-            (n, k, h, w), form = t.shape, L.PLANES_F32_NKHW
-        else:
-            raise TypeError("%s: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % (what, t.dtype))
-        out = torch.empty((n, h * w), dtype=torch.uint8, device=t.device)
-        L.check(E.lib.isa_labels_from_planes(L.ptr(t), form, n, k, h * w, L.ptr(out), E.st()), "isa_labels_from_planes")
-        return out, k
+        out, k = self.net.labels_from_planes(t, what, self._new)
+        return out.view(out.shape[0], -1), k
+
+    def _new(self, shape, dtype):
+        """The allocator of the calls that answer in new tensors, not in a step's arena."""
+        return torch.empty(shape, dtype=dtype, device=self.store.device)
 
     def _pair_scores(self, a, b, na, nb, n_a, n_b, oob):
         """[B,8] scores (isa_instance_scores) of the uint8 maps a, b [B, L]; the out-of-range counts go to oob [B]."""
@@ -273,10 +267,8 @@ class ReSeg(nn.Module):
             raise ValueError("label ids: %d x %d counters; each side at most 256 and the product at most 16384" % (na, nb))
         hist = torch.empty((n, na, nb), dtype=torch.int32, device=a.device)
         out = torch.empty((n, 8), dtype=torch.float64, device=a.device)
-        L.check(E.lib.isa_label_pair_hist(L.ptr(a), L.ptr(b), n, Lp, na, nb, L.ptr(hist), L.ptr(oob), L.HIST_AGGREGATE,
-                                          E.st()), "isa_label_pair_hist")
-        L.check(E.lib.isa_instance_scores(L.ptr(hist), n, na, nb, L.ptr(n_a), L.ptr(n_b), L.ptr(out), E.st()),
-                "isa_instance_scores")
+        E.lib.isa_label_pair_hist(a, b, n, Lp, na, nb, hist, oob, L.HIST_AGGREGATE, E.st())
+        E.lib.isa_instance_scores(hist, n, na, nb, n_a, n_b, out, E.st())
         return out
 
     def score_instances(self, labels, n_objects, ins_target, n_target, sem_argmax=None, sem_target=None, *,
@@ -323,9 +315,7 @@ class ReSeg(nn.Module):
                 else:
                     assert st.dtype == torch.int64 and st.dim() == 4, "sem_target: one-hot int64 [B,C,H,W]"
                     nc = st.shape[1]
-                    fg_gt = torch.empty((B, st.shape[2] * st.shape[3]), dtype=torch.uint8, device=dev)
-                    L.check(self.engine.lib.isa_labels_from_onehot(L.ptr(st), B, nc, fg_gt.shape[1], L.ptr(fg_gt), None,
-                                                                   self.engine.st()), "isa_labels_from_onehot")
+                    fg_gt = self.net.labels_from_onehot(st, self._new).view(st.shape[0], -1)
                 assert tuple(fg_gt.shape) == tuple(pred.shape) == tuple(fg_pred.shape)
                 sem = self._pair_scores(fg_gt, fg_pred, nc, 2, None, None, oob[1])
                 out[:, 6].copy_(sem[:, 6])
@@ -343,6 +333,25 @@ class ReSeg(nn.Module):
             return out
 
     # ------------------------------------------------------------------ discriminative embedding loss
+    def _emb_act(self, emb):
+        """(Act, emb was one already) of an embedding: an engine Act as it is, fp32 or bf16 [B,C,H,W] copied into NHWC."""
+        from .engine import Act, rup
+        as_act = isinstance(emb, Act)
+        if as_act:
+            a = emb
+        else:
+            dev = self.store.device
+            t = emb.to(dev)
+            if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError("emb: fp32 or bf16 [B,C,H,W] or an engine Act, got %s %s" % (t.dtype, tuple(t.shape)))
+            B, C, H, W = t.shape
+            buf = torch.zeros((B, H, W, rup(C, 8)), dtype=t.dtype, device=dev)
+            buf[..., :C].copy_(t.permute(0, 2, 3, 1))
+            a = Act(buf, 0, C)
+        if not 1 <= a.c <= 32:
+            raise ValueError("emb: 1..32 channels, got %d" % a.c)
+        return a, as_act
+
     def discriminative_loss(self, emb, ins, n_objects, delta_var=0.5, delta_dist=1.5, norm=2, form='reference',
                             weights=None, unit_means=None, grad=False):
         """The discriminative (pull / push) loss of an instance embedding, on the device (DiscriminativeLoss,
@@ -355,23 +364,11 @@ class ReSeg(nn.Module):
         gamma, gamma_q) and unit_means override the form's.  Returns a dict of device tensors: loss, var, dist, reg, qreg
         (scalars) and means [B,K,C]; with grad=True also grad = d loss / d emb, shaped like emb (an Act for an Act).  Nothing
         is read back: the call does not synchronise."""
-        from .engine import Act, rup
+        from .engine import Act
         from .network import DiscCriterion
         dev = self.store.device
         with torch.no_grad():
-            if isinstance(emb, Act):
-                a, as_act = emb, True
-            else:
-                as_act = False
-                t = emb.to(dev)
-                if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
-                    raise TypeError("emb: fp32 or bf16 [B,C,H,W] or an engine Act, got %s %s" % (t.dtype, tuple(t.shape)))
-                B, C, H, W = t.shape
-                buf = torch.zeros((B, H, W, rup(C, 8)), dtype=t.dtype, device=dev)
-                buf[..., :C].copy_(t.permute(0, 2, 3, 1))
-                a = Act(buf, 0, C)
-            if not 1 <= a.c <= 32:
-                raise ValueError("emb: 1..32 channels, got %d" % a.c)
+            a, as_act = self._emb_act(emb)
             lab = ins.to(dev).contiguous()
             if lab.dtype == torch.uint8 and lab.dim() == 3:
                 labels, k = lab.view(lab.shape[0], -1), L.DISC_MAX_K
@@ -384,8 +381,7 @@ class ReSeg(nn.Module):
             assert n_obj.numel() == a.n
             crit = DiscCriterion(dev)
             crit.set(1.0, delta_var, delta_dist, norm, form, weights, unit_means)
-            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-            scal, mu, gfn = self.net.disc_loss(a, labels, k, n_obj, crit.cfg, crit.norm, alloc)
+            scal, mu, gfn = self.net.disc_loss(a, labels, k, n_obj, crit.cfg, crit.norm, self._new)
             out = dict(loss=scal[0], var=scal[1], dist=scal[2], reg=scal[3], qreg=scal[4], means=mu[:, :k, :a.c])
             if grad:
                 g = Act(torch.empty_like(a.buf), a.c0, a.c)
@@ -406,13 +402,18 @@ class ReSeg(nn.Module):
             assert x.dim() == 4 and x.shape[1] == 21, "expects [B,21,H,W] (ImageEx tensor, utils.py:109)"
             B, H, W = x.shape[0], x.shape[2], x.shape[3]
         assert H % 16 == 0 and W % 16 == 0
+        x_dec, feats = self._eval_unet(x, key)
+        return x_dec, feats, B, H, W
+
+    def _eval_unet(self, x, key):
+        """Starts an eval-mode step in the arena of (key, x's shape and dtype), repacks weights that changed and runs the
+        backbone on `x`: (x_dec, feats).  Asks nothing of the model's heads; the caller has checked for eval mode."""
         E, net = self.engine, self.net
         E.begin(bn_train=False, record=False, key=(key, tuple(x.shape), x.dtype))
         if getattr(self, "_weights_dirty", True) and E.packer.entries:
             E.packer.pack()
         self._weights_dirty = False
-        x_dec, feats = net.unet(net.input_view(x))
-        return x_dec, feats, B, H, W
+        return net.unet(net.input_view(x))
 
     def embedding(self, x):
         """The instance embedding x_enc float32 [B,24,H,W] of images `x` (either input form of forward) from the eval-mode
@@ -442,7 +443,6 @@ class ReSeg(nn.Module):
         Returns a dict of device tensors: labels uint8 [B,H,W] (0 background, 1..n in the order of the centres), n_objects
         int32 [B], centres float32 [B,32,C], sizes int32 [B,32], moved int32 [B] (k-means: pixels whose label changed in the
         last iteration).  Bit-reproducible; nothing is read back: the call does not synchronise and can be captured."""
-        from .engine import Act, rup
         if method not in ('meanshift', 'kmeans'):
             raise ValueError("method must be 'meanshift' or 'kmeans', got %r" % (method,))
         max_objects, shifts, iters, refine, min_pixels = int(max_objects), int(shifts), int(iters), int(refine), int(min_pixels)
@@ -464,18 +464,7 @@ class ReSeg(nn.Module):
             raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
         dev = self.store.device
         with torch.no_grad():
-            if isinstance(emb, Act):
-                a = emb
-            else:
-                t = emb.to(dev)
-                if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
-                    raise TypeError("emb: fp32 or bf16 [B,C,H,W] or an engine Act, got %s %s" % (t.dtype, tuple(t.shape)))
-                B, C, H, W = t.shape
-                buf = torch.zeros((B, H, W, rup(C, 8)), dtype=t.dtype, device=dev)
-                buf[..., :C].copy_(t.permute(0, 2, 3, 1))
-                a = Act(buf, 0, C)
-            if not 1 <= a.c <= 32:
-                raise ValueError("emb: 1..32 channels, got %d" % a.c)
+            a, _ = self._emb_act(emb)
             f = fg.to(dev)
             if f.dtype != torch.uint8:
                 f = (f != 0).to(torch.uint8)
@@ -628,14 +617,9 @@ class ReSeg(nn.Module):
         """Backbone and semantic head alone, eval mode: leaves the logits of `x` (either input form of forward) in
         self._last_sem for class_map() / score_semantic().  Works for instance models too (their head is not run)."""
         assert not self.training, "eval mode only (running BatchNorm statistics)"
-        E, net = self.engine, self.net
         with torch.no_grad():
-            E.begin(bn_train=False, record=False, key=("semantic", tuple(x.shape), x.dtype))
-            if getattr(self, "_weights_dirty", True) and E.packer.entries:
-                E.packer.pack()
-            self._weights_dirty = False
-            x_dec, _ = net.unet(net.input_view(x))
-            self._last_sem = net.sem_head(x_dec)
+            x_dec, _ = self._eval_unet(x, "semantic")
+            self._last_sem = self.net.sem_head(x_dec)
 
     def class_map(self):
         """uint8 class ids [B,H,W] on the device from the logits of the LAST forward() or segment(): arg-max over the
@@ -666,9 +650,7 @@ class ReSeg(nn.Module):
             else:
                 assert t.dtype == torch.int64 and t.dim() == 4 and tuple(t.shape[2:]) == (sem.h, sem.w) and \
                     t.shape[0] == sem.n and 2 <= t.shape[1] <= 256, "sem_target: uint8 [B,H,W] or one-hot int64 [B,C,H,W]"
-                labels = torch.empty((sem.n, sem.h, sem.w), dtype=torch.uint8, device=dev)
-                L.check(self.engine.lib.isa_labels_from_onehot(L.ptr(t), sem.n, t.shape[1], sem.h * sem.w, L.ptr(labels),
-                                                               None, self.engine.st()), "isa_labels_from_onehot")
+                labels = self.net.labels_from_onehot(t, self._new)
             conf, oob = self.net.sem_confusion(sem, labels)
             scores = self.net.sem_scores(conf)
             self.last_sem_oob = oob

@@ -176,26 +176,22 @@ class Trainer:
         self.sqnorm.zero_()
         lo, n_upd = self.lo, st.n_train - self.lo
         params, S = st.flat[lo:st.n_train], self.state
-        tail = (L.ptr(self.sqnorm), float(self.clip))       # ..., gscale, lr_dev, stream follow in every entry
+        tail = (self.sqnorm, float(self.clip))       # ..., gscale, lr_dev, stream follow in every entry
 
         def sqnorm_fn(grad, n, gscale):
-            L.check(lib.isa_sqnorm(L.ptr(grad), n, gscale, L.ptr(self.sqnorm), L.stream_ptr()), "isa_sqnorm")
+            lib.isa_sqnorm(grad, n, gscale, self.sqnorm, L.stream_ptr())
 
         def update_fn(grad, n, gscale):
-            p, g, end = L.ptr(params), L.ptr(grad), (gscale, L.ptr(self.lr_dev), L.stream_ptr())
+            p, g, end = params, grad, (gscale, self.lr_dev, L.stream_ptr())
             if self.optimizer == 'Adadelta':
-                rc = lib.isa_adadelta(p, g, L.ptr(self.sq), L.ptr(self.acc), n, self.lr, self.rho, self.eps, self.wd,
-                                      *tail, *end)
+                lib.isa_adadelta(p, g, self.sq, self.acc, n, self.lr, self.rho, self.eps, self.wd, *tail, *end)
             elif self.optimizer == 'Adam':
-                rc = lib.isa_adam(p, g, L.ptr(S["exp_avg"]), L.ptr(S["exp_avg_sq"]), L.ptr(S["step"]),
-                                  L.ptr(self._adam_aux), n, self.lr, self.betas[0], self.betas[1], self.adam_eps, self.wd,
-                                  *tail, *end)
+                lib.isa_adam(p, g, S["exp_avg"], S["exp_avg_sq"], S["step"], self._adam_aux, n, self.lr, self.betas[0],
+                             self.betas[1], self.adam_eps, self.wd, *tail, *end)
             elif self.optimizer == 'RMSprop':
-                rc = lib.isa_rmsprop(p, g, L.ptr(S["square_avg"]), n, self.lr, self.alpha, self.rms_eps, self.wd,
-                                     *tail, *end)
+                lib.isa_rmsprop(p, g, S["square_avg"], n, self.lr, self.alpha, self.rms_eps, self.wd, *tail, *end)
             else:
-                rc = lib.isa_sgd(p, g, L.ptr(S["momentum_buffer"]), n, self.lr, self.momentum, self.wd, *tail, *end)
-            L.check(rc, "isa_" + self.optimizer.lower())
+                lib.isa_sgd(p, g, S["momentum_buffer"], n, self.lr, self.momentum, self.wd, *tail, *end)
 
         exchange_and_update(st.grad[lo:st.n_train], n_upd, self.world, sqnorm_fn, update_fn, self.clip)
         self.model.mark_weights_dirty()
