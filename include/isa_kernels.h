@@ -210,6 +210,11 @@ int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* y, const is
  *   dy = BN-backward(g, y; ybn);  dw += dy^T . pro(x);  dx (+)= dy . W;  xbn as above.
  * `addend` (optional, shape of x): dx += addend, e.g. the gradient arriving through the block's residual branch
  * (saves the separate accumulate pass).
+ * y == NULL: the kernel does not read the conv's output but recomputes it per pixel tile as W . pro(x), with the
+ * operand rounding and the MFMA sequence of isa_conv_gemm, and rounds it to bf16 as that call stored it: one cold
+ * N-channel read less, results bit-identical to the call with y.  The caller then guarantees that BN(y)'s input is
+ * what isa_conv_gemm stored for this x, this prologue and this w (bf16, 1x1, no bias, ISA_OUT_PLAIN, no accumulate).
+ * Only with ybn->act ISA_ACT_RELU6 or ISA_ACT_NONE; any other activation with y == NULL is ISA_EINVAL.
  * bf16 storage only, N <= 64, K <= 64, both multiples of 8; otherwise ISA_EINVAL (callers then use
  * isa_bn_bwd_apply + isa_conv_wgrad + isa_conv_gemm).                                               */
 int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,

@@ -3,7 +3,8 @@
 //     dW  += dy^T . pro(x)                             (isa_conv_wgrad)
 //     dx (+)= dy . W                                   (isa_conv_gemm data gradient)
 //     xbn:  sums of BN(x)'s backward over the finished dx   (isa_bn_bwd_reduce of the layer that made x)
-// in ONE pass: reads g, y, x once and writes dx once (6 narrow-tensor passes instead of 12-13).
+// in ONE pass: reads g, y, x once and writes dx once (6 narrow-tensor passes instead of 12-13).  With y == NULL (REC) y is
+// not read either: the wave recomputes its 32 x N tile from the pro(x) slab and W, bit for bit what isa_conv_gemm stored.
 //
 // Built on the bf16 weight-gradient kernel's structure (conv_wgrad.hip): every WAVE owns 32-pixel chunks,
 // staged row-major in a wave-private LDS slab; no __syncthreads in the main loop; the next chunk's raw
@@ -36,10 +37,38 @@ struct PwParams {
 __device__ unsigned long long phase_buf[10];
 #endif
 
+// dy of one element: BN(y)'s backward (isa_bn_bwd_apply) with q = invstd * mean(g' yhat) and k0 = mean(g').  The recompute
+// variant's form of the expression that the stored-y stash spells out: same operations in the same order
+template <int YACT>
+__device__ __forceinline__ float bn_bwd_dy(float g, float yy, float sc, float sh, float mu, float q, float k0, int rt) {
+    const float dz = g * act_grad_t<YACT>(fmaf(yy, sc, sh), rt);
+    return sc * (dz - k0 - (yy - mu) * q);
+}
+
+// tr_frag (tr_lds.hpp) with the half-waves HS rows apart: element j of lane (r, h) <- tile[row0 + HS h + j][col0 + r]
+template <int HS>
+__device__ __forceinline__ bf16x8 tr_frag_h(const char* tile, int stride_bytes, int row0, int col0, int lane) {
+    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
+    const char* a = tile + (row0 + HS * (g >> 1) + q) * stride_bytes + (col0 + 16 * (g & 1) + 4 * pp) * 2;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_S16X4(a));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_S16X4(a + 4 * stride_bytes));
+    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, v);
+}
+
+// W fragment of the recompute's contraction step s (see wf in the kernel) for the 32-channel tile i, from the [k][n] staging
+template <int WP>
+__device__ __forceinline__ bf16x8 rec_wfrag(const bf16_t* wl, int s, int i, int lane) {
+    return tr_frag_h<16>(reinterpret_cast<const char*>(wl), WP * 2, 32 * (s >> 1) + 8 * (s & 1), i * 32, lane);
+}
+
 // XMODE 0: plain x; 1: x = relu6(scale*x+shift) with BN(x) sums produced; 2: runtime prologue, sums if p.xred
 // EPI: the store epilogue adds the old dx and / or the residual addend (p.accumulate, p.addend); without it their
 // loads and the waits that go with them are compiled out
-template <int TN, int TK, int YACT, int XMODE, bool EPI>
+// REC: y is not read but recomputed per chunk as W . pro(x) from the pro(x) slab and register-held W fragments, with the
+// forward kernel's MFMA sequence (conv_gemm.hip, conv_gemm_kernel) so that the rounded bf16 value is the one it stored;
+// raw g waits in the dy slab and is overwritten by dy in the accumulator layout
+template <int TN, int TK, int YACT, int XMODE, bool EPI, bool REC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pw_bn_bwd_kernel(PwParams p) {
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
     PHASE_DECL(); PHASE(0);
@@ -58,7 +87,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const GroupSel gs = group_sel(p.G);
     if (gs.g) {                                                  // this workgroup's statistic group: rows [g*M, (g+1)*M)
         const long gm = (long)gs.g * p.M;
-        p.g += gm * p.ldg; p.y += gm * p.ldy; p.x += gm * p.ldx; p.dx += gm * p.lddx;
+        p.g += gm * p.ldg;
+        if constexpr (!REC) p.y += gm * p.ldy;
+        p.x += gm * p.ldx; p.dx += gm * p.lddx;
         if (p.addend) p.addend += gm * p.lda;
         p.ysc += gs.g * p.N; p.ysh += gs.g * p.N; p.ymu += gs.g * p.N; p.yis += gs.g * p.N; p.yred += gs.g * ISA_STAT_R * 2 * p.N;
         p.xsc = goff(p.xsc, (long)gs.g * p.K); p.xsh = goff(p.xsh, (long)gs.g * p.K); p.xmu = goff(p.xmu, (long)gs.g * p.K);
@@ -72,7 +103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bool nok = cn0 < p.N, kok = ck0 < p.K;
     const int cnl = nok ? cn0 : 0, ckl = kok ? ck0 : 0;           // clamped: a 16-byte piece that exists in every row
 
-    bf16x8 rg[LOADS_N], ry[LOADS_N], rx[LOADS_K], rxc[LOADS_K];
+    bf16x8 rg[LOADS_N], ry[REC ? 1 : LOADS_N], rx[LOADS_K], rxc[LOADS_K];
     const long nchunks = (p.M + PMB - 1) / PMB;
     // raw 16-byte loads only, for EVERY lane at a clamped address and with no branch in front: nothing here waits on
     // memory, and the number of loads in flight is the same on every path.  stash() zeroes what lies past M, N or K.
@@ -82,7 +113,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int v = 0; v < LOADS_N; ++v) {
             const long m = min(mbase + v * RPN + rown, p.M - 1);
             rg[v] = *reinterpret_cast<const bf16x8*>(p.g + m * p.ldg + cnl);
-            ry[v] = *reinterpret_cast<const bf16x8*>(p.y + m * p.ldy + cnl);
+            if constexpr (!REC) ry[v] = *reinterpret_cast<const bf16x8*>(p.y + m * p.ldy + cnl);
         }
 #pragma unroll
         for (int v = 0; v < LOADS_K; ++v) {
@@ -105,7 +136,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // to the TN*32 x TK*32 tile, so that a fragment is ONE unconditional 16-byte LDS read; the predicated form was
     // 8 * NS * TK single reads, each in an exec-mask region of its own.
     constexpr int WP = TN * 32 + 8;                               // row pitch (bf16): rows stay 16-byte aligned
-    bf16_t* wl = reinterpret_cast<bf16_t*>(ldsb);
+    // WLDS (the recompute variant of the 2 x 2 tile): the recompute's W fragments would be 32 more registers on top of
+    // wb's 32 and the 64 accumulators, i.e. scratch; there the staging lies behind the constants, in the part of the
+    // allocation that only the fold at the end uses, stays for the whole kernel and the fragments are read per chunk
+    constexpr bool WLDS = REC && TN * TK == 4;
+    bf16_t* wl = reinterpret_cast<bf16_t*>(WLDS ? ldsb + 4 * SLAB + 9 * 64 * 4 : ldsb);
     float wv[TN * TK * 4];                                        // requested here, written to LDS after the constants:
 #pragma unroll                                                    // both sets of loads are in flight together
     for (int it = 0; it < TN * TK * 4; ++it) {                    // clamped address, select after: loads back to back
@@ -146,6 +181,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int j = 0; j < TK; ++j)
             wb[s][j] = *reinterpret_cast<const bf16x8*>(wl + (32 * j + r) * WP + 16 * s + 8 * hh);
+    // ---- W fragments for the recompute of y: B[k = 32 g + 16 hh + 8 q + jj][n = 32 i + r], step 2 g + q.  The forward
+    // kernel gives the upper half-wave the upper 16 channels of a 32-group (its A fragments are contiguous row pieces),
+    // and an MFMA's result depends on which contraction slot a product sits in: the same assignment here
+    constexpr bool WREG = REC && !WLDS;
+    bf16x8 wf[WREG ? 2 * TK : 1][WREG ? TN : 1];
+    if constexpr (WREG) {
+#pragma unroll
+        for (int s = 0; s < 2 * TK; ++s)
+#pragma unroll
+            for (int i = 0; i < TN; ++i) wf[s][i] = rec_wfrag<WP>(wl, s, i, lane);
+    }
     __syncthreads();                                              // the slabs reuse W's staging area
     PHASE(2);
 
@@ -160,7 +206,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     auto stash = [&](long chunk) {                               // BN-backward / prologue arithmetic, then LDS
         const long mbase = chunk * PMB;
-        {
+        if constexpr (REC) {                                      // raw g; recompute() turns it into dy
+#pragma unroll
+            for (int v = 0; v < LOADS_N; ++v) *reinterpret_cast<bf16x8*>(sD + (v * RPN + rown) * SN + cgn * 16) = rg[v];
+        } else {
         float ysc[8], ysh[8], ymu[8], yq[8], yk0[8];
         ldc(0, cn0, ysc); ldc(1, cn0, ysh); ldc(2, cn0, ymu); ldc(3, cn0, yq); ldc(4, cn0, yk0);
 #pragma unroll
@@ -215,6 +264,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
         if (chunk + stride < nchunks) fetch(chunk + stride);
+        if constexpr (REC) {
+            // y tile of the chunk in the accumulator layout (lane = channel 32 i + r, 16 pixels), rounded as the forward
+            // stored it, then dy over raw g in the dy slab: every lane reads and rewrites its own elements.  What lies past
+            // M or N is zeroed by an AND on the stored bits: written as a select, the element's LDS read and arithmetic
+            // were sunk into an exec-mask region of its own, 16 dependent LDS round trips per tile
+            const int rows = (int)min((long)PMB, p.M - chunk * PMB) - 4 * hh;
+#pragma unroll
+            for (int i = 0; i < TN; ++i) {                        // one 32-channel tile at a time: 16 live accumulators
+                f32x16 ya = f32x16{0};
+#pragma unroll
+                for (int s = 0; s < 2 * TK; ++s) {
+                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(sX + r * SK + (32 * (s >> 1) + 16 * hh + 8 * (s & 1)) * 2);
+                    bf16x8 b;
+                    if constexpr (WLDS) b = rec_wfrag<WP>(wl, s, i, lane); else b = wf[s][i];
+                    ya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, ya, 0, 0, 0);
+                }
+                const int n = 32 * i + r;
+                const float ysc = cst[0 * 64 + n], ysh = cst[1 * 64 + n], ymu = cst[2 * 64 + n], yq = cst[3 * 64 + n], yk0 = cst[4 * 64 + n];
+                const unsigned colm = n < p.N ? 0xffffu : 0u;
+                unsigned short* d = reinterpret_cast<unsigned short*>(sD + 4 * hh * SN + n * 2);
+                unsigned short gr[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) gr[e] = d[((e & 3) + 8 * (e >> 2)) * (SN / 2)];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float val = bn_bwd_dy<YACT>(__uint_as_float((unsigned)gr[e] << 16), (float)(bf16_t)ya[e], ysc, ysh, ymu, yq, yk0, p.yact);
+                    const unsigned o = __builtin_bit_cast(unsigned short, (bf16_t)val);
+                    d[((e & 3) + 8 * (e >> 2)) * (SN / 2)] = (unsigned short)(o & ((e & 3) + 8 * (e >> 2) < rows ? colm : 0u));
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
         // ---- weight gradient
 #pragma unroll
         for (int s = 0; s < PMB / 16; ++s) {
@@ -325,12 +407,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     PHASE_FLUSH(phase_buf);
 }
 
-template <int TN, int TK, int YACT, int XMODE>
+template <int TN, int TK, int YACT, int XMODE, bool REC>
 int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     constexpr size_t slab = (size_t)32 * (SN + SK) * 4 + 9 * 64 * 4;
     constexpr size_t redb = ((size_t)fold_part_floats<TN, TK>() + 16 * 2 * TK * 32) * 4;   // parked partials + BN(x) sum slots
-    constexpr size_t lds = slab > redb ? slab : redb;
+    constexpr size_t wkeep = (REC && TN * TK == 4) ? (size_t)TK * 32 * (TN * 32 + 8) * 2 : 0;     // WLDS: W stays behind the constants
+    constexpr size_t lds = slab + wkeep > redb ? slab + wkeep : redb;
     const long nchunks = (p.M + 31) / 32;
     const long slabf = (long)TN * TK * 1024 + TN * 32;
     long gx = (nchunks + 3) / 4 * p.G;
@@ -341,8 +424,8 @@ int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* 
     if (gx > ws_cap) gx = ws_cap;
     gx = group_grid(gx, p.G);
     if (int rc = fin_standalone(xfin, p.K, xfin_groups, s)) return rc;      // every check has passed
-    if (p.accumulate || p.addend) hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, true>), dim3((unsigned)gx), dim3(256), lds, s, p);
-    else hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, false>), dim3((unsigned)gx), dim3(256), lds, s, p);
+    if (p.accumulate || p.addend) hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, true, REC>), dim3((unsigned)gx), dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, false, REC>), dim3((unsigned)gx), dim3(256), lds, s, p);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
     return wgrad_slab_reduce_launch(p.ws, p.dw, nullptr, (int)gx, TN, TK, p.N, p.K, 1, sa, s);
 }
@@ -350,12 +433,12 @@ int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* 
 template <int TN, int TK>
 int launch_tile(PwParams& p, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     const bool y6 = p.yact == ISA_ACT_RELU6, y0 = p.yact == ISA_ACT_NONE;
-#define PW_X(YA) (xmode == 0 ? launch_inst<TN, TK, YA, 0>(p, ws_floats, sa, xfin, xfin_groups, s) \
-                : xmode == 1 ? launch_inst<TN, TK, YA, 1>(p, ws_floats, sa, xfin, xfin_groups, s) \
-                             : launch_inst<TN, TK, YA, 2>(p, ws_floats, sa, xfin, xfin_groups, s))
-    if (y6) return PW_X(ISA_ACT_RELU6);
-    if (y0) return PW_X(ISA_ACT_NONE);
-    return PW_X(ACT_RT);
+#define PW_X(YA, RC) (xmode == 0 ? launch_inst<TN, TK, YA, 0, RC>(p, ws_floats, sa, xfin, xfin_groups, s) \
+                    : xmode == 1 ? launch_inst<TN, TK, YA, 1, RC>(p, ws_floats, sa, xfin, xfin_groups, s) \
+                                 : launch_inst<TN, TK, YA, 2, RC>(p, ws_floats, sa, xfin, xfin_groups, s))
+    if (y6) return p.y ? PW_X(ISA_ACT_RELU6, false) : PW_X(ISA_ACT_RELU6, true);
+    if (y0) return p.y ? PW_X(ISA_ACT_NONE, false) : PW_X(ISA_ACT_NONE, true);
+    return PW_X(ACT_RT, false);                                   // a null y was refused by the entry point
 #undef PW_X
 }
 
@@ -370,23 +453,25 @@ extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y,
                                        const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
                                        const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
                                        void* stream) {
-    if (!tensor_ok(g, 8) || !tensor_ok(y, 8) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
+    if (!tensor_ok(g, 8) || (y && !tensor_ok(y, 8)) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
     if (!fin_valid(xpro)) return ISA_EINVAL;      // a pending finalize (no in-kernel form here) runs after the last check
-    if (g->dtype != ISA_BF16 || y->dtype != ISA_BF16 || x->dtype != ISA_BF16 || dx->dtype != ISA_BF16) return ISA_EINVAL;
+    if (g->dtype != ISA_BF16 || (y && y->dtype != ISA_BF16) || x->dtype != ISA_BF16 || dx->dtype != ISA_BF16) return ISA_EINVAL;
     if (!ybn || !ybn->scale || !ybn->shift || !ybn->mean || !ybn->invstd || !ybn->red || !(ybn->count > 0)) return ISA_EINVAL;
     if (!w || !dw || (!ws && !defer)) return ISA_EINVAL;
+    // y == NULL: recomputed in the kernel, which has that form for the two compile-time activations only
+    if (!y && ybn->act != ISA_ACT_RELU6 && ybn->act != ISA_ACT_NONE) return ISA_EINVAL;
     const int N = g->c, K = x->c;
     if (N > 64 || K > 64 || N % 8 || K % 8) return ISA_EINVAL;
-    if (y->c != N || dx->c != K) return ISA_EINVAL;
+    if ((y && y->c != N) || dx->c != K) return ISA_EINVAL;
     const isa_tensor* ts[3] = {y, x, dx};
     for (const isa_tensor* t : ts)
-        if (t->n != g->n || t->h != g->h || t->w != g->w) return ISA_EINVAL;
+        if (t && (t->n != g->n || t->h != g->h || t->w != g->w)) return ISA_EINVAL;
     const ProDev xp = make_pro(xpro);
     if (xp.bscale) return ISA_EINVAL;
     if (xbn && (!xbn->mean || !xbn->invstd || !xbn->out_red)) return ISA_EINVAL;
     PwParams p{};
-    p.g = (const bf16_t*)g->data; p.y = (const bf16_t*)y->data; p.x = (const bf16_t*)x->data; p.dx = (bf16_t*)dx->data;
-    p.w = w; p.dw = dw; p.N = N; p.K = K; p.ldg = g->ld; p.ldy = y->ld; p.ldx = x->ld; p.lddx = dx->ld;
+    p.g = (const bf16_t*)g->data; p.y = y ? (const bf16_t*)y->data : nullptr; p.x = (const bf16_t*)x->data; p.dx = (bf16_t*)dx->data;
+    p.w = w; p.dw = dw; p.N = N; p.K = K; p.ldg = g->ld; p.ldy = y ? y->ld : 0; p.ldx = x->ld; p.lddx = dx->ld;
     p.G = tensor_groups(g);                                       // BN(y) constants and sums are per statistic group
     if (g->n % p.G) return ISA_EINVAL;
     p.M = (long)(g->n / p.G) * g->h * g->w;

@@ -576,6 +576,9 @@ class Engine:
         self._dw_out: Dict[tuple, ConvFusion] = {}
         # the same for bias-free 1x1 convs with <= 64 channels either side (isa_conv1x1_bn_backward, bf16 only)
         self.fuse_pw_bn = os.environ.get("ISA_FUSE_PW_BN", "1") != "0"
+        # ... which recomputes the conv's raw output from x and W instead of reading it (y = NULL); ISA_PW_RECOMPUTE=0
+        # hands it the stored tensor
+        self.pw_recompute = os.environ.get("ISA_PW_RECOMPUTE", "1") != "0"
         # eval mode: BatchNorm (a constant affine), activation and residual ride in the conv's output epilogue
         # (isa_conv_gemm_ep) instead of a lazy prologue in the consumer plus a materialising pass per block
         self.fuse_eval = os.environ.get("ISA_FUSE_EVAL", "1") != "0"
@@ -955,9 +958,14 @@ class Engine:
         ydesc, xdesc = self._fused_descs(x, rec)
         acc = self.grads.claim(x, self)
         g = rec.g
+        # rec.ybn.raw is what isa_conv_gemm stored for this x, this prologue and this weight (conv() fuses bias-free plain
+        # 1x1 bf16 convs only), so the kernel can recompute it; its compile-time activations are the two the blocks use.
+        # More than 32 channels on both sides (the kernel's 2 x 2 tile) keep the stored y: the read saved is a quarter of
+        # the bytes there and the recompute costs as much (profiles/ab_pw_recompute.txt)
+        y = None if (self.pw_recompute and rec.ybn.act in (L.ACT_RELU6, L.ACT_NONE) and min(g.c, x.c) <= 32) else rec.ybn.raw.d()
         if self.profile:
-            self.next_bytes = x.n * x.h * x.w * (2 * g.c + 2 * x.c) * x.buf.element_size()
-        self.lib.isa_conv1x1_bn_backward(g.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
+            self.next_bytes = x.n * x.h * x.w * ((1 if y is None else 2) * g.c + 2 * x.c) * x.buf.element_size()
+        self.lib.isa_conv1x1_bn_backward(g.d(), y, C.byref(ydesc), x.d(), x.p(),
                                          C.byref(xdesc) if xdesc is not None else None, self.params.ptr(wname),
                                          self.params.gptr(wname), self.grads.grad_of(x).d(), acc,
                                          rec.addend.d() if rec.addend is not None else None, self.ws, self.ws.numel(),
