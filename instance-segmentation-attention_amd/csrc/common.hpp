@@ -333,6 +333,15 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's GLOBAL stores (vmcnt(0)
+// ahead of s_barrier): in the persistent tile loops of dwconv.hip that exposed the latency of the output stores once per
+// tile, and in the K loop of conv_gemm_tiled_kernel nothing but LDS is shared between the waves.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // For `item = pixel*cg + channel_group` grid-stride loops: round the grid so that the stride (grid*256) is a multiple
 // of cg.  A lane then keeps ONE channel group for its whole life and its per-channel partial sums are flushed
 // once, not on every trip (cg = 3 for the 24-channel attention tensors: 2048*256 % 3 != 0 flushed every trip).

@@ -484,8 +484,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(GemmParams p) {
 // next tile's global loads are in registers while the MFMAs of the current one run, one barrier per step.  The lazy
 // prologue is applied once per element when the A tile is written to LDS.  Epilogue as above (bias, statistics,
 // transpose through LDS, 16-byte row stores, optional accumulate).
-template <int WN, int PRO, bool EP = false>
-__global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
+// BS: launches whose prologue has a per-image multiplier (Dropout2d) are instantiations of their own: the multiplier is
+// loaded where the tile is stashed, which drains that step's prefetch and needs registers the others then keep for it.
+template <int WN, int PRO, bool EP = false, bool BS = false>
+__global__ __launch_bounds__(256, 2) void conv_gemm_tiled_kernel(GemmParams p) {
     constexpr int BM = 128, BK = 64, BN = 64 * WN, LDT = BK + 8;
     constexpr bool HAS_PRO = PRO != 0;
     constexpr int ACT = PRO == 1 ? ISA_ACT_RELU6 : ACT_RT;
@@ -509,17 +511,9 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
     const int n0 = tn * BN, K = p.kp;
     const bf16_t* xin = reinterpret_cast<const bf16_t*>(p.x);
     const bf16_t* wg = reinterpret_cast<const bf16_t*>(p.w);
-    bool fin = false;                                              // pending finalize: see conv_gemm_kernel
-    if constexpr (HAS_PRO && !EP) fin = p.fin.stats != nullptr;
-    if constexpr (HAS_PRO) {
-        for (int k = tid; k < K; k += 256) {
-            if (fin && k < p.cin) continue;
-            pro_tab[k] = (!fin && p.pro.scale) ? p.pro.scale[k] : 1.f;
-            pro_tab[K + k] = (!fin && p.pro.shift) ? p.pro.shift[k] : 0.f;
-        }
-    }
     // staging: thread -> rows srow + 32 i, 8 contraction elements at sseg
     const int srow = tid >> 3, sseg = (tid & 7) * 8;
+    const int KT = K / BK;                                         // >= 2 (launch0: kp >= 128)
     long aoff[4];
     const float* bsrow[4];
 #pragma unroll
@@ -527,17 +521,7 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
         long m = m0 + srow + 32 * i;
         if (m > p.M - 1) m = p.M - 1;                              // rows >= M read the last valid row; the epilogue masks them
         aoff[i] = m * p.ldx + sseg;
-        bsrow[i] = (HAS_PRO && p.pro.bscale) ? p.pro.bscale + (m / ((long)p.mh * p.mw)) * p.cin + sseg : nullptr;
-    }
-    if constexpr (HAS_PRO && !EP) {
-        if (fin) {                                                 // see conv_gemm_kernel: touch the first tile's rows, finalize
-            unsigned probe[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) probe[i] = *reinterpret_cast<const unsigned*>(xin + aoff[i]);
-            asm volatile("" ::: "memory");
-            bn_fin_inline<256>(p.fin, p.cin, p.G, gs.g, pro_tab, K, tid);
-            asm volatile("" :: "v"(probe[0]), "v"(probe[1]), "v"(probe[2]), "v"(probe[3]));
-        }
+        bsrow[i] = BS ? p.pro.bscale + (m / ((long)p.mh * p.mw)) * p.cin + sseg : nullptr;
     }
     // two register sets: the loads of K tile kt + 2 are issued while tile kt is multiplied and tile kt + 1 is written
     // to LDS - with one workgroup per CU on these small problems nothing else covers the memory latency
@@ -549,14 +533,21 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
         if (n > p.N - 1) n = p.N - 1;                              // rows >= N read the last valid row; zeroed when stashed
         boff[i] = (long)n * K + sseg;
     }
-    auto fetch = [&](Regs& R, int kt) {
+    // (every lambda of the K loop is force-inlined: one left as a call keeps the register sets it captures in scratch)
+    auto fetch = [&](Regs& R, int kt) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) R.a[i] = *reinterpret_cast<const bf16x8*>(xin + aoff[i] + kt * BK);
 #pragma unroll
         for (int i = 0; i < BN / 32; ++i) R.b[i] = *reinterpret_cast<const bf16x8*>(wg + boff[i] + kt * BK);
         asm volatile("" ::: "memory");                              // keep the prefetch here (LLVM sinks loads to their use)
     };
-    auto stash = [&](const Regs& R, int buf, int kt) {
+    auto stash = [&](Regs& R, int buf, int kt) __attribute__((always_inline)) {
+        // the tile's registers are first read HERE: without this the selects and conversions below, which touch no
+        // memory, are placed up among the previous step's MFMAs and take their full wait on the loads along
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(R.a[i]));
+#pragma unroll
+        for (int i = 0; i < BN / 32; ++i) asm volatile("" : "+v"(R.b[i]));
         const bf16x8 (&ra)[4] = R.a;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -569,9 +560,11 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     v[j] = act_t<ACT>(fmaf((float)ra[i][j], j < 4 ? s0[j & 3] : s1[j & 3], j < 4 ? h0[j & 3] : h1[j & 3]), p.pro.act);
-                if (bsrow[i]) {
+                if constexpr (BS) {
+                    const float* bp = bsrow[i] + kt * BK;
+                    asm volatile("" : "+v"(bp));                   // keeps this row's loads here (hoisted, all four rows' spill)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] *= bsrow[i][kt * BK + j];
+                    for (int j = 0; j < 8; ++j) v[j] *= bp[j];
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = (bf16_t)v[j];
@@ -583,21 +576,43 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
             *reinterpret_cast<bf16x8*>(sB + (buf * BN + srow + 32 * i) * LDT + sseg) = (n0 + srow + 32 * i < p.N) ? R.b[i] : bf16x8{0};
     };
 
+    // ---- launch prologue, one round trip: the first two tiles are the kernel's first memory instructions; the scale /
+    // shift table is requested behind them in one batch through pointer selects (a null optional pointer reads the
+    // weights, which always hold K floats' worth of bytes, and the value is replaced by the neutral constant) and waited
+    // for once.  A pending finalize (see conv_gemm_kernel) fills the table itself, behind the same tile requests.
+    Regs R0, R1;
+    fetch(R0, 0);
+    fetch(R1, 1);
+    if constexpr (HAS_PRO) {
+        bool fin = false;
+        if constexpr (!EP) fin = p.fin.stats != nullptr;
+        if (fin) {                                                 // cin == K here: the whole table, and its barrier
+            if constexpr (!EP) bn_fin_inline<256>(p.fin, p.cin, p.G, gs.g, pro_tab, K, tid);
+        } else {
+            constexpr int TJ = 2048 / 256;                         // kp <= 2048 (launch0)
+            const float* sp = p.pro.scale ? p.pro.scale : reinterpret_cast<const float*>(wg);
+            const float* hp = p.pro.shift ? p.pro.shift : reinterpret_cast<const float*>(wg);
+            float sc[TJ], sh[TJ];
+#pragma unroll
+            for (int j = 0; j < TJ; ++j) {
+                const int k = min(tid + 256 * j, K - 1);
+                sc[j] = sp[k]; sh[j] = hp[k];
+            }
+#pragma unroll
+            for (int j = 0; j < TJ; ++j) {
+                const int k = tid + 256 * j;
+                if (k < K) { pro_tab[k] = p.pro.scale ? sc[j] : 1.f; pro_tab[K + k] = p.pro.shift ? sh[j] : 0.f; }
+            }
+            lds_barrier();                                         // pro_tab
+        }
+    }
+
     f32x16 acc[2][WN];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < WN; ++j) acc[i][j] = f32x16{0};
-    const int KT = K / BK;
-    Regs R0, R1;
-    fetch(R0, 0);
-    if (KT > 1) fetch(R1, 1);
-    __syncthreads();                                               // pro_tab
-    stash(R0, 0, 0);
-    __syncthreads();
-    auto step = [&](int kt, Regs& Rnext, Regs& Rfree) {            // Rnext holds tile kt + 1; Rfree (tile kt, already in LDS) takes kt + 2
-        const int buf = kt & 1;
-        if (kt + 2 < KT) fetch(Rfree, kt + 2);
+    auto mma = [&](int buf) __attribute__((always_inline)) {
         const bf16_t* tA = sA + (buf * BM + wm * 64 + r) * LDT + 8 * hh;
         const bf16_t* tB = sB + (buf * BN + wn * 32 * WN + r) * LDT + 8 * hh;
 #pragma unroll
@@ -612,12 +627,34 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
 #pragma unroll
                 for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
-        if (kt + 1 < KT) stash(Rnext, buf ^ 1, kt + 1);
-        __syncthreads();
     };
-    for (int kt = 0; kt < KT; kt += 2) {
-        step(kt, R1, R0);
-        if (kt + 1 < KT) step(kt + 1, R0, R1);
+    // The K loop.  Steady state is straight-line code, two steps per trip (the register sets alternate by name): every step
+    // requests a tile - past the end the last one again, which is never stashed - so the same number of loads is in
+    // flight at the top and the bottom of a trip and the waits ahead of the stash are partial.  The last one or two steps
+    // are peeled: nothing left to request.
+    {
+        stash(R0, 0, 0);
+        lds_barrier();
+        auto step = [&](int kt, Regs& Rnext, Regs& Rfree) __attribute__((always_inline)) {   // Rnext holds tile kt + 1; Rfree (tile kt, already in LDS) takes kt + 2
+            fetch(Rfree, min(kt + 2, KT - 1));
+            mma(kt & 1);
+            stash(Rnext, (kt & 1) ^ 1, kt + 1);
+            lds_barrier();
+        };
+        int kt = 0;
+        for (; kt + 2 < KT; kt += 2) {
+            step(kt, R1, R0);
+            step(kt + 1, R0, R1);
+        }
+        if (kt + 1 < KT) {                                         // KT even: tile kt + 1 is in R1
+            mma(0);
+            stash(R1, 1, kt + 1);
+            lds_barrier();
+            mma(1);
+        } else {
+            mma(0);
+        }
+        lds_barrier();                                             // the epilogue reuses the tile buffers
     }
 
     // ---------------- epilogue (the tile buffers are free now): lane r <-> output channel -----------------------
@@ -692,7 +729,7 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
         }
     }
     if (p.stats) {
-        __shared__ float sred[2 * 128];
+        float* sred = reinterpret_cast<float*>(smem) + 4 * 32 * 33;  // [2][BN], behind the four stage tiles, inside the free tile buffers
         if (tid < 2 * BN) sred[tid] = 0.f;
         __syncthreads();
 #pragma unroll
@@ -714,23 +751,25 @@ __global__ __launch_bounds__(256) void conv_gemm_tiled_kernel(GemmParams p) {
 template <int WN, bool EP>
 int launch_tiled_ep(const GemmParams& p, bool has_pro, hipStream_t s) {
     constexpr int BN = 64 * WN, LDT = 72;
+    // the kernel has no channel guards, and a pending finalize fills exactly cin table entries
+    if (p.cin != p.kp || p.kp % 64 || p.kp < 128 || p.kp > 2048) return ISA_EINVAL;
     const size_t tiles = 2 * (size_t)(128 + BN) * LDT * 2;
     const size_t lds = tiles + (has_pro ? 2 * (size_t)p.kp * 4 : 0);
     const long grid = ((p.M + 127) / 128) * ((p.N + BN - 1) / BN) * p.G;      // p.M is per group
-    const int idx = has_pro && p.pro.act == ISA_ACT_RELU6 ? 1 : (has_pro ? 2 : 0);
-    const void* fn = idx == 1 ? reinterpret_cast<const void*>(&conv_gemm_tiled_kernel<WN, 1, EP>)
-                   : idx == 2 ? reinterpret_cast<const void*>(&conv_gemm_tiled_kernel<WN, 2, EP>)
-                              : reinterpret_cast<const void*>(&conv_gemm_tiled_kernel<WN, 0, EP>);
-    if (lds > 64 * 1024) {
-        static bool configured[3] = {false, false, false};
+    // 0: no prologue; 1 / 2: ReLU6 / run-time activation; 3 / 4: the same with a per-image multiplier
+    const int idx = !has_pro ? 0 : (p.pro.act == ISA_ACT_RELU6 ? 1 : 2) + (p.pro.bscale ? 2 : 0);
+    void (*const fns[5])(GemmParams) = {&conv_gemm_tiled_kernel<WN, 0, EP>, &conv_gemm_tiled_kernel<WN, 1, EP>,
+                                        &conv_gemm_tiled_kernel<WN, 2, EP>, &conv_gemm_tiled_kernel<WN, 1, EP, true>,
+                                        &conv_gemm_tiled_kernel<WN, 2, EP, true>};
+    if (lds > 64 * 1024) {                                         // at most 73 728 + 2 * 2048 * 4 = 90 112 B, no static LDS
+        static bool configured[5] = {false, false, false, false, false};
         if (!configured[idx]) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) return ISA_ELAUNCH;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fns[idx]), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
+                return ISA_ELAUNCH;
             configured[idx] = true;
         }
     }
-    if (idx == 1) hipLaunchKernelGGL((conv_gemm_tiled_kernel<WN, 1, EP>), dim3((unsigned)grid), dim3(256), lds, s, p);
-    else if (idx == 2) hipLaunchKernelGGL((conv_gemm_tiled_kernel<WN, 2, EP>), dim3((unsigned)grid), dim3(256), lds, s, p);
-    else hipLaunchKernelGGL((conv_gemm_tiled_kernel<WN, 0, EP>), dim3((unsigned)grid), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(fns[idx], dim3((unsigned)grid), dim3(256), lds, s, p);
     return launch_status();
 }
 template <int WN>
