@@ -699,6 +699,55 @@ int isa_cc_label(const uint8_t* map, int32_t n, int32_t h, int32_t w, int32_t co
 int isa_cc_select(const uint8_t* map, const int32_t* comp, int32_t n, int32_t h, int32_t w, int32_t mode, int32_t min_area,
                   int32_t max_objects, uint8_t* out, int32_t* count, int32_t* dropped, void* scratch, int64_t scratch_bytes,
                   void* stream);
+/* ---- measuring instances: area, box, moments, perimeter, colour; filtering and ordering by them -----------------------
+ * Every entry checks all its arguments before it launches or writes anything (ISA_EINVAL / ISA_EALIGN), is asynchronous on
+ * `stream`, allocates nothing, needs no scratch and never reads anything back: the launch count is fixed (props 2, the
+ * others 1), so a captured hipGraph replays them.  Integers only up to acc, table, count and dropped: two runs are
+ * bit-identical, whatever order workgroups ran in.  n <= 65535; 1 <= nl <= 256; h, w <= ISA_PROPS_MAX_SIDE (so that no sum
+ * can pass 2^63).  x is the column and y the row of a pixel.
+ * isa_label_props: labels uint8 [n,h,w] (4-byte aligned, h*w % 4 == 0; 16-byte aligned maps with h*w % 16 == 0 are read 16
+ *   pixels per load); image uint8 [n,h,w,c], c in {1,3,4} (c == 4: 4-byte aligned), or NULL with c == 0.
+ *   acc int64 [n][nl][ISA_PROPS_ACC] (8-byte aligned), set to the empty values by the entry itself; oob int32 [n] counts
+ *   the pixels with label >= nl (cleared by the entry).  Label 0 is background and is not measured: its row stays empty.
+ *   Slots of label v (empty label):  0 area (0);  1, 2 min x, max x (w, -1);  3, 4 min y, max y (h, -1);
+ *     5, 6 sum x, sum y (0);  7, 8, 9 sum x^2, sum y^2, sum x*y (0);  10 perimeter (0);
+ *     11 smallest row-major pixel index y*w + x (h*w);  12..15 sum of image channel 0..3 (0; absent channels 0).
+ *   Perimeter is the crack length: the number of (pixel, 4-neighbour) pairs where the pixel holds v and the neighbour
+ *   holds another value or lies outside the image.  One pixel: 4; a 2 x 3 rectangle: 10; the edges of a hole count.
+ * isa_instance_props: out double [n][nl][ISA_PROPS_OUT] (8-byte aligned) from acc; c as given to isa_label_props.
+ *     0 area          1..4 half-open box x0, y0, x1, y1 (min, min, max + 1, max + 1)          5, 6 centroid sum x / A, sum y / A
+ *     7, 8, 9 central second moments per pixel mxx = (A sum x^2 - (sum x)^2) / A^2, myy, mxy = (A sum xy - sum x sum y) / A^2:
+ *       the numerators are formed exactly in 128-bit integers, then divided once
+ *     10, 11 major and minor axis length 4 sqrt(l1), 4 sqrt(l2), l1,2 = (mxx + myy) / 2 +- sqrt(((mxx - myy) / 2)^2 + mxy^2)
+ *     12 eccentricity sqrt(1 - l2 / l1), 0 when l1 == 0
+ *     13 orientation 0.5 atan2(2 mxy, mxx - myy) in (-pi/2, pi/2], 0 when both arguments are 0: the angle of the major axis
+ *        from the x axis, positive towards +y, and y points DOWN (rows), so a positive angle turns clockwise on the screen.
+ *        This is the project's own convention (not scikit-image's, which measures from the row axis).
+ *     14 perimeter          15 1.0 if the box touches an image edge, else 0.0          16 extent A / box area
+ *     17 equivalent diameter sqrt(4 A / pi)          18 compactness 4 pi A / P^2          19 first pixel index
+ *     20..23 mean of image channel 0..3, NaN for absent channels
+ *   A label with area 0 (label 0 always) gives column 0 = 0 and NaN everywhere else.
+ * isa_props_select: table uint8 [n][256] (old label -> new label), count int32 [n], dropped int32 [n] from acc.  A label
+ *   1..nl-1 survives when it is non-empty, min_area <= area, area <= max_area (max_area == 0: no upper limit) and, with
+ *   clear_border == 1, its box touches no image edge.  The survivors are ranked by `order` - ISA_ORDER_LABEL: old label
+ *   ascending; ISA_ORDER_AREA: area descending, equal areas by the smaller old label; ISA_ORDER_RASTER: first pixel
+ *   ascending - and the first max_objects (1..255) get the new labels 1, 2, ..; every other entry of the table is 0.
+ *   count = labels given, dropped = non-empty labels - count.
+ * isa_relabel_u8: out[i][p] = table[i][labels[i][p]] for uint8 maps [n, L]; L % 4 == 0, L < 2^31, maps 4-byte aligned
+ *   (16-byte accesses when both are 16-byte aligned and L % 16 == 0).  out == labels is allowed; any other overlap is
+ *   ISA_EINVAL. */
+#define ISA_PROPS_ACC 16
+#define ISA_PROPS_OUT 24
+#define ISA_PROPS_MAX_SIDE 32768
+enum { ISA_ORDER_LABEL = 0, ISA_ORDER_AREA = 1, ISA_ORDER_RASTER = 2 };
+int isa_label_props(const uint8_t* labels, const uint8_t* image, int32_t n, int32_t h, int32_t w, int32_t c, int32_t nl,
+                    int64_t* acc, int32_t* oob, void* stream);
+int isa_instance_props(const int64_t* acc, int32_t n, int32_t nl, int32_t h, int32_t w, int32_t c, double* out,
+                       void* stream);
+int isa_props_select(const int64_t* acc, int32_t n, int32_t nl, int32_t h, int32_t w, int32_t min_area, int32_t max_area,
+                     int32_t clear_border, int32_t order, int32_t max_objects, uint8_t* table, int32_t* count,
+                     int32_t* dropped, void* stream);
+int isa_relabel_u8(const uint8_t* labels, const uint8_t* table, int32_t n, int64_t L, uint8_t* out, void* stream);
 /* ---- exact Euclidean distance transform to the two nearest instances; border weights and instance fill -----------------
  * Every entry checks all its arguments before it launches or writes anything (ISA_EINVAL / ISA_EALIGN / ISA_ENOMEM), is
  * asynchronous on `stream`, allocates nothing and never reads anything back: the launch count depends on the shape alone,

@@ -43,7 +43,9 @@ def cc_select_scratch_bytes(n, h, w):
     return n * (h * w * 4 + CC_TAB_BYTES)
 
 
-EDT_MAX_SIDE, EDT_COL_LANES, EDT_ROW_LANES = 4096, 64, 256      # ISA_EDT_MAX_SIDE, ISA_EDT_COL_LANES, ISA_EDT_ROW_LANES
+PROPS_ACC, PROPS_OUT, PROPS_MAX_SIDE = 16, 24, 32768      # ISA_PROPS_ACC, ISA_PROPS_OUT, ISA_PROPS_MAX_SIDE
+ORDER_LABEL, ORDER_AREA, ORDER_RASTER = 0, 1, 2
+EDT_MAX_SIDE, EDT_COL_LANES, EDT_ROW_LANES = 4096, 64, 256     # ISA_EDT_MAX_SIDE, ISA_EDT_COL_LANES, ISA_EDT_ROW_LANES
 
 
 def edt_scratch_bytes(n, h, w):
@@ -268,6 +270,11 @@ SIGNATURES = {
     # connected components and instance clean-up (ReSeg.components, split_components, clean_instances)
     "isa_cc_label": [VP, I32, I32, I32, I32, VP, VP, VP, I64, VP],
     "isa_cc_select": [VP, VP, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, I64, VP],
+    # measuring instances (ReSeg.instance_properties, select_instances)
+    "isa_label_props": [VP, VP, I32, I32, I32, I32, I32, VP, VP, VP],
+    "isa_instance_props": [VP, I32, I32, I32, I32, I32, VP, VP],
+    "isa_props_select": [VP, I32, I32, I32, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP],
+    "isa_relabel_u8": [VP, VP, I32, I64, VP, VP],
     # distance transform to the two nearest instances (ReSeg.distance_transform, border_weights, fill_instances)
     "isa_edt2_u8": [VP, I32, I32, I32, VP, VP, VP, VP, I64, VP],
     "isa_border_weights": [VP, VP, VP, VP, I32, I64, VP, VP],

@@ -129,11 +129,12 @@ class Model(object):
         return sem_arg, labels, count
 
     def __score_batch(self, batch, max_objects, check, clean=None, method='attention', bandwidth=None, fill=False,
-                      fill_max_dist=None):
+                      fill_max_dist=None, select=None):
         """segment() + score_instances() of one loader batch: the device tensor [B,8], and the number of pixels whose
         label the histograms do not hold (a device scalar: the callers read it with their one copy and raise).
         clean: keyword arguments of ReSeg.clean_instances, applied to the labels before they are scored; fill: then the
-        unlabelled foreground of the predicted class map goes to the nearest instance (ReSeg.fill_instances)."""
+        unlabelled foreground of the predicted class map goes to the nearest instance (ReSeg.fill_instances); select: then
+        keyword arguments of ReSeg.select_instances."""
         images, sem, ins, n_objects = batch
         m = self.model
         sem_arg, labels, count = self.__instances(images, max_objects, method, bandwidth, n_objects)
@@ -141,6 +142,8 @@ class Model(object):
             labels, count, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         if fill:
             labels, _ = m.fill_instances(labels, m.class_map(), fill_max_dist)
+        if select is not None:
+            labels, count, _ = m.select_instances(labels, max_objects=max_objects, **select)
         out = m.score_instances(labels, count, ins, n_objects, sem_arg, sem, max_objects=max_objects, check=check)
         return out, m.last_score_oob.sum()
 
@@ -313,8 +316,20 @@ class Model(object):
             return None
         return {'keep': keep or 'all', 'connectivity': connectivity, 'min_area': int(min_area)}
 
+    @staticmethod
+    def __select_arguments(order, clear_border, max_area):
+        """None when the defaults ask for no selection (then nothing of it runs), else ReSeg.select_instances' keywords."""
+        if order not in (None, 'label', 'area', 'raster'):
+            raise ValueError("order must be None, 'label', 'area' or 'raster', got %r" % (order,))
+        if max_area is not None and int(max_area) < 1:
+            raise ValueError("max_area must be positive or None, got %r" % (max_area,))
+        if order is None and not clear_border and max_area is None:
+            return None
+        return {'order': order or 'label', 'clear_border': bool(clear_border), 'max_area': max_area}
+
     def predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
-                          bandwidth=None, n_objects=None, fill=False, fill_max_dist=None):
+                          bandwidth=None, n_objects=None, fill=False, fill_max_dist=None, order=None, clear_border=False,
+                          max_area=None):
         """Instance inference for models built with use_instance_segmentation=True (ReSeg.segment; the reference's own
         instance prediction is dead at HEAD).  images: [b,21,h,w] float or raw uint8 RGB [b,h,w,3].  Returns host tensors
         (fg_prob [b,h,w] = softmax probability of the foreground class, labels uint8 [b,h,w] with 0 = no instance,
@@ -326,12 +341,27 @@ class Model(object):
         decoder (ReSeg.segment_embedding, at most 32 per image): mean-shift of radius bandwidth (default 1.5 = delta_dist),
         or k-means with the object counts n_objects [b].
         fill=True gives, after the clean-up, every foreground pixel of the predicted class map that is still 0 to the nearest
-        instance (ReSeg.fill_instances), within fill_max_dist pixels when that is given.  Off by default."""
+        instance (ReSeg.fill_instances), within fill_max_dist pixels when that is given.  Off by default.
+        order='label' | 'area' | 'raster', clear_border=True and / or max_area then filter and renumber the instances by
+        their measurements (ReSeg.select_instances, after the clean-up and the fill): instances that touch the image edge or
+        exceed max_area pixels are dropped, and the rest are numbered by old label, largest first, or by first pixel.  Off
+        by default."""
+        fg_prob, labels, n_objects = self.__predict_instances(
+            images, max_objects, min_area=min_area, keep=keep, connectivity=connectivity, method=method, bandwidth=bandwidth,
+            n_objects=n_objects, fill=fill, fill_max_dist=fill_max_dist, order=order, clear_border=clear_border,
+            max_area=max_area)
+        return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
+
+    def __predict_instances(self, images, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
+                            bandwidth=None, n_objects=None, fill=False, fill_max_dist=None, order=None, clear_border=False,
+                            max_area=None):
+        """predict_instances' answer as device tensors."""
         assert len(images.size()) == 4
         m = self.model
         if not m.use_instance_seg:
             raise RuntimeError("predict_instances() needs a model built with use_instance_segmentation=True")
         clean = self.__clean_arguments(min_area, keep, connectivity)
+        select = self.__select_arguments(order, clear_border, max_area)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
         _, labels, n_objects = self.__instances(images, max_objects, method, bandwidth, n_objects)
@@ -339,8 +369,22 @@ class Model(object):
             labels, n_objects, _ = m.clean_instances(labels, max_objects=max_objects, **clean)
         if fill:
             labels, _ = m.fill_instances(labels, m.class_map(), fill_max_dist)
-        fg_prob = m.net.softmax_nchw(m._last_sem)[:, 1]
-        return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
+        if select is not None:
+            labels, n_objects, _ = m.select_instances(labels, max_objects=max_objects, **select)
+        return m.net.softmax_nchw(m._last_sem)[:, 1], labels, n_objects
+
+    def measure_instances(self, images, **predict_kwargs):
+        """predict_instances(images, **predict_kwargs) and the measurements of what it found: (fg_prob, labels, n_objects,
+        props), props a list with one float64 ndarray [n_objects[b], 24] per image whose row k describes instance k + 1 in
+        the columns reseg.PROPS_COLUMNS (ReSeg.instance_properties, taken on the device at model resolution; the colour
+        means are those of raw uint8 RGB input and NaN for any other input)."""
+        m = self.model
+        fg_prob, labels, n_objects = self.__predict_instances(images, **predict_kwargs)
+        raw = images if images.dtype == torch.uint8 and tuple(images.shape) == tuple(labels.shape) + (3,) else None
+        props = m.instance_properties(labels, raw).cpu().numpy()
+        counts = n_objects.cpu()
+        rows = [props[b, 1:1 + int(counts[b])] for b in range(props.shape[0])]
+        return fg_prob.cpu(), labels.cpu(), counts, rows
 
     def predict_components(self, images, *, min_area=1, connectivity=8, max_objects=None):
         """The count-the-blobs baseline, for any model (no instance head is run): the connected components of the predicted
@@ -361,7 +405,7 @@ class Model(object):
         return fg_prob.cpu(), labels.cpu(), n_objects.cpu()
 
     def evaluate(self, loader, max_objects=None, *, min_area=0, keep=None, connectivity=8, method='attention',
-                 bandwidth=None, fill=False, fill_max_dist=None):
+                 bandwidth=None, fill=False, fill_max_dist=None, order=None, clear_border=False, max_area=None):
         """Scores of ground-truth-free instance inference over a loader of (images, sem, ins, n_objects) batches, either
         target form: every batch is segmented (ReSeg.segment, at most max_objects instances per image; default: the
         constructor's max_n_objects) and scored on the device (ReSeg.score_instances); one device-to-host copy at the end.
@@ -370,6 +414,7 @@ class Model(object):
         averages the images it scored), n_skipped counts the images whose SBD is NaN (neither map holds an object).
         min_area / keep / connectivity: the clean-up of predict_instances, applied to every label map before it is scored
         (with the defaults none of it runs).  fill / fill_max_dist: predict_instances' fill, after the clean-up.
+        order / clear_border / max_area: predict_instances' selection by measurement, after both (off by default).
         method='meanshift' | 'kmeans': the instances come from clusters of the instance embedding (predict_instances);
         'kmeans' is given every batch's ground-truth object counts - the reference's protocol, a count supplied.
         It scores what the loader yields on THIS rank; reducing over ranks is left to the caller."""
@@ -377,10 +422,11 @@ class Model(object):
         if not m.use_instance_seg:
             raise RuntimeError("evaluate() needs a model built with use_instance_segmentation=True")
         clean = self.__clean_arguments(min_area, keep, connectivity)
+        select = self.__select_arguments(order, clear_border, max_area)
         m.eval()
         max_objects = self.max_n_objects if max_objects is None else max_objects
         rows = [self.__score_batch(b, max_objects, check=False, clean=clean, method=method, bandwidth=bandwidth, fill=fill,
-                                   fill_max_dist=fill_max_dist) for b in loader]
+                                   fill_max_dist=fill_max_dist, select=select) for b in loader]
         if not rows:
             nan = float('nan')
             return {'SBD': nan, '|DiC|': nan, 'FG Dice': nan, 'n_images': 0, 'n_skipped': 0,

@@ -577,6 +577,53 @@ class Network:
                             scratch.numel(), E.st())
         return out, count, dropped
 
+    def label_props(self, labels: torch.Tensor, image: torch.Tensor = None, n_labels=256):
+        """(acc int64 [n,n_labels,16], oob int32 [n]) of a uint8 label map [n,h,w] and an optional uint8 image [n,h,w,c]
+        (isa_label_props): area, box, raw moments, crack perimeter, first pixel and channel sums per label.  New tensors."""
+        E = self.E
+        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
+        n, h, w = labels.shape
+        c = 0
+        if image is not None:
+            assert image.dtype == torch.uint8 and image.dim() == 4 and image.is_contiguous() and \
+                tuple(image.shape[:3]) == (n, h, w), "image: contiguous uint8 [n,h,w,c]"
+            c = image.shape[3]
+        acc = torch.empty((n, n_labels, L.PROPS_ACC), dtype=torch.int64, device=labels.device)
+        oob = torch.empty((n,), dtype=torch.int32, device=labels.device)
+        E.lib.isa_label_props(labels, image, n, h, w, c, int(n_labels), acc, oob, E.st())
+        return acc, oob
+
+    def instance_props(self, acc: torch.Tensor, h, w, c=0) -> torch.Tensor:
+        """double [n,n_labels,24] of label_props' accumulators (isa_instance_props).  A new tensor."""
+        E = self.E
+        n, nl = acc.shape[0], acc.shape[1]
+        out = torch.empty((n, nl, L.PROPS_OUT), dtype=torch.float64, device=acc.device)
+        E.lib.isa_instance_props(acc, n, nl, int(h), int(w), int(c), out, E.st())
+        return out
+
+    def props_select(self, acc: torch.Tensor, h, w, min_area=1, max_area=0, clear_border=False, order=L.ORDER_LABEL,
+                     max_objects=255):
+        """(table uint8 [n,256], count int32 [n], dropped int32 [n]) from label_props' accumulators (isa_props_select):
+        the new label of every old one after filtering by area and border contact and ranking by `order`.  New tensors."""
+        E = self.E
+        n, nl = acc.shape[0], acc.shape[1]
+        table = torch.empty((n, 256), dtype=torch.uint8, device=acc.device)
+        count = torch.empty((n,), dtype=torch.int32, device=acc.device)
+        dropped = torch.empty((n,), dtype=torch.int32, device=acc.device)
+        E.lib.isa_props_select(acc, n, nl, int(h), int(w), int(min_area), int(max_area), int(bool(clear_border)), int(order),
+                               int(max_objects), table, count, dropped, E.st())
+        return table, count, dropped
+
+    def relabel(self, labels: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """table[i][labels[i]] of a uint8 map [n,...] (isa_relabel_u8); out may be labels itself.  A new tensor without out."""
+        E = self.E
+        assert labels.dtype == torch.uint8 and labels.is_contiguous() and table.dtype == torch.uint8 and table.is_contiguous()
+        n = labels.shape[0]
+        assert tuple(table.shape) == (n, 256)
+        out = torch.empty_like(labels) if out is None else out
+        E.lib.isa_relabel_u8(labels, table, n, labels.numel() // n, out, E.st())
+        return out
+
     # ------------------------------------------------------------------ boundary
     def to_nhwc(self, x: torch.Tensor, c_pad=None) -> Act:
         """NCHW fp32 (reference layout) -> NHWC activation view."""

@@ -15,6 +15,11 @@ from .network import Network
 from .instance_head import InstanceHead
 from .schema import state_dict_schema
 
+# the columns of ReSeg.instance_properties (isa_instance_props, include/isa_kernels.h)
+PROPS_COLUMNS = ("area", "x0", "y0", "x1", "y1", "centroid_x", "centroid_y", "mu_xx", "mu_yy", "mu_xy", "major_axis",
+                 "minor_axis", "eccentricity", "orientation", "perimeter", "touches_border", "extent", "equivalent_diameter",
+                 "compactness", "first_pixel", "mean_c0", "mean_c1", "mean_c2", "mean_c3")
+
 
 class _Node(nn.Module):
     """Anonymous container reproducing the reference's module tree for state_dict naming."""
@@ -556,6 +561,74 @@ class ReSeg(nn.Module):
             t = self._cc_map(labels, connectivity, min_area, max_objects)
             comp, _ = self.net.cc_label(t, connectivity)
             return self.net.cc_select(t, comp, L.CC_LARGEST if keep == 'largest' else L.CC_SPLIT, min_area, max_objects)
+
+    # ------------------------------------------------------------------ measuring instances, filtering and ordering by them
+    def _props_map(self, labels):
+        t = labels.to(self.store.device).contiguous()
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise TypeError("expects a uint8 label map [B,H,W], got %s %s" % (t.dtype, tuple(t.shape)))
+        n, h, w = t.shape
+        if (h * w) % 4 or max(h, w) > L.PROPS_MAX_SIDE or not 1 <= n <= 65535 or min(h, w) < 1:
+            raise ValueError("labels [B,H,W]: H*W a multiple of 4, H and W at most %d, 1 <= B <= 65535; got %s"
+                             % (L.PROPS_MAX_SIDE, tuple(t.shape)))
+        return t
+
+    def instance_properties(self, labels, image=None, *, n_labels=256, check=True):
+        """Measurements of every instance of a uint8 label map [B,H,W] (segment's, clean_instances', ...), on the device: a
+        double tensor [B, n_labels, 24] whose row v describes label v of the image and whose columns are PROPS_COLUMNS:
+        area; the half-open box x0, y0, x1, y1; the centroid; the central second moments per pixel mu_xx, mu_yy, mu_xy; major
+        and minor axis length 4 sqrt(lambda); eccentricity; orientation (the angle of the major axis from the x axis in
+        (-pi/2, pi/2], y pointing down: the project's own convention); perimeter as crack length (pixel edges between the
+        label and anything else, the image edge and holes included); touches_border; extent; equivalent diameter;
+        compactness 4 pi A / P^2; the first pixel's row-major index; the mean of up to four image channels.
+        x is the column, y the row.  A label that is absent (label 0 always: background is not measured) has area 0 and NaN
+        elsewhere.  image: uint8 [B,H,W,C], C in 1, 3, 4 - such as the raw RGB batch forward() accepts - or None (NaN means).
+        Labels >= n_labels are not measured: with check=True (one device read, the only host synchronisation) they raise
+        ValueError; with check=False nothing is read back and the counts stay in self.last_props_oob (int32 [B]).
+        isa_label_props + isa_instance_props; DESIGN.md section 20."""
+        with torch.no_grad():
+            t = self._props_map(labels)
+            if not 1 <= int(n_labels) <= 256:
+                raise ValueError("n_labels must be in 1..256, got %r" % (n_labels,))
+            img = None
+            if image is not None:
+                img = image.to(self.store.device).contiguous()
+                if img.dtype != torch.uint8 or img.dim() != 4 or tuple(img.shape[:3]) != tuple(t.shape) or \
+                        img.shape[3] not in (1, 3, 4):
+                    raise TypeError("image: uint8 %s + (C,), C in 1, 3, 4; got %s %s"
+                                    % (tuple(t.shape), img.dtype, tuple(img.shape)))
+            acc, oob = self.net.label_props(t, img, int(n_labels))
+            out = self.net.instance_props(acc, t.shape[1], t.shape[2], 0 if img is None else img.shape[3])
+            self.last_props_oob = oob
+            if check:
+                bad = oob.cpu()
+                if int(bad.sum()):
+                    raise ValueError("instance_properties: %d pixels of images %s carry a label >= n_labels = %d"
+                                     % (int(bad.sum()), torch.nonzero(bad).view(-1).tolist(), int(n_labels)))
+            return out
+
+    def select_instances(self, labels, *, min_area=1, max_area=None, clear_border=False, order='label', max_objects=255):
+        """Filters and renumbers the instances of a uint8 label map [B,H,W] by their measurements, on the device; returns
+        (labels, n_objects, dropped) as clean_instances does, ready for score_instances.  An instance stays when it has
+        min_area <= area <= max_area (None: no upper limit) pixels and, with clear_border, its box touches no image edge
+        (a truncated leaf).  Those that stay are numbered 1, 2, .. by order: 'label' (the old labels ascending), 'area'
+        (largest first, equal areas by the smaller old label) or 'raster' (by first pixel); past max_objects (1..255) an
+        instance gets no label.  dropped counts the instances of the input that ended without one.  Nothing is read back.
+        isa_label_props + isa_props_select + isa_relabel_u8."""
+        orders = {'label': L.ORDER_LABEL, 'area': L.ORDER_AREA, 'raster': L.ORDER_RASTER}
+        if order not in orders:
+            raise ValueError("order must be 'label', 'area' or 'raster', got %r" % (order,))
+        if not 1 <= int(max_objects) <= 255:
+            raise ValueError("max_objects must be in 1..255 (labels are uint8), got %d" % max_objects)
+        if int(min_area) < 0 or (max_area is not None and int(max_area) < 1):
+            raise ValueError("min_area must not be negative and max_area must be positive or None, got %r, %r"
+                             % (min_area, max_area))
+        with torch.no_grad():
+            t = self._props_map(labels)
+            acc, _ = self.net.label_props(t, None, 256)
+            table, count, dropped = self.net.props_select(acc, t.shape[1], t.shape[2], int(min_area), int(max_area or 0),
+                                                          clear_border, orders[order], int(max_objects))
+            return self.net.relabel(t, table), count, dropped
 
     # ------------------------------------------------------------------ distance transform, border weights, instance fill
     def _edt_map(self, labels):

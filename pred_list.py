@@ -24,6 +24,11 @@ components of the predicted class map (ReSeg.split_components; `--min-area`, `--
 written as <name>-ins_mask.png, <name>-ins_mask_color.png and <name>-n_objects.npy - the count-the-blobs baseline.
 `--fill` gives, after that clean-up, every foreground pixel of the predicted class map that no instance holds to the
 nearest instance (ReSeg.fill_instances, on the device); `--fill-max-dist D` only within D pixels.
+`--order label|area|raster`, `--clear-border` and `--max-area N` then filter and renumber the instances of `--instances` or
+`--components` by their measurements (ReSeg.select_instances: largest first, truncated objects dropped); `--properties`
+measures what is left on the device (ReSeg.instance_properties) and writes <name>-instances.csv - one row per instance in
+the columns reseg.PROPS_COLUMNS, taken at model resolution, followed by model_w, model_h, orig_w, orig_h so that a caller
+can rescale - and <name>-ins_mask_model.png, the label map at model resolution that the rows describe.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -92,6 +97,7 @@ def parse_args(argv=None):
     add_cleanup_arguments(parser)
     add_embedding_arguments(parser)
     add_fill_arguments(parser)
+    add_measure_arguments(parser)
     opt = parser.parse_args(argv)
     if not 2 <= opt.n_classes <= 32:
         parser.error('--n-classes must be in [2, 32]')
@@ -100,6 +106,7 @@ def parse_args(argv=None):
     check_cleanup_arguments(parser, opt)
     check_embedding_arguments(parser, opt)
     check_fill_arguments(parser, opt)
+    check_measure_arguments(parser, opt)
     return opt
 
 
@@ -179,6 +186,57 @@ def clean_and_fill(net, labels, counts, clean, fill):
     return labels, counts
 
 
+def add_measure_arguments(parser):
+    parser.add_argument('--properties', action='store_true', help='with --instances or --components: measure every instance '
+                        'on the device (ReSeg.instance_properties) and write <name>-instances.csv, one row per instance, '
+                        'and <name>-ins_mask_model.png, the label map at model resolution that the rows describe')
+    parser.add_argument('--order', choices=['label', 'area', 'raster'], default=None, help='with --instances or '
+                        '--components: renumber the instances by old label, largest first, or by first pixel')
+    parser.add_argument('--clear-border', action='store_true', help='with --instances or --components: drop the instances '
+                        'that touch the image edge')
+    parser.add_argument('--max-area', type=int, default=None, help='with --instances or --components: drop the instances '
+                        'of more than N pixels (at model resolution)')
+
+
+def check_measure_arguments(parser, opt):
+    if (opt.properties or opt.order or opt.clear_border or opt.max_area is not None) and not (opt.instances or opt.components):
+        parser.error('--properties, --order, --clear-border and --max-area need --instances or --components')
+    if opt.max_area is not None and opt.max_area < 1:
+        parser.error('--max-area must be positive')
+
+
+def select_arguments(opt):
+    """ReSeg.select_instances' keywords for the label maps, or None when the flags ask for no selection."""
+    if opt.order is None and not opt.clear_border and opt.max_area is None:
+        return None
+    return {'order': opt.order or 'label', 'clear_border': opt.clear_border, 'max_area': opt.max_area,
+            'max_objects': opt.max_objects}
+
+
+def select_and_measure(net, labels, counts, x, select, properties):
+    """The label maps after the selection by measurement (ReSeg.select_instances' keywords, or None), and with `properties`
+    the measurements of what is left (ReSeg.instance_properties with the colour means of the uint8 RGB batch x), else
+    None: at model resolution, on the device."""
+    if select is not None:
+        labels, counts, _ = net.select_instances(labels, **select)
+    return labels, counts, (net.instance_properties(labels, x) if properties else None)
+
+
+def write_properties(d, name, labels, props, n_objects, out_h, out_w):
+    """<name>-instances.csv: the columns reseg.PROPS_COLUMNS of instances 1..n_objects (row k: label k), measured at model
+    resolution, then both sizes so that a caller can rescale; <name>-ins_mask_model.png: the uint8 label map [h,w] the
+    rows describe."""
+    from PIL import Image
+    from isa_amd.reseg import PROPS_COLUMNS
+    h, w = labels.shape
+    sizes = ['%d' % v for v in (w, h, out_w, out_h)]
+    with open(os.path.join(d, name + '-instances.csv'), 'w') as f:
+        f.write(','.join(PROPS_COLUMNS + ('model_w', 'model_h', 'orig_w', 'orig_h')) + '\n')
+        for k in range(1, int(n_objects) + 1):
+            f.write(','.join([repr(float(v)) for v in props[k]] + sizes) + '\n')
+    Image.fromarray(labels).save(os.path.join(d, name + '-ins_mask_model.png'))
+
+
 def cleanup_arguments(opt):
     """ReSeg.clean_instances' keywords for the --instances label maps, or None when the flags ask for no clean-up."""
     if opt.keep is None and opt.min_area <= 1:
@@ -218,7 +276,8 @@ def main():
         imgs = [ld() for ld in loaders[s:s + opt.batch]]
         # resize on the device (isa_resize_bilinear_u8, bit-identical to PIL's BILINEAR): one launch per source size
         x = torch.cat([resize_bilinear(torch.from_numpy(im[None]), (H, W)) for im in imgs])   # uint8 [B,H,W,3]; ImageEx follows
-        labels = counts = classes = None
+        labels = counts = classes = props = None
+        select = select_arguments(opt)
         if opt.n_classes > 2:
             with torch.no_grad():
                 net(False, x)
@@ -227,23 +286,27 @@ def main():
             if opt.components:
                 labels, counts, _ = net.split_components(classes, connectivity=opt.connectivity, min_area=opt.min_area,
                                                          max_objects=opt.max_objects)
+                labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
                 labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
             classes = classes.cpu().numpy()
         elif opt.instances:
             sem_arg, labels, counts = segment_instances(net, x, opt)
             # at model resolution, before the nearest up-sampling
             labels, counts = clean_and_fill(net, labels, counts, cleanup_arguments(opt), fill_arguments(opt))
+            labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         elif opt.components:
             with torch.no_grad():
                 _, sem_arg = net(False, x)
                 labels, counts, _ = net.split_components(net.class_map(), connectivity=opt.connectivity,
                                                          min_area=opt.min_area, max_objects=opt.max_objects)
+                labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         else:
             _, sem_arg = net.infer_graphed(x) if len(imgs) == opt.batch else net(False, x)
         # softmax(l)[1] > 0.5 (pred.py:117-121) is l1 > l0: the arg-max map the library already returns
         fg = (sem_arg[:, 0] > 0.5).to(torch.uint8).cpu().numpy()
+        props = None if props is None else props.cpu().numpy()
         for i, (im, name, m) in enumerate(zip(imgs, names[s:s + opt.batch], fg)):
             d = os.path.join(out_dir, name)
             os.makedirs(d, exist_ok=True)
@@ -252,6 +315,8 @@ def main():
             Image.fromarray(full.astype(np.uint8)).save(os.path.join(d, name + '-fg_mask.png'))
             if labels is not None:
                 write_instances(d, name, labels[i], counts[i], im.shape[0], im.shape[1])
+            if props is not None:
+                write_properties(d, name, labels[i], props[i], counts[i], im.shape[0], im.shape[1])
             if classes is not None:
                 write_classes(d, name, classes[i], im.shape[0], im.shape[1])
             done += 1
