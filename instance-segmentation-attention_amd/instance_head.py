@@ -13,6 +13,7 @@ What changes vs. the reference's control flow (same results, MI355X-first):
   * concat order inside the decoder is [gated_up | cross | mask_all | position] so every slice
     starts 16-byte aligned; conv1's weight columns are permuted to match when packed.
 """
+import collections
 import math
 import os
 
@@ -32,14 +33,21 @@ DROP_RATE = 0.5                             # config.py:64
 ROW_PART = 64 * 4                           # floats of chunk partials per softmax row (ISA_ROW_CHUNKS * 4, isa_kernels.h)
 SEG_PART = 64 * 2                           # floats of chunk candidates per row of isa_seg_begin / isa_seg_claim
 
+# One decoder pass: iterations [it0, it0 + G) as G*n images with G BatchNorm statistic groups; the cross branches run on
+# stream sc, the level chain on stream sm; defer: its running-statistics updates wait for Engine.flush_bn_running().
+Pass = collections.namedtuple("Pass", "it0 G sc sm defer")
+# What a pass computes ahead of its levels, one row per (iteration, image): see InstanceHead.front.
+Front = collections.namedtuple("Front", "idx alpha s_t targets sums_all")
+
 
 class InstanceHead:
     def __init__(self, net):
         self.net = net
         self.E: Engine = net.E
         self.drop_rate = DROP_RATE
-        # concurrent HIP streams for the pyramid passes: 1 = none, 2 = odd iterations on a side stream, 3 = cross
-        # chains on the step's stream + one side stream per iteration's level chain (see forward)
+        # The two flags choose the decoder's pass list (see passes); one driver runs whatever they choose.
+        # concurrent HIP streams for the pyramid passes: 1 = none, 2 = odd iterations (the batched pass: its cross chain)
+        # on a side stream, 3 = cross chains on the step's stream + one side stream per iteration's level chain
         self.streams = int(os.environ.get("ISA_STREAMS", "2"))
         # all decoder iterations of a train-mode pass as ONE batch of max_iter * B images with a BatchNorm statistic group
         # per iteration (attenet2.py:384-399 runs them one after the other through the same weights): half the launches,
@@ -154,66 +162,109 @@ class InstanceHead:
         return merge
 
     # ------------------------------------------------------------------ pyramid decoder
-    def _draw_masks(self, n, max_iter, training):
-        """All Dropout2d masks of a step from ONE torch.rand draw (3 per level and iteration: utils.py:869-892).
-        Per-mask draws were ~120 five-microsecond launches per step."""
-        self._mask_pool, self._mask_cursor = None, 0
-        if self.drop_rate <= 0 or not (training or self.E.bn_train) or self.injected_masks is not None:
-            return
-        total = max_iter * sum(3 * n * oc for oc in OUT_CH)
-        keep = 1.0 - self.drop_rate
-        u = torch.rand(total, device=self.E.device)          # torch supplies the random numbers (graph-safe generator)
-        self._mask_pool = torch.empty_like(u)
-        self.E.lib.isa_dropout_mask(u, total, keep, self._mask_pool, self.E.st())
+    def passes(self, max_iter):
+        """The decoder passes of a step that runs max_iter iterations.  The iterations share weights and backbone
+        features but not data (attenet2.py:384-399 runs them one after the other), and inside an iteration the cross
+        branch of every level only reads the backbone.  Most of these launches are too small to fill 256 CUs (16x16 ...
+        64x64 maps), so independent chains run on separate HIP streams.
+        Train-mode BatchNorm, 2..4 iterations (batch_iters): ONE pass over max_iter * n images, rows ordered
+        [iteration][image].  BatchNorm statistics stay per iteration (isa_tensor.groups = G), running statistics take the
+        G updates in iteration order inside isa_bn_finalize, the REINFORCE baseline EMA runs in iteration order inside
+        isa_head_loss.  The cross chain runs beside the level chain on side stream 1 (streams >= 2), one edge per level.
+        Otherwise one pass per iteration.  streams == 2 (default): odd iterations run whole on side stream 1, one fork
+        and one join per pass (34.3 -> 30.0 ms/step at the BASELINE shape under hipGraph replay).  streams == 3: the
+        cross chains of all iterations stay on the step's own stream, the level chain of iteration i runs on side stream
+        1 + i % 2, one edge per level; measured slower (31.9 ms: every extra cross-stream edge costs more than the finer
+        overlap returns; cross chains on their own side streams 32.4 - 33.9 ms).  Every edge has the origin stream at
+        one end: hipGraph capture of side -> side edges crashes inside ROCm 7.2's hipStreamEndCapture
+        (scripts/graph_probe.py).
+        What the sequential order guaranteed is restored explicitly: a BatchNorm layer must see iteration 0's update
+        first, so only iteration 0's in-launch update is kept when iterations can overlap and later ones are queued
+        (Pass.defer) for flush_bn_running() after the join, in iteration order (isa_bn_running_update); gradients of
+        backbone features read from a side stream are accumulated per stream and merged (GradBook.merge_shared); loss
+        assembly stays on the origin stream."""
+        if self.batch_iters and self.E.bn_train and 2 <= max_iter <= 4:
+            return [Pass(0, max_iter, 1 if self.streams >= 2 else 0, 0, False)]
+        ns = self.streams if max_iter >= 2 else 1
+        assert ns in (1, 2, 3), "ISA_STREAMS must be 1, 2 or 3"
+        sc_sm = {1: lambda it: (0, 0), 2: lambda it: (it % 2, it % 2), 3: lambda it: (0, 1 + it % 2)}[ns]
+        return [Pass(it, 1, *sc_sm(it), self.E.bn_train and it >= 1 and ns > 1) for it in range(max_iter)]
 
-    def _masks_batched(self, n, G, training):
-        """Dropout2d masks of a pass that batches the G iterations: per level {cross, d1, d2} as [G*n, C] arrays
-        ([iteration][image] rows, the order the batched tensors use).  Inactive d1 / d2 masks are absent; an inactive
-        cross mask is all ones (the broadcast materialising pass always takes a per-image scale)."""
+    def fg_pyramid(self, sem_map, nobj, n, H, W):
+        """mask_all: the foreground map at the five pyramid sizes (sem_map itself at full size)."""
         E = self.E
-        keep = 1.0 - self.drop_rate
-        act_cross = self.drop_rate > 0 and E.bn_train
-        act_d = self.drop_rate > 0 and training
-        inj = self.injected_masks
         out = []
+        for f in FACTORS[:-1]:
+            m = E.f32(n * (H // f) * (W // f))
+            E.lib.isa_pool_target(None, None, sem_map, nobj, n, H, W, f, m, n, E.st())
+            out.append(m)
+        return out + [sem_map]
+
+    def front(self, p, merge, ins, idx_dev, injected_s_t, training, n, H, W):
+        """What a pass needs before its first level, for its G*n rows: instance softmax, glimpse point, the five pyramid
+        targets, and the zeroed sums isa_head_loss reads ([level][iteration][image][8])."""
+        E = self.E
+        Lp, R, nobj = H * W, p.G * n, ins.shape[1]
+        idx = idx_dev[p.it0:p.it0 + p.G].reshape(-1).contiguous()          # [G*n] instance order
+        alpha, rowstat = E.f32(R * Lp), E.f32(2 * R)
+        E.lib.isa_ins_softmax(merge, ins, idx, R, nobj, Lp, alpha, rowstat, n, E.f32(R * ROW_PART), E.st())
+        if injected_s_t is None:
+            # attenet2.py:304-321 `sample`: training draws s_t ~ Multinomial(alpha), eval takes the argmax.
+            # The draw is argmax(alpha / Exp(1)) (the exponential-race form torch.multinomial itself uses
+            # for one sample); torch supplies the random numbers (graph-safe generator), the row argmax is ours.
+            race = None
+            if training and self.sample_in_training:
+                race = torch.empty(R, Lp, dtype=torch.float32, device=alpha.device).exponential_(1.0)
+            s_t = E.arena.alloc((R,), torch.int32)
+            E.lib.isa_row_argmax(alpha, race, R, Lp, s_t, E.st())
+        elif p.G == 1:
+            s_t = injected_s_t[p.it0]
+        else:
+            s_t = E.arena.alloc((R,), torch.int32)
+            for g in range(p.G):
+                s_t[g * n:(g + 1) * n].copy_(injected_s_t[p.it0 + g])
+        targets = []
+        for f in FACTORS:
+            t = E.f32(R * (H // f) * (W // f))
+            E.lib.isa_pool_target(ins, idx, None, nobj, R, H, W, f, t, n, E.st())
+            targets.append(t)
+        return Front(idx, alpha, s_t, targets, E.scratch(5 * 8 * R))
+
+    def drop_masks(self, passes, n, training):
+        """All Dropout2d masks of a step (utils.py:869-892: three per level and iteration) from ONE torch.rand draw and one
+        launch - per-mask draws were ~120 five-microsecond launches per step.  Returns [pass][level] {cross, d1, d2} of
+        [G*n, C] arrays ([iteration][image] rows), taken from the draw in the order pass, level, kind.  Only the active
+        kinds are drawn (cross: train-mode BatchNorm, the module's own nn.Dropout2d; d1 / d2: training); an inactive mask
+        is absent, but a pass with G > 1 gets all ones for cross: its broadcast materialising pass always takes a
+        per-image scale.  injected_masks replaces the draw."""
+        E, inj = self.E, self.injected_masks
+        kinds = [k for k, on in (("cross", E.bn_train), ("d1", training), ("d2", training)) if on and self.drop_rate > 0]
+        total = sum(len(kinds) * p.G * n * oc for p in passes for oc in OUT_CH)
         pool, cur = None, 0
-        if inj is None and (act_cross or act_d):
-            total = sum((int(act_cross) + 2 * int(act_d)) * G * n * oc for oc in OUT_CH)
-            u = torch.rand(total, device=E.device)
+        if inj is None and total:
+            u = torch.rand(total, device=E.device)           # torch supplies the random numbers (graph-safe generator)
             pool = torch.empty_like(u)
-            E.lib.isa_dropout_mask(u, total, keep, pool, E.st())
-
-        def take(lvl, kind, oc):
-            nonlocal cur
-            if inj is not None:
-                return torch.cat([inj[it, lvl, kind].to(E.device, torch.float32).reshape(n, oc) for it in range(G)]).contiguous()
-            m = pool[cur:cur + G * n * oc].view(G * n, oc)
-            cur += G * n * oc
-            return m
-
-        for lvl, oc in enumerate(OUT_CH):
-            masks = {}
-            if act_cross:
-                masks["cross"] = take(lvl, "cross", oc)
-            else:
-                ones = getattr(self, "_ones", None)
-                if ones is None or ones.numel() < G * n * oc:
-                    ones = self._ones = torch.ones(G * n * max(OUT_CH), device=E.device)
-                masks["cross"] = ones[:G * n * oc].view(G * n, oc)
-            if act_d:
-                masks["d1"] = take(lvl, "d1", oc)
-                masks["d2"] = take(lvl, "d2", oc)
-            out.append(masks)
+            E.lib.isa_dropout_mask(u, total, 1.0 - self.drop_rate, pool, E.st())
+        out = []
+        for p in passes:
+            R = p.G * n
+            out.append([])
+            for lvl, oc in enumerate(OUT_CH):
+                masks = {}
+                for kind in kinds:
+                    if inj is not None:
+                        masks[kind] = torch.cat([inj[p.it0 + g, lvl, kind].to(E.device, torch.float32).reshape(n, oc)
+                                                 for g in range(p.G)])
+                    else:
+                        masks[kind] = pool[cur:cur + R * oc].view(R, oc)
+                        cur += R * oc
+                if p.G > 1 and "cross" not in masks:
+                    ones = getattr(self, "_ones", None)
+                    if ones is None or ones.numel() < R * oc:
+                        ones = self._ones = torch.ones(R * max(OUT_CH), device=E.device)
+                    masks["cross"] = ones[:R * oc].view(R, oc)
+                out[-1].append(masks)
         return out
-
-    def _drop_mask(self, n, c, active, key=None):
-        if not active or self.drop_rate <= 0:
-            return None
-        if self.injected_masks is not None:
-            return self.injected_masks[key].to(self.E.device, torch.float32).reshape(n, c).contiguous()
-        m = self._mask_pool[self._mask_cursor:self._mask_cursor + n * c].view(n, c)
-        self._mask_cursor += n * c
-        return m
 
     def level_cross(self, lvl, skip: Act, masks, G=1):
         """The `cross` branch of one UpAttenLayer (utils.py:1058-1075): IR -> Dropout2d(module) -> IR on the backbone
@@ -350,14 +401,7 @@ class InstanceHead:
         merge = self.hard_attention_scores(s, sem_map)
         nmin = int(min(int(v) for v in n_ins))
         max_iter = min(MAX_ITER, nmin) if training else nmin
-        mask_all = []
-        for f in FACTORS:
-            if f == 1:
-                mask_all.append(sem_map)
-            else:
-                m = E.f32(n * (H // f) * (W // f))
-                E.lib.isa_pool_target(None, None, sem_map, nobj, n, H, W, f, m, n, E.st())
-                mask_all.append(m)
+        mask_all = self.fg_pyramid(sem_map, nobj, n, H, W)
         if idx_dev is None:          # [max_iter, n] int32 instance order; pre-staged by the graph-captured step
             idx_dev = self.order_tensor(selected_idx, max_iter, n).to(E.device)
         skips = [feats[4], feats[3], feats[2], feats[1], feats[0]]
@@ -367,184 +411,63 @@ class InstanceHead:
             self.baseline = torch.zeros(1, dtype=torch.float32, device=E.device)
         if capture is not None:
             capture.update(x_enc=x_enc, s_sp=s, merge=merge)
-        if self.batch_iters and E.bn_train and 2 <= max_iter <= 4:
-            return self._forward_batched(x_enc, merge, skips, sem_map, ins, n, H, W, nobj, max_iter, training, idx_dev,
-                                         injected_s_t, capture, mask_all, scal)
-        self._draw_masks(n, max_iter, training)
-        # ---- per-iteration front: instance softmax, glimpse point, pyramid targets (main stream) ----------------
-        pre = []
-        for it in range(max_iter):
-            idx = idx_dev[it]
-            alpha, rowstat = E.f32(n * Lp), E.f32(2 * n)
-            E.lib.isa_ins_softmax(merge, ins, idx, n, nobj, Lp, alpha, rowstat, n, E.f32(n * ROW_PART), E.st())
-            if injected_s_t is not None:
-                s_t = injected_s_t[it]
-            else:
-                # attenet2.py:304-321 `sample`: training draws s_t ~ Multinomial(alpha), eval takes the argmax.
-                # The draw is argmax(alpha / Exp(1)) (the exponential-race form torch.multinomial itself uses
-                # for one sample); torch supplies the random numbers (graph-safe generator), the row argmax is ours.
-                race = None
-                if training and self.sample_in_training:
-                    race = torch.empty(n, Lp, dtype=torch.float32, device=alpha.device).exponential_(1.0)
-                s_t = E.arena.alloc((n,), torch.int32)
-                E.lib.isa_row_argmax(alpha, race, n, Lp, s_t, E.st())
-            targets = []
-            for f in FACTORS:
-                t = E.f32(n * (H // f) * (W // f))
-                E.lib.isa_pool_target(ins, idx, None, nobj, n, H, W, f, t, n, E.st())
-                targets.append(t)
-            sums_all = E.scratch(5 * 8 * n)                 # [level][image][8], contiguous for isa_head_loss
-            pre.append((idx, alpha, s_t, targets, sums_all))
-        # ---- the pyramid passes.  The iterations share weights and backbone features but not data (attenet2.py:384-
-        # 399 runs them one after the other), and inside an iteration the cross branch of every level only reads the
-        # backbone.  Most of these launches are too small to fill 256 CUs (16x16 ... 64x64 maps), so independent
-        # chains run on separate HIP streams.  streams == 2 (default): odd iterations run whole on side stream 1, one
-        # fork and one join per pass (34.3 -> 30.0 ms/step at the BASELINE shape under hipGraph replay).  streams == 3:
-        # the cross chains of all iterations stay on the step's own stream, the level chain of iteration i runs on
-        # side stream 1 + i % 2, one edge per level; measured slower (31.9 ms: every extra cross-stream edge costs
-        # more than the finer overlap returns; cross chains on their own side streams 32.4 - 33.9 ms).  Every edge has
-        # the origin stream at one end: hipGraph capture of side -> side edges crashes inside ROCm 7.2's
-        # hipStreamEndCapture (scripts/graph_probe.py).
-        # What the sequential order guaranteed is restored explicitly: BatchNorm running statistics of work that
-        # runs beside iteration 0 are applied after the join in iteration order (isa_bn_running_update), gradients of
-        # backbone features read from a side stream are accumulated per stream and merged (GradBook.merge_shared),
-        # loss assembly stays on the origin stream.
-        nstreams = self.streams if max_iter >= 2 else 1
-        assert nstreams in (1, 2, 3), "ISA_STREAMS must be 1, 2 or 3"
-        for sk in skips:
-            E.grads.share(sk)
-        if E.record and nstreams > 1:
-            E.tape.append(lambda: E.grads.merge_shared(E))      # runs after the reversed forks have joined stream 0
-        forked = [] if nstreams == 1 else ([1] if nstreams == 2 else [1, 2][:max_iter])
-        for sid in forked:                  # all forks up front: a fork issued later would wait for iteration 0's chain
-            E.sync(0, sid)
-        masks_of = {}
-        for it in range(max_iter):          # Dropout2d masks in the reference's call order (iteration-major)
-            for lvl in range(5):
-                masks = {}
-                if self.drop_rate > 0:
-                    oc = OUT_CH[lvl]
-                    masks = dict(cross=self._drop_mask(n, oc, E.bn_train, (it, lvl, "cross")),
-                                 d1=self._drop_mask(n, oc, training, (it, lvl, "d1")),
-                                 d2=self._drop_mask(n, oc, training, (it, lvl, "d2")))
-                    masks = {k: v for k, v in masks.items() if v is not None}
-                masks_of[it, lvl] = masks
-        state = [dict(x=None, pred=None, preds=[]) for _ in range(max_iter)]
-        for lvl in range(5):                # level-major issue order: the cross chains of all iterations interleave
-            for it in range(max_iter):
-                idx, alpha, s_t, targets, sums_all = pre[it]
-                if nstreams == 3:
-                    sc, sm = 0, 1 + it % 2
-                elif nstreams == 2:
-                    sc = sm = it % 2
-                else:
-                    sc = sm = 0
-                st_ = state[it]
-                masks = masks_of[it, lvl]
-                # a BatchNorm layer must see iteration 0's update first: only iteration 0's in-launch update is kept
-                # when iterations can overlap, later ones are queued for flush_bn_running()
-                E.defer_bn_running = E.bn_train and it >= 1 and nstreams > 1
-                with E.on(sc):
-                    cat = self.level_cross(lvl, skips[lvl], masks)
-                E.sync(sc, sm)
-                with E.on(sm):
-                    x, pred = self.level_main(lvl, cat, st_["x"], st_["pred"], mask_all[lvl], s_t, W, training, masks)
-                    E.lib.isa_mask_loss_sums(pred.d(), targets[lvl], None, sums_all[lvl * 8 * n:(lvl + 1) * 8 * n], E.st())
-                st_["x"], st_["pred"] = x, pred
-                st_["preds"].append(pred)
-                if capture is not None:
-                    capture["it%d.L%d.x" % (it, lvl)] = x
-                    capture["it%d.L%d.pred" % (it, lvl)] = pred
-        E.defer_bn_running = False
-        for sid in forked:
-            E.sync(sid, 0)
-        E.flush_bn_running()
-        recs = [(state[it]["preds"], [pre[it][4][l * 8 * n:(l + 1) * 8 * n] for l in range(5)]) for it in range(max_iter)]
-        for it in range(max_iter):
-            idx, alpha, s_t, targets, sums_all = pre[it]
-            preds, sums = recs[it]
-            coef, adv = E.f32(5 * 4 * n), E.f32(n)
-            E.lib.isa_head_loss(sums_all, alpha, s_t, Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L, LAMBDA_R, 1.0 / max_iter,
-                                self.baseline, 1 if training else 0, coef, adv, scal, 1, E.st())
-            if E.record:
-                def bwd_losses(preds=preds, targets=targets, coef=coef, alpha=alpha, idx=idx, s_t=s_t, adv=adv):
-                    for lvl in range(5):
-                        acc = E.grads.claim(preds[lvl], E)
-                        E.lib.isa_mask_loss_grad(preds[lvl].d(), targets[lvl], None, coef[lvl * 4 * n:(lvl + 1) * 4 * n],
-                                                 E.grads.grad_of(preds[lvl]).d(), acc, E.st())
-                    E.lib.isa_ins_softmax_bwd(alpha, ins, idx, s_t, adv, n, nobj, Lp, self.dmerge, n, E.st())
-                E.tape.append(bwd_losses)
-            iters.append(dict(idx=idx, alpha=alpha, s_t=s_t, targets=targets, preds=preds, sums=sums))
-        return dict(iters=iters, max_iter=max_iter, merge=merge, x_enc=x_enc, scal=scal)
-
-    def _forward_batched(self, x_enc, merge, skips, sem_map, ins, n, H, W, nobj, G, training, idx_dev, injected_s_t,
-                         capture, mask_all, scal):
-        """The G decoder iterations as one pass over G*n images, rows ordered [iteration][image] (attenet2.py:384-399
-        runs them one after the other; they share weights and backbone features and do not read each other's outputs).
-        BatchNorm statistics stay per iteration (isa_tensor.groups = G), running statistics take the G updates in
-        iteration order inside isa_bn_finalize, the REINFORCE baseline EMA runs in iteration order inside isa_head_loss.
-        The cross branches (backbone features only) run beside the level chain on side stream 1 (ISA_STREAMS >= 2)."""
-        E = self.E
-        Lp, R = H * W, G * n
-        idx_flat = idx_dev.reshape(-1).contiguous()          # [G*n]
-        alpha, rowstat = E.f32(R * Lp), E.f32(2 * R)
-        E.lib.isa_ins_softmax(merge, ins, idx_flat, R, nobj, Lp, alpha, rowstat, n, E.f32(R * ROW_PART), E.st())
-        s_t = E.arena.alloc((R,), torch.int32)
-        if injected_s_t is not None:
-            for it in range(G):
-                s_t[it * n:(it + 1) * n].copy_(injected_s_t[it])
-        else:
-            race = None                                      # attenet2.py:304-321 `sample`, see the per-iteration path
-            if training and self.sample_in_training:
-                race = torch.empty(R, Lp, dtype=torch.float32, device=alpha.device).exponential_(1.0)
-            E.lib.isa_row_argmax(alpha, race, R, Lp, s_t, E.st())
-        targets = []
-        for f in FACTORS:
-            t = E.f32(R * (H // f) * (W // f))
-            E.lib.isa_pool_target(ins, idx_flat, None, nobj, R, H, W, f, t, n, E.st())
-            targets.append(t)
-        sums_all = E.scratch(5 * 8 * R)                      # [level][iteration][image][8]
-        masks = self._masks_batched(n, G, training)
-        sc = 1 if self.streams >= 2 else 0                   # the cross chain's stream
-        if sc:
+        # One driver for every configuration: the pass list is the only thing the mode decides (one batched pass, or one
+        # pass of G = 1 per iteration).  Fronts and masks on the step's stream, forks, the five levels, joins, losses.
+        passes = self.passes(max_iter)
+        fronts = [self.front(p, merge, ins, idx_dev, injected_s_t, training, n, H, W) for p in passes]
+        masks = self.drop_masks(passes, n, training)
+        side = sorted({sid for p in passes for sid in (p.sc, p.sm) if sid})
+        if side:
             for sk in skips:
                 E.grads.share(sk)
             if E.record:
-                E.tape.append(lambda: E.grads.merge_shared(E))
-            E.sync(0, sc)
-        x = pred = None
-        preds = []
-        for lvl in range(5):
-            with E.on(sc):
-                cat = self.level_cross(lvl, skips[lvl], masks[lvl], G)
-            E.sync(sc, 0)
-            x, pred = self.level_main(lvl, cat, x, pred, mask_all[lvl], s_t, W, training, masks[lvl])
-            E.lib.isa_mask_loss_sums(pred.d(), targets[lvl], None, sums_all[lvl * 8 * R:(lvl + 1) * 8 * R], E.st())
-            preds.append(pred)
-            if capture is not None:
-                for it in range(G):
-                    capture["it%d.L%d.x" % (it, lvl)] = x.images(it * n, n)
-                    capture["it%d.L%d.pred" % (it, lvl)] = pred.images(it * n, n)
-        coef, adv = E.f32(5 * 4 * R), E.f32(R)
-        E.lib.isa_head_loss(sums_all, alpha, s_t, Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L, LAMBDA_R, 1.0 / G,
-                            self.baseline, 1 if training else 0, coef, adv, scal, G, E.st())
-        if E.record:
-            def bwd_losses():
-                for lvl in range(5):
-                    acc = E.grads.claim(preds[lvl], E)
-                    E.lib.isa_mask_loss_grad(preds[lvl].d(), targets[lvl], None, coef[lvl * 4 * R:(lvl + 1) * 4 * R],
-                                             E.grads.grad_of(preds[lvl]).d(), acc, E.st())
-                E.lib.isa_ins_softmax_bwd(alpha, ins, idx_flat, s_t, adv, R, nobj, Lp, self.dmerge, n, E.st())
-            E.tape.append(bwd_losses)
-        iters = []
-        for it in range(G):                                  # per-iteration views, as the one-pass-per-iteration path returns them
-            hw = [(H // f) * (W // f) for f in FACTORS]
-            iters.append(dict(idx=idx_flat[it * n:(it + 1) * n], alpha=alpha[it * n * Lp:(it + 1) * n * Lp],
-                              s_t=s_t[it * n:(it + 1) * n],
-                              targets=[targets[l][it * n * hw[l]:(it + 1) * n * hw[l]] for l in range(5)],
-                              preds=[p.images(it * n, n) for p in preds],
-                              sums=[sums_all[l * 8 * R + it * 8 * n:l * 8 * R + (it + 1) * 8 * n] for l in range(5)]))
-        return dict(iters=iters, max_iter=G, merge=merge, x_enc=x_enc, scal=scal)
+                E.tape.append(lambda: E.grads.merge_shared(E))      # runs after the reversed forks have joined stream 0
+        for sid in side:                    # all forks up front: a fork issued later would wait for iteration 0's chain
+            E.sync(0, sid)
+        chain = [(None, None)] * len(passes)                        # (x, pred) of each pass's previous level
+        preds = [[] for _ in passes]
+        for lvl in range(5):                # level-major issue order: the cross chains of all passes interleave
+            for k, (p, fr) in enumerate(zip(passes, fronts)):
+                R = p.G * n
+                E.defer_bn_running = p.defer
+                with E.on(p.sc):
+                    cat = self.level_cross(lvl, skips[lvl], masks[k][lvl], p.G)
+                E.sync(p.sc, p.sm)
+                with E.on(p.sm):
+                    x, pred = self.level_main(lvl, cat, *chain[k], mask_all[lvl], fr.s_t, W, training, masks[k][lvl])
+                    E.lib.isa_mask_loss_sums(pred.d(), fr.targets[lvl], None, fr.sums_all[lvl * 8 * R:(lvl + 1) * 8 * R],
+                                             E.st())
+                chain[k] = (x, pred)
+                preds[k].append(pred)
+                if capture is not None:
+                    for g in range(p.G):
+                        capture["it%d.L%d.x" % (p.it0 + g, lvl)] = x.images(g * n, n)
+                        capture["it%d.L%d.pred" % (p.it0 + g, lvl)] = pred.images(g * n, n)
+        E.defer_bn_running = False
+        for sid in sorted({p.sm for p in passes if p.sm}):          # a cross-only side stream was joined level by level
+            E.sync(sid, 0)
+        E.flush_bn_running()
+        hw = [(H // f) * (W // f) for f in FACTORS]
+        for k, (p, fr) in enumerate(zip(passes, fronts)):           # losses in iteration order: the baseline is an EMA
+            R = p.G * n
+            coef, adv = E.f32(5 * 4 * R), E.f32(R)
+            E.lib.isa_head_loss(fr.sums_all, fr.alpha, fr.s_t, Lp, n, self._level_w, CE_WEIGHT, LAMBDA_L, LAMBDA_R,
+                                1.0 / max_iter, self.baseline, 1 if training else 0, coef, adv, scal, p.G, E.st())
+            if E.record:
+                def bwd_losses(fr=fr, R=R, preds=preds[k], coef=coef, adv=adv):
+                    for lvl in range(5):
+                        acc = E.grads.claim(preds[lvl], E)
+                        E.lib.isa_mask_loss_grad(preds[lvl].d(), fr.targets[lvl], None, coef[lvl * 4 * R:(lvl + 1) * 4 * R],
+                                                 E.grads.grad_of(preds[lvl]).d(), acc, E.st())
+                    E.lib.isa_ins_softmax_bwd(fr.alpha, ins, fr.idx, fr.s_t, adv, R, nobj, Lp, self.dmerge, n, E.st())
+                E.tape.append(bwd_losses)
+            for g in range(p.G):                                    # per-iteration views of the pass's tensors
+                rows = lambda t, per: t[g * n * per:(g + 1) * n * per]
+                iters.append(dict(idx=rows(fr.idx, 1), alpha=rows(fr.alpha, Lp), s_t=rows(fr.s_t, 1),
+                                  targets=[rows(fr.targets[l], hw[l]) for l in range(5)],
+                                  preds=[q.images(g * n, n) for q in preds[k]],
+                                  sums=[rows(fr.sums_all[l * 8 * R:(l + 1) * 8 * R], 8) for l in range(5)]))
+        return dict(iters=iters, max_iter=max_iter, merge=merge, x_enc=x_enc, scal=scal)
 
     # ------------------------------------------------------------------ ground-truth-free inference (ReSeg.segment)
     def segment(self, x_dec: Act, feats, sem_map: torch.Tensor, max_objects: int, injected_s_t=None, capture=None):
@@ -567,14 +490,7 @@ class InstanceHead:
         x_enc = self.stems(x_dec)
         s = self.spatial_attention(x_enc, sem_map)
         merge = self.hard_attention_scores(s, sem_map)
-        mask_all = []
-        for f in FACTORS:
-            if f == 1:
-                mask_all.append(sem_map)
-            else:
-                m = E.f32(n * (H // f) * (W // f))
-                E.lib.isa_pool_target(None, None, sem_map, 1, n, H, W, f, m, n, E.st())
-                mask_all.append(m)
+        mask_all = self.fg_pyramid(sem_map, 1, n, H, W)
         if capture is not None:
             capture.update(x_enc=x_enc, s_sp=s, merge=merge)
         skips = [feats[4], feats[3], feats[2], feats[1], feats[0]]

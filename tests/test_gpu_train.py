@@ -527,6 +527,47 @@ def test_batched_iterations_match_the_per_iteration_pass():
     assert abs(b1 - bN) <= 1e-6 * max(1.0, abs(b1))
 
 
+def test_one_iteration_training_step_vs_oracle():
+    """A training batch whose smallest image holds ONE object runs one decoder iteration (attenet2.py:377-380:
+    max_iter = min(MAX_ITER, smallest object count)): one pass of B images, one statistic group, no side stream.  The
+    loss scalars against the live CPU oracle at the fp32 bound of test_forward_with_gt_vs_reference_golden (1e-3 relative);
+    every decoder BatchNorm - in the level chain and in the cross branch - advances exactly once; the gradients are
+    finite and the nine never-trained tensors stay zero."""
+    ReSeg, Trainer = need_gpu()
+    x, sem, ins, n = R.synth_batch(2, 64, 64, seed=1)
+    n[0] = 1
+    assert [int(v) for v in n.view(-1)] == [1, 6]
+    sel = [list(range(int(k))) for k in n.view(-1)]
+    sd = R.synth_state_dict(23, True)
+    m = ReSeg(2, True, dtype=torch.float32)
+    m.load_state_dict(sd)
+    m.train()
+    m.head.drop_rate = 0.0
+    m.head.sample_in_training = False                     # greedy glimpse point: the oracle takes the argmax too
+    tr = Trainer(m)
+    layers = ("decoder.bone.upAtten4.UpAtten.conv1.1", "decoder.bone.upAtten4.UpAtten.cross.up_feature.0.conv.1")
+    tracked = {k: int(m.store.int_buffers[k + ".num_batches_tracked"]) for k in layers}
+    out = tr.forward_backward(x, sem, ins, n, selected_idx=sel)
+    torch.cuda.synchronize()
+    assert m.last_record["max_iter"] == 1 and len(m.last_record["iters"]) == 1
+    with torch.no_grad():
+        ref = R.reseg_forward(sd, x, sem, ins, n, ctx=R.Ctx(bn_train=True, training=True, drop_rate=0.0),
+                              state=R.HeadState(), selected_idx=sel, sample_fn=lambda a: a.argmax(1))
+    for i, key in enumerate(("ins_cost_finite", "criterion", "ins_ce_loss", "ins_dice_loss")):
+        got, r = float(out["head"][i]), float(ref[key])
+        print("%s: %.7g (oracle %.7g)" % (key, got, r))
+        assert abs(got - r) <= 1e-3 * max(1.0, abs(r)), (key, got, r)
+    for k in layers:
+        assert int(m.store.int_buffers[k + ".num_batches_tracked"]) == tracked[k] + 1, k
+    assert torch.isfinite(m.store.grad[:m.store.n_train]).all()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "train_64_f64.npz"))
+    never = [k[len("grad_none/"):] for k in z.files if k.startswith("grad_none/")]
+    assert len(never) == 9
+    for name in never:
+        assert float(m.store.gview(name).abs().max()) == 0.0, name
+        assert m.store.offsets[name] >= m.store.n_train
+
+
 def _family(name):
     if name.startswith("base."):
         return "backbone"
