@@ -204,6 +204,14 @@ int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* y, const is
                               const void* w_flipped, float* dw, int32_t csrc,
                               const isa_tensor* dx, int32_t accumulate, const isa_tensor* addend,
                               float* ws, int64_t ws_floats, isa_slab_arena* defer, void* stream);
+/* The same call for a depthwise conv WITH a bias (the instance stems, reseg.py:78-102): dbias[c] += sum of dy over all
+ * pixels, folded with dw (same launch, immediate or deferred).  Nothing else depends on the bias: y is the stored conv
+ * output, bias included.  dbias == NULL is isa_dwconv3x3_bn_backward, bit for bit.                   */
+int isa_dwconv3x3_bias_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                   const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                   const void* w_flipped, float* dw, int32_t csrc,
+                                   const isa_tensor* dx, int32_t accumulate, const isa_tensor* addend,
+                                   float* ws, int64_t ws_floats, isa_slab_arena* defer, void* stream, float* dbias);
 
 /* The same fusion for a bias-free 1x1 convolution y = W x (W fp32 [N][K], state_dict layout) followed by a
  * train-mode BatchNorm2d (MobileNetDenseASPP.py:105-107,113-114 expand / project; :81-82 InvertedV1):
@@ -222,6 +230,16 @@ int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_
                             const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
                             const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
                             void* stream);
+/* The same call for a 1x1 conv WITH a bias, y = W x + bias (fp32 [N] each): dbias[n] += sum of dy[.][n] over all pixels,
+ * folded with dw (same launch, immediate or deferred).  With y == NULL the recompute adds bias[n] where isa_conv_gemm's
+ * epilogue does (fp32, before the bf16 rounding), so the caller's guarantee above reads "with this bias".
+ * bias and dbias come together: one without the other is ISA_EINVAL, checked before anything is launched.  Both NULL
+ * is isa_conv1x1_bn_backward, bit for bit.                                                          */
+int isa_conv1x1_bias_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                 const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                 const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
+                                 const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
+                                 void* stream, const float* bias, float* dbias);
 
 /* ---- deferred weight-gradient folds ------------------------------------------------------------
  * Every weight-gradient entry point is two-stage: partial slabs, then a small fold kernel that adds them into

@@ -32,6 +32,20 @@ struct PwParams {
     const bf16_t* addend; int lda;       // optional: dx += addend (the residual branch's gradient, saves its axpy pass)
     int G;                               // statistic groups: M is per group (common.hpp)
 };
+constexpr int PW_BIAS = 4;               // flag on the kernel's XMODE_ argument: the conv has a bias
+// The y slot of the argument block in the biased recompute instantiations (REC && BIAS): REC never reads y, and there
+// the slot holds the conv's fp32 bias vector instead.  These two functions are the only places that say so; kernel code
+// that wants the bias calls rec_bias<REC, BIAS>(p) and fails to compile in any other instantiation.
+template <bool REC, bool BIAS>
+__host__ __device__ __forceinline__ const float* rec_bias(const PwParams& p) {
+    static_assert(REC && BIAS, "the y slot carries the bias vector in the biased recompute instantiations only");
+    return reinterpret_cast<const float*>(p.y);
+}
+template <bool REC, bool BIAS>
+inline void set_rec_bias(PwParams& p, const float* bias) {
+    static_assert(REC && BIAS, "the y slot carries the bias vector in the biased recompute instantiations only");
+    p.y = reinterpret_cast<const bf16_t*>(bias);
+}
 
 #ifdef ISA_PHASE_TRACE
 __device__ unsigned long long phase_buf[10];
@@ -68,8 +82,16 @@ __device__ __forceinline__ bf16x8 rec_wfrag(const bf16_t* wl, int s, int i, int 
 // REC: y is not read but recomputed per chunk as W . pro(x) from the pro(x) slab and register-held W fragments, with the
 // forward kernel's MFMA sequence (conv_gemm.hip, conv_gemm_kernel) so that the rounded bf16 value is the one it stored;
 // raw g waits in the dy slab and is overwritten by dy in the accumulator layout
-template <int TN, int TK, int YACT, int XMODE, bool EPI, bool REC>
+// BIAS: the conv has a bias.  The recompute adds it where the forward's epilogue does (fp32, before the bf16 rounding), and
+// lane (r, hh) sums the dy values of its 16 pixels of channel 32 i + r as the dy slab holds them (rounded and masked): the
+// slab's bias slot carries the workgroup's column sums of dy instead of zeros.  The stored-y form reads them back from
+// the slab in the recompute's layout and order, so both forms give the same bits.  Without BIAS all of this is compiled out.
+// BIAS rides on the XMODE argument (XMODE_ = xmode | PW_BIAS) and the recompute finds the bias vector in the y slot, which
+// it does not use otherwise: the bias-free instantiations keep their names, their argument block and their code
+template <int TN, int TK, int YACT, int XMODE_, bool EPI, bool REC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pw_bn_bwd_kernel(PwParams p) {
+    constexpr int XMODE = XMODE_ & 3;
+    constexpr bool BIAS = (XMODE_ & PW_BIAS) != 0;
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
     PHASE_DECL(); PHASE(0);
     constexpr int PMB = 32;
@@ -203,6 +225,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float s0[8], s1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+    // bias gradient partials: channel 32 i + r, this half-wave's 16 pixels of every chunk (the accumulator layout)
+    constexpr int NSB = BIAS ? TN : 1;
+    float sb[NSB];
+#pragma unroll
+    for (int j = 0; j < NSB; ++j) sb[j] = 0.f;
+    // the recompute's bias values, channel 32 i + r: loaded once, ahead of the loop.  (A load inside the loop is waited for
+    // with the next chunk's prefetch in front of it in the in-order counter, i.e. it drains the prefetch.)
+    float bvr[BIAS && REC ? TN : 1];
+    if constexpr (BIAS && REC) {
+#pragma unroll
+        for (int i = 0; i < TN; ++i) bvr[i] = rec_bias<REC, BIAS>(p)[min(32 * i + r, p.N - 1)];
+    }
 
     auto stash = [&](long chunk) {                               // BN-backward / prologue arithmetic, then LDS
         const long mbase = chunk * PMB;
@@ -289,13 +323,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int e = 0; e < 16; ++e) gr[e] = d[((e & 3) + 8 * (e >> 2)) * (SN / 2)];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
+                    if constexpr (BIAS) {                         // y = W . pro(x) + bias, rounded as the forward's epilogue stored it
+                        const float val = bn_bwd_dy<YACT>(__uint_as_float((unsigned)gr[e] << 16), (float)(bf16_t)(ya[e] + bvr[i]), ysc, ysh, ymu, yq, yk0, p.yact);
+                        const unsigned o = __builtin_bit_cast(unsigned short, (bf16_t)val);
+                        const unsigned om = o & ((e & 3) + 8 * (e >> 2) < rows ? colm : 0u);
+                        d[((e & 3) + 8 * (e >> 2)) * (SN / 2)] = (unsigned short)om;
+                        sb[i] += __uint_as_float(om << 16);
+                    } else {
                     const float val = bn_bwd_dy<YACT>(__uint_as_float((unsigned)gr[e] << 16), (float)(bf16_t)ya[e], ysc, ysh, ymu, yq, yk0, p.yact);
                     const unsigned o = __builtin_bit_cast(unsigned short, (bf16_t)val);
                     d[((e & 3) + 8 * (e >> 2)) * (SN / 2)] = (unsigned short)(o & ((e & 3) + 8 * (e >> 2) < rows ? colm : 0u));
+                    }
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
+        } else if constexpr (BIAS) {
+#pragma unroll
+            for (int i = 0; i < TN; ++i) {
+                const unsigned short* d = reinterpret_cast<const unsigned short*>(sD + 4 * hh * SN + (32 * i + r) * 2);
+                unsigned short dv[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) dv[e] = d[((e & 3) + 8 * (e >> 2)) * (SN / 2)];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) sb[i] += __uint_as_float((unsigned)dv[e] << 16);
+            }
         }
         // ---- weight gradient
 #pragma unroll
@@ -388,13 +440,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if ((lane & 15) < VK) { slot[ck0 + j] = v0; slot[TK * 32 + ck0 + j] = v1; }
         }
     }
+    // bias gradient: the two half-waves hold the same channels; every wave parks one slot
+    float* bs = xs + 16 * 2 * TK * 32;                            // [4 waves][TN*32]
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int i = 0; i < TN; ++i) {
+            const float v = sb[i] + __shfl_xor(sb[i], 32, 64);
+            if (lane < 32) bs[wave * (TN * 32) + 32 * i + r] = v;
+        }
+    }
     __syncthreads();
     PHASE(6);
     constexpr int SLABF = TN * TK * 1024 + TN * 32;
     float* slab = p.ws + (long)blockIdx.x * SLABF;
     fold_store<TN, TK>(part, slab, tid);
     PHASE(7);
-    if (tid < TN * 32) slab[TN * TK * 1024 + tid] = 0.f;         // no conv bias on this path
+    if constexpr (BIAS) {
+        if (tid < TN * 32) {                                      // column sums of dy: the fold adds them to dbias
+            float v = 0.f;
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl) v += bs[sl * (TN * 32) + tid];
+            slab[TN * TK * 1024 + tid] = v;
+        }
+    } else {
+        if (tid < TN * 32) slab[TN * TK * 1024 + tid] = 0.f;     // no conv bias on this path
+    }
     if (want_xred && tid < 2 * TK * 32) {
         float v = 0.f;
 #pragma unroll
@@ -407,11 +477,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     PHASE_FLUSH(phase_buf);
 }
 
-template <int TN, int TK, int YACT, int XMODE, bool REC>
-int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
+template <int TN, int TK, int YACT, int XMODE, bool REC, bool BIAS>
+int launch_inst(PwParams& p, const float* bias, float* dbias, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
     constexpr size_t slab = (size_t)32 * (SN + SK) * 4 + 9 * 64 * 4;
-    constexpr size_t redb = ((size_t)fold_part_floats<TN, TK>() + 16 * 2 * TK * 32) * 4;   // parked partials + BN(x) sum slots
+    constexpr size_t redb = ((size_t)fold_part_floats<TN, TK>() + 16 * 2 * TK * 32 + (BIAS ? 4 * TN * 32 : 0)) * 4;   // parked partials + BN(x) sum slots (+ bias slots)
     constexpr size_t wkeep = (REC && TN * TK == 4) ? (size_t)TK * 32 * (TN * 32 + 8) * 2 : 0;     // WLDS: W stays behind the constants
     constexpr size_t lds = slab + wkeep > redb ? slab + wkeep : redb;
     const long nchunks = (p.M + 31) / 32;
@@ -424,18 +494,21 @@ int launch_inst(PwParams& p, long ws_floats, isa_slab_arena* sa, const isa_pro* 
     if (gx > ws_cap) gx = ws_cap;
     gx = group_grid(gx, p.G);
     if (int rc = fin_standalone(xfin, p.K, xfin_groups, s)) return rc;      // every check has passed
-    if (p.accumulate || p.addend) hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, true, REC>), dim3((unsigned)gx), dim3(256), lds, s, p);
-    else hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XMODE, false, REC>), dim3((unsigned)gx), dim3(256), lds, s, p);
+    constexpr int XM = XMODE | (BIAS ? PW_BIAS : 0);
+    PwParams q = p;
+    if constexpr (BIAS && REC) set_rec_bias<REC, BIAS>(q, bias);
+    if (p.accumulate || p.addend) hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XM, true, REC>), dim3((unsigned)gx), dim3(256), lds, s, q);
+    else hipLaunchKernelGGL((pw_bn_bwd_kernel<TN, TK, YACT, XM, false, REC>), dim3((unsigned)gx), dim3(256), lds, s, q);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
-    return wgrad_slab_reduce_launch(p.ws, p.dw, nullptr, (int)gx, TN, TK, p.N, p.K, 1, sa, s);
+    return wgrad_slab_reduce_launch(p.ws, p.dw, BIAS ? dbias : nullptr, (int)gx, TN, TK, p.N, p.K, 1, sa, s);
 }
 
-template <int TN, int TK>
-int launch_tile(PwParams& p, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
+template <int TN, int TK, bool BIAS>
+int launch_tile(PwParams& p, const float* bias, float* dbias, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     const bool y6 = p.yact == ISA_ACT_RELU6, y0 = p.yact == ISA_ACT_NONE;
-#define PW_X(YA, RC) (xmode == 0 ? launch_inst<TN, TK, YA, 0, RC>(p, ws_floats, sa, xfin, xfin_groups, s) \
-                    : xmode == 1 ? launch_inst<TN, TK, YA, 1, RC>(p, ws_floats, sa, xfin, xfin_groups, s) \
-                                 : launch_inst<TN, TK, YA, 2, RC>(p, ws_floats, sa, xfin, xfin_groups, s))
+#define PW_X(YA, RC) (xmode == 0 ? launch_inst<TN, TK, YA, 0, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s) \
+                    : xmode == 1 ? launch_inst<TN, TK, YA, 1, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s) \
+                                 : launch_inst<TN, TK, YA, 2, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s))
     if (y6) return p.y ? PW_X(ISA_ACT_RELU6, false) : PW_X(ISA_ACT_RELU6, true);
     if (y0) return p.y ? PW_X(ISA_ACT_NONE, false) : PW_X(ISA_ACT_NONE, true);
     return PW_X(ACT_RT, false);                                   // a null y was refused by the entry point
@@ -448,11 +521,13 @@ int launch_tile(PwParams& p, int xmode, long ws_floats, isa_slab_arena* sa, cons
 extern "C" int isa_phase_trace_pw(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(phase_buf), sizeof(phase_buf)) == hipSuccess ? ISA_OK : ISA_ELAUNCH; }
 #endif
 
-extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
-                                       const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
-                                       const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
-                                       const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
-                                       void* stream) {
+// bias / dbias: both or neither (the conv's bias and its gradient); see include/isa_kernels.h
+extern "C" int isa_conv1x1_bias_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                            const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                            const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
+                                            const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
+                                            void* stream, const float* bias, float* dbias) {
+    if ((bias == nullptr) != (dbias == nullptr)) return ISA_EINVAL;
     if (!tensor_ok(g, 8) || (y && !tensor_ok(y, 8)) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
     if (!fin_valid(xpro)) return ISA_EINVAL;      // a pending finalize (no in-kernel form here) runs after the last check
     if (g->dtype != ISA_BF16 || (y && y->dtype != ISA_BF16) || x->dtype != ISA_BF16 || dx->dtype != ISA_BF16) return ISA_EINVAL;
@@ -489,8 +564,20 @@ extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y,
     if (!pro_trivial(xp) || xbn) xmode = (xbn && xp.act == ISA_ACT_RELU6) ? 1 : 2;
     hipStream_t s = as_stream(stream);
     const int tn = (N + 31) / 32, tk = (K + 31) / 32;
-    if (tn == 1 && tk == 1) return launch_tile<1, 1>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), s);
-    if (tn == 1 && tk == 2) return launch_tile<1, 2>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), s);
-    if (tn == 2 && tk == 1) return launch_tile<2, 1>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), s);
-    return launch_tile<2, 2>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), s);
+#define PW_T(TN_, TK_) (bias ? launch_tile<TN_, TK_, true>(p, bias, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), s) \
+                             : launch_tile<TN_, TK_, false>(p, bias, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), s))
+    if (tn == 1 && tk == 1) return PW_T(1, 1);
+    if (tn == 1 && tk == 2) return PW_T(1, 2);
+    if (tn == 2 && tk == 1) return PW_T(2, 1);
+    return PW_T(2, 2);
+#undef PW_T
+}
+
+extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                       const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                       const float* w, float* dw, const isa_tensor* dx, int32_t accumulate,
+                                       const isa_tensor* addend, float* ws, int64_t ws_floats, isa_slab_arena* defer,
+                                       void* stream) {
+    return isa_conv1x1_bias_bn_backward(g, y, ybn, x, xpro, xbn, w, dw, dx, accumulate, addend, ws, ws_floats, defer, stream,
+                                        nullptr, nullptr);
 }

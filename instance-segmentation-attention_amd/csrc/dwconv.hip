@@ -714,8 +714,22 @@ template <> struct dd_stride<bf16_t> { static constexpr int v = 40; };         /
 //     per-channel constants in registers: it is VALU-issue bound next to the compute wave of the same SIMD.
 // EPI: the tile epilogue has extra operands (accumulate into old dx and / or a residual addend): rare, so the common
 // variant compiles their loads and registers out.
-template <typename T, int YACT, int XMODE, bool DB, bool EPI>
+// BIAS: the conv has a bias.  Its gradient is the sum of dy over the tile's own pixels: the compute role adds the centre
+// values it loads for the weight gradient (halo pixels belong to the neighbouring tiles, out-of-image slots hold zero),
+// and slab row 9 carries the sums instead of zeros.  With a plain x (XMODE 0, ~200 VGPRs) the lane's eight running sums
+// are registers.  With a prologue the bias-free kernel sits at the 256-register limit of two waves per SIMD and eight more
+// accumulators spilled in its tile loop: there they live in two 16-byte LDS words of the lane's own, read, added to and
+// written back once per tile (no contention, a fixed order).  Measured (profiles/ab_fused_bias.txt, HBM-cold, 16 x 256^2):
+// the stems' 48-channel launch with a ReLU6 prologue 157.5 us against 155.2 for the bias-free kernel (208 with the spill,
+// 228 with one LDS float atomic per sum and tile), the 32-channel one with a plain x 75.2 against 74.0; in the step
+// 159 and 71 us (profiles/fused_bias_step.txt).  Nothing else depends on the bias: y is stored.  BIAS rides on the
+// XMODE argument (XMODE_ = xmode | DW_BIAS): the bias-free instantiations keep their names and their code, and pay
+// nothing for this.
+constexpr int DW_BIAS = 4;
+template <typename T, int YACT, int XMODE_, bool DB, bool EPI>
 __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dw_bn_bwd_kernel(FusedParams p) {
+    constexpr int XMODE = XMODE_ & 3;
+    constexpr bool BIAS = (XMODE_ & DW_BIAS) != 0;
     constexpr int PSD = dd_stride<T>::v;
     constexpr int XACT = XMODE == 1 ? ISA_ACT_RELU6 : (XMODE == 0 ? ISA_ACT_NONE : ACT_RT);
     constexpr int NBUF = DB ? 2 : 1;
@@ -726,7 +740,9 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     T* dt_base = xt_base + NBUF * TILE_ELEMS;                                // [NBUF][HALO][PSD] dy
     float* wts = reinterpret_cast<float*>(dt_base + NBUF * TILE_ELEMS);      // [9][CB] flipped taps
     float* cst = wts + 9 * CB;                                               // [10][CB] per-channel constants
-    float* red = cst + 10 * CB;                                              // [11*CB]
+    float* red = cst + 10 * CB;                                              // [11*CB] (BIAS: [12*CB])
+    f32x4* dbl = reinterpret_cast<f32x4*>(red + 12 * CB);                    // DB_LDS: [2][256] per-lane sums of dy
+    constexpr bool DB_LDS = BIAS && XMODE != 0;
     const int tid = threadIdx.x;
     const int ltid = tid & 255;                                              // index inside the role group
     const bool loader = DB && tid >= 256;
@@ -880,7 +896,7 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         const int i = tid + k * NTHR;
         if (i < 9 * CB) wts[i] = (c_base + (i & (CB - 1)) < p.c) ? wv[k] : 0.f;
     }
-    for (int i = tid; i < 11 * CB; i += NTHR) red[i] = 0.f;     // rows 0-8: dW taps, 9-10: BN(x) sums
+    for (int i = tid; i < (11 + BIAS) * CB; i += NTHR) red[i] = 0.f;     // rows 0-8: dW taps, 9-10: BN(x) sums (BIAS: 11 = sum dy)
 
     // single-buffer form: one tile, chunks of NB slots
     auto stage = [&](int b, int ty, int tx, T* xt, T* dt) {
@@ -899,6 +915,12 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         }
     };
 
+    float db[BIAS && !DB_LDS ? 8 : 1];                           // BIAS: sum of dy over this lane's centre pixels (compute role)
+#pragma unroll
+    for (int j = 0; j < (BIAS && !DB_LDS ? 8 : 1); ++j) db[j] = 0.f;
+    if constexpr (DB_LDS) {
+        if (!loader) { dbl[ltid] = f32x4{0.f, 0.f, 0.f, 0.f}; dbl[256 + ltid] = f32x4{0.f, 0.f, 0.f, 0.f}; }     // this lane's own words
+    }
     auto compute = [&](int b, int ty, int tx, const T* xt, const T* dt, float (&acc)[9][8], float (&s0)[8], float (&s1)[8]) {
         const long torg = ((long)b * p.h + ty * TH) * p.w_ + tx * TW;                      // tile origin pixel
         T* dxb = dxo + torg * p.lddx + oodx;
@@ -979,6 +1001,18 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             float d[4][8];
 #pragma unroll
             for (int o = 0; o < 4; ++o) load8<T>(dt + ((row + 1) * (TW + 2) + x0 + 1 + o) * PSD + cg * 8, d[o]);
+            if constexpr (DB_LDS) {
+                f32x4 lo = dbl[ltid], hi = dbl[256 + ltid];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    lo[j] += (d[0][j] + d[1][j]) + (d[2][j] + d[3][j]);
+                    hi[j] += (d[0][4 + j] + d[1][4 + j]) + (d[2][4 + j] + d[3][4 + j]);
+                }
+                dbl[ltid] = lo; dbl[256 + ltid] = hi;
+            } else if constexpr (BIAS) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) db[j] += (d[0][j] + d[1][j]) + (d[2][j] + d[3][j]);
+            }
             float ps[8], ph[8];
             if constexpr (XMODE != 0) { ld8(cst + 6 * CB + cg * 8, ps); ld8(cst + 7 * CB + cg * 8, ph); }
             // Zero padding applies to pro(x), not to x: on border tiles the out-of-image window slots are masked after
@@ -1103,11 +1137,27 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             const float v0 = row_fold<4>(s0[j]), v1 = row_fold<4>(s1[j]);
             if (writer) { part[(72 + j) * 64 + slot] = v0; part[(80 + j) * 64 + slot] = v1; }
         }
+        if constexpr (BIAS) {
+            float dv[8];
+            if constexpr (DB_LDS) {
+                const f32x4 lo = dbl[ltid], hi = dbl[256 + ltid];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { dv[j] = lo[j]; dv[4 + j] = hi[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dv[j] = db[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = row_fold<4>(dv[j]);
+                if (writer) part[(88 + j) * 64 + slot] = v;
+            }
+        }
     }
     __syncthreads();
     {
         const float* part = reinterpret_cast<const float*>(sm);
-        for (int o = tid; o < 88 * 4; o += NTHR) {               // o = v * 4 + cg
+        for (int o = tid; o < (88 + 8 * BIAS) * 4; o += NTHR) {  // o = v * 4 + cg
             const f32x4 a = *reinterpret_cast<const f32x4*>(part + o * 16), b = *reinterpret_cast<const f32x4*>(part + o * 16 + 4),
                         c = *reinterpret_cast<const f32x4*>(part + o * 16 + 8), d = *reinterpret_cast<const f32x4*>(part + o * 16 + 12);
             const f32x4 t = (a + b) + (c + d);
@@ -1117,7 +1167,11 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     }
     __syncthreads();
     float* slab = p.ws + ((long)blockIdx.x * gridDim.y + blockIdx.y) * 10 * CB;
-    for (int i = tid; i < 10 * CB; i += NTHR) slab[i] = i < 9 * CB ? red[i] : 0.f;       // row 9 = conv bias slot (none here)
+    if constexpr (BIAS) {
+        for (int i = tid; i < 10 * CB; i += NTHR) slab[i] = i < 9 * CB ? red[i] : red[i + 2 * CB];     // row 9 = conv bias slot: sum dy
+    } else {
+        for (int i = tid; i < 10 * CB; i += NTHR) slab[i] = i < 9 * CB ? red[i] : 0.f;       // row 9 = conv bias slot (none here)
+    }
     if (want_xred && tid < 2 * CB) {
         const int cc = tid & (CB - 1), which = tid / CB;
         const float v = red[9 * CB + tid];
@@ -1128,26 +1182,27 @@ __global__ __launch_bounds__(DB ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
-template <typename T, int YACT, int XMODE, bool EPI = true>
+template <typename T, int YACT, int XMODE, bool BIAS, bool EPI = true>
 int launch_fused_inst(FusedParams& p, dim3 grid, hipStream_t s) {
     constexpr bool DB = sizeof(T) == 2;                          // two pairs of tile buffers: 109 KB for bf16, 196 KB for f32
     if constexpr (EPI) {
-        if (!p.accumulate && !p.addend) return launch_fused_inst<T, YACT, XMODE, false>(p, grid, s);
+        if (!p.accumulate && !p.addend) return launch_fused_inst<T, YACT, XMODE, BIAS, false>(p, grid, s);
     }
     constexpr int NBUF = DB ? 2 : 1;
-    constexpr size_t lds = NBUF * 2 * (size_t)HALO * dd_stride<T>::v * sizeof(T) + (9 + 10 + 11) * CB * 4;   // raw x + dy tiles
+    constexpr size_t lds = NBUF * 2 * (size_t)HALO * dd_stride<T>::v * sizeof(T) + (9 + 10 + 11 + BIAS) * CB * 4 + BIAS * 8 * 256 * 4;   // raw x + dy tiles
+    constexpr auto kern = &dw_bn_bwd_kernel<T, YACT, XMODE | (BIAS ? DW_BIAS : 0), DB, EPI>;
     static bool configured = false;
     if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bn_bwd_kernel<T, YACT, XMODE, DB, EPI>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ISA_ELAUNCH;
         configured = true;
     }
-    hipLaunchKernelGGL((dw_bn_bwd_kernel<T, YACT, XMODE, DB, EPI>), grid, dim3(DB ? 512 : 256), lds, s, p);
+    hipLaunchKernelGGL(kern, grid, dim3(DB ? 512 : 256), lds, s, p);
     return ISA_OK;
 }
 
 template <typename T>
-int launch_fused(FusedParams& p, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
+int launch_fused(FusedParams& p, float* dbias, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
     p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
     p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;              // p.n: images per statistic group
     const int ncb = (p.c + CB - 1) / CB;
@@ -1164,13 +1219,16 @@ int launch_fused(FusedParams& p, int xmode, long ws_floats, isa_slab_arena* sa, 
     int rc = fin_standalone(xfin, p.c, xfin_groups, s);                 // every check has passed
     if (rc != ISA_OK) return rc;
     const bool y6 = p.yact == ISA_ACT_RELU6;
-    if (xmode == 0) rc = y6 ? launch_fused_inst<T, ISA_ACT_RELU6, 0>(p, grid, s) : launch_fused_inst<T, ACT_RT, 0>(p, grid, s);
-    else if (xmode == 1) rc = y6 ? launch_fused_inst<T, ISA_ACT_RELU6, 1>(p, grid, s) : launch_fused_inst<T, ACT_RT, 1>(p, grid, s);
-    else rc = y6 ? launch_fused_inst<T, ISA_ACT_RELU6, 2>(p, grid, s) : launch_fused_inst<T, ACT_RT, 2>(p, grid, s);
+#define DW_X(XM) (dbias ? (y6 ? launch_fused_inst<T, ISA_ACT_RELU6, XM, true>(p, grid, s) : launch_fused_inst<T, ACT_RT, XM, true>(p, grid, s)) \
+                        : (y6 ? launch_fused_inst<T, ISA_ACT_RELU6, XM, false>(p, grid, s) : launch_fused_inst<T, ACT_RT, XM, false>(p, grid, s)))
+    if (xmode == 0) rc = DW_X(0);
+    else if (xmode == 1) rc = DW_X(1);
+    else rc = DW_X(2);
+#undef DW_X
     if (rc != ISA_OK) return rc;
-    if (defer_push(sa, FoldDesc{p.ws, p.dw, nullptr, nullptr, 1, (int)gx, ncb, 9, 1, 0, CB, p.c, 0, p.csrc, 0, 0, 0, 0},
+    if (defer_push(sa, FoldDesc{p.ws, p.dw, dbias, nullptr, 1, (int)gx, ncb, 9, 1, 0, CB, p.c, 0, p.csrc, 0, 0, 0, 0},
                    gx * ncb * 10L * CB)) return ISA_OK;
-    hipLaunchKernelGGL(dw2_wgrad_reduce_kernel, dim3(ncb, DW2_RSPLIT), dim3(256), 0, s, p.ws, (int)gx, ncb, p.c, p.csrc, p.dw, (float*)nullptr);
+    hipLaunchKernelGGL(dw2_wgrad_reduce_kernel, dim3(ncb, DW2_RSPLIT), dim3(256), 0, s, p.ws, (int)gx, ncb, p.c, p.csrc, p.dw, dbias);
     return launch_status();
 }
 
@@ -1233,12 +1291,13 @@ extern "C" int isa_dwconv3x3_wgrad(const isa_tensor* x, const isa_pro* pro, cons
     return launch_wg2<float>(p, has_pro, ws_floats, defer, pro, as_stream(stream));
 }
 
-// Fused BN-apply + depthwise dgrad/wgrad + next BN-reduce; see dw_bn_bwd_kernel.
-extern "C" int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
-                                         const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
-                                         const void* w_flipped, float* dw, int32_t csrc,
-                                         const isa_tensor* dx, int32_t accumulate, const isa_tensor* addend,
-                                         float* ws, int64_t ws_floats, isa_slab_arena* defer, void* stream) {
+// Fused BN-apply + depthwise dgrad/wgrad + next BN-reduce; see dw_bn_bwd_kernel.  dbias (optional): the conv's bias gradient
+extern "C" int isa_dwconv3x3_bias_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                              const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                              const void* w_flipped, float* dw, int32_t csrc,
+                                              const isa_tensor* dx, int32_t accumulate, const isa_tensor* addend,
+                                              float* ws, int64_t ws_floats, isa_slab_arena* defer, void* stream,
+                                              float* dbias) {
     if (!tensor_ok(g, 8) || !tensor_ok(y, 8) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
     if (!fin_valid(xpro)) return ISA_EINVAL;      // a pending finalize (no in-kernel form here) runs after the last check
     if (!ybn || !ybn->scale || !ybn->shift || !ybn->mean || !ybn->invstd || !ybn->red || !(ybn->count > 0)) return ISA_EINVAL;
@@ -1271,6 +1330,15 @@ extern "C" int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* 
     p.n = g->n / p.G;
     int xmode = 0;
     if (!pro_trivial(xp) || xbn) xmode = (xbn && xp.act == ISA_ACT_RELU6) ? 1 : 2;
-    if (g->dtype == ISA_BF16) return launch_fused<bf16_t>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
-    return launch_fused<float>(p, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
+    if (g->dtype == ISA_BF16) return launch_fused<bf16_t>(p, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
+    return launch_fused<float>(p, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
+}
+
+extern "C" int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,
+                                         const isa_tensor* x, const isa_pro* xpro, const isa_bn_bwd* xbn,
+                                         const void* w_flipped, float* dw, int32_t csrc,
+                                         const isa_tensor* dx, int32_t accumulate, const isa_tensor* addend,
+                                         float* ws, int64_t ws_floats, isa_slab_arena* defer, void* stream) {
+    return isa_dwconv3x3_bias_bn_backward(g, y, ybn, x, xpro, xbn, w_flipped, dw, csrc, dx, accumulate, addend, ws, ws_floats,
+                                          defer, stream, nullptr);
 }

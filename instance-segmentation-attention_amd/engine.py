@@ -579,6 +579,9 @@ class Engine:
         # ... which recomputes the conv's raw output from x and W instead of reading it (y = NULL); ISA_PW_RECOMPUTE=0
         # hands it the stored tensor
         self.pw_recompute = os.environ.get("ISA_PW_RECOMPUTE", "1") != "0"
+        # convs WITH a bias ahead of a train-mode BN (the instance stems) take the same two fusions through the _bias_
+        # entry points; ISA_FUSE_BIAS=0 puts them back on the separate kernels
+        self.fuse_bias = os.environ.get("ISA_FUSE_BIAS", "1") != "0"
         # eval mode: BatchNorm (a constant affine), activation and residual ride in the conv's output epilogue
         # (isa_conv_gemm_ep) instead of a lazy prologue in the consumer plus a materialising pass per block
         self.fuse_eval = os.environ.get("ISA_FUSE_EVAL", "1") != "0"
@@ -886,7 +889,7 @@ class Engine:
         if self.record and record_bwd:
             rec = None
             if self.fuse_pw_bn and self.bn_train and self.dtype == torch.bfloat16 and taps == 1 and not transposed \
-                    and kmap is None and bias is None and x.needs_grad and out.c <= 64 and x.c <= 64 \
+                    and kmap is None and (bias is None or self.fuse_bias) and x.needs_grad and out.c <= 64 and x.c <= 64 \
                     and out.c % 8 == 0 and x.c % 8 == 0 and (x.pro is None or x.pro.bscale is None):
                 rec = self._pw_out[self._key(out)] = self._pw_in[self._key(x)] = ConvFusion(self._bn_just_recorded(x))
             # weight gradient: K is axis 1 of [N, K, kh, kw] and axis 0 of a ConvTranspose2d's [K, Co, 2, 2], whose bias
@@ -898,7 +901,7 @@ class Engine:
                 if rec is not None:
                     rec.done = True
                     if rec.ybn is not None:
-                        self._fused_pw_backward(x, wname, rec)
+                        self._fused_pw_backward(x, wname, rec, bias)
                         return
                     self._flush_addend(x, rec)
                 dy = self.grads.grad_of(out)
@@ -952,24 +955,26 @@ class Engine:
             acc = self.grads.claim(x, self)
             self.lib.isa_axpy(rec.addend.d(), self.grads.grad_of(x).d(), 1.0, acc, self.st())
 
-    def _fused_pw_backward(self, x: Act, wname, rec):
+    def _fused_pw_backward(self, x: Act, wname, rec, bias=None):
         """BN-apply of the conv's output BN + weight gradient + data gradient (+ reduce of the BN that
-        produced x) in one pass: isa_conv1x1_bn_backward."""
+        produced x) in one pass: isa_conv1x1_bn_backward, or isa_conv1x1_bias_bn_backward (+ bias gradient)."""
         ydesc, xdesc = self._fused_descs(x, rec)
         acc = self.grads.claim(x, self)
         g = rec.g
-        # rec.ybn.raw is what isa_conv_gemm stored for this x, this prologue and this weight (conv() fuses bias-free plain
+        # rec.ybn.raw is what isa_conv_gemm stored for this x, this prologue, this weight and this bias (conv() fuses plain
         # 1x1 bf16 convs only), so the kernel can recompute it; its compile-time activations are the two the blocks use.
         # More than 32 channels on both sides (the kernel's 2 x 2 tile) keep the stored y: the read saved is a quarter of
         # the bytes there and the recompute costs as much (profiles/ab_pw_recompute.txt)
         y = None if (self.pw_recompute and rec.ybn.act in (L.ACT_RELU6, L.ACT_NONE) and min(g.c, x.c) <= 32) else rec.ybn.raw.d()
         if self.profile:
             self.next_bytes = x.n * x.h * x.w * ((1 if y is None else 2) * g.c + 2 * x.c) * x.buf.element_size()
-        self.lib.isa_conv1x1_bn_backward(g.d(), y, C.byref(ydesc), x.d(), x.p(),
-                                         C.byref(xdesc) if xdesc is not None else None, self.params.ptr(wname),
-                                         self.params.gptr(wname), self.grads.grad_of(x).d(), acc,
-                                         rec.addend.d() if rec.addend is not None else None, self.ws, self.ws.numel(),
-                                         self.defer_handle(), self.st())
+        args = (g.d(), y, C.byref(ydesc), x.d(), x.p(), C.byref(xdesc) if xdesc is not None else None, self.params.ptr(wname),
+                self.params.gptr(wname), self.grads.grad_of(x).d(), acc, rec.addend.d() if rec.addend is not None else None,
+                self.ws, self.ws.numel(), self.defer_handle(), self.st())
+        if bias:
+            self.lib.isa_conv1x1_bias_bn_backward(*args, self.params.ptr(bias), self.params.gptr(bias))
+        else:
+            self.lib.isa_conv1x1_bn_backward(*args)
 
     def _launch_conv(self, x, reg, bias, out, in_mode, out_mode, st):
         if self.packer.table is None:
@@ -998,7 +1003,7 @@ class Engine:
                                out.d(), st, self.st())
         if self.record:
             rec = None
-            if self.fuse_dw_bn and self.bn_train and x.c % 8 == 0 and bias is None and x.needs_grad \
+            if self.fuse_dw_bn and self.bn_train and x.c % 8 == 0 and (bias is None or self.fuse_bias) and x.needs_grad \
                     and (x.pro is None or x.pro.bscale is None):
                 # BN(out)'s backward may leave its "apply" to this conv's backward (see bn()); BN(x)'s
                 # "reduce" can be produced here (see _bn_just_recorded)
@@ -1016,12 +1021,15 @@ class Engine:
                         acc = self.grads.claim(x, self)
                         if self.profile:
                             self.next_bytes = 4 * nb
-                        self.lib.isa_dwconv3x3_bn_backward(dy.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
-                                                           C.byref(xdesc) if xdesc is not None else None,
-                                                           self.packer.ptr(reg["dgrad"]), self.params.gptr(wname),
-                                                           self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
-                                                           rec.addend.d() if rec.addend is not None else None, self.ws,
-                                                           self.ws.numel(), self.defer_handle(), self.st())
+                        args = (dy.d(), rec.ybn.raw.d(), C.byref(ydesc), x.d(), x.p(),
+                                C.byref(xdesc) if xdesc is not None else None, self.packer.ptr(reg["dgrad"]),
+                                self.params.gptr(wname), self.params.shapes[wname][0], self.grads.grad_of(x).d(), acc,
+                                rec.addend.d() if rec.addend is not None else None, self.ws, self.ws.numel(),
+                                self.defer_handle(), self.st())
+                        if bias:
+                            self.lib.isa_dwconv3x3_bias_bn_backward(*args, self.params.gptr(bias))
+                        else:
+                            self.lib.isa_dwconv3x3_bn_backward(*args)
                         return
                     self._flush_addend(x, rec)
                 if self.profile:

@@ -166,6 +166,9 @@ SIGNATURES = {
     "isa_dwconv3x3_wgrad": [P_T, P_PRO, P_T, VP, VP, I32, VP, I64, VP, VP],
     "isa_dwconv3x3_bn_backward": [P_T, P_T, P_BN, P_T, P_PRO, P_BN, VP, VP, I32, P_T, I32, P_T, VP, I64, VP, VP],
     "isa_conv1x1_bn_backward": [P_T, P_T, P_BN, P_T, P_PRO, P_BN, VP, VP, P_T, I32, P_T, VP, I64, VP, VP],
+    # the same two for convs with a bias: ... + dbias, and ... + bias, dbias
+    "isa_dwconv3x3_bias_bn_backward": [P_T, P_T, P_BN, P_T, P_PRO, P_BN, VP, VP, I32, P_T, I32, P_T, VP, I64, VP, VP, VP],
+    "isa_conv1x1_bias_bn_backward": [P_T, P_T, P_BN, P_T, P_PRO, P_BN, VP, VP, P_T, I32, P_T, VP, I64, VP, VP, VP, VP],
     "isa_slab_arena_create": [VP, I64, C.POINTER(C.c_void_p)],
     "isa_slab_arena_destroy": [VP],
     "isa_slab_arena_begin": [VP],
