@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/isa_kernels.h"
+#include "slab_plan.hpp"
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -65,6 +66,14 @@ template <typename F> static inline auto by_dtype(int dtype, F&& f) {
 template <typename F> static inline auto by_flag(bool on, F&& f) {
     if (on) return f(std::true_type{});
     return f(std::false_type{});
+}
+// one of the compile-time ints Vs...: the one that equals v, else the last of them
+template <int V, int... Vs, typename F> static inline auto by_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+    else {
+        if (v == V) return f(std::integral_constant<int, V>{});
+        return by_int<Vs...>(v, f);
+    }
 }
 // channels (classes) held per thread, rounded up to eights: 8, 16, 24, else 32
 template <typename F> static inline auto by_width8(int c, F&& f) {
@@ -379,8 +388,14 @@ __device__ __forceinline__ GroupSel group_sel(int G) {
 }
 template <typename P> __device__ __forceinline__ P* goff(P* p, long off) { return p ? p + off : p; }
 static inline int tensor_groups(const isa_tensor* t) { return (t && t->groups > 1) ? t->groups : 1; }
-// grid of a grouped launch: a multiple of G, at least G
-static inline long group_grid(long gx, int G) { if (G <= 1) return gx < 1 ? 1 : gx; gx = gx / G * G; return gx < G ? G : gx; }
+// group_grid (slab_plan.hpp): the grid of a grouped launch, a multiple of G and at least G
+// The statistic groups a launch over x runs as: G when `per_group` (something the launch reads or writes differs by group),
+// else 1; 0 when the images do not divide into G groups (the caller refuses with ISA_EINVAL)
+static inline int stat_groups(const isa_tensor* x, bool per_group) {
+    const int G = tensor_groups(x);
+    if (G <= 1 || !per_group) return 1;
+    return x->n % G ? 0 : G;
+}
 
 // exclusive scan of n uint32 entries per segment, in place, one workgroup per segment (seg_sort.hip)
 int seg_exclusive_scan_u32(uint32_t* table, int nseg, long n, hipStream_t s);
@@ -415,6 +430,9 @@ __device__ __forceinline__ void block_sums_atomic(float (&a)[K], float* sh, floa
 // the second-stage fold in it (defer_push) instead of launching it; isa_slab_arena_flush folds every recorded slab
 // set in a handful of launches (descriptors travel as kernel arguments, so a captured hipGraph keeps them by
 // value).  All state lives in the caller's handle: no globals, no thread-locals.
+// Every weight-gradient launcher goes the same way: its own `want`, slab_plan for the region and
+// the grid, fin_standalone once every check has passed, the launch, then wgrad_slab_reduce_launch (MFMA-fragment slabs) or
+// dw_slab_reduce_launch (depthwise tile slabs), which record the fold in the arena or launch it at once.
 #include <vector>
 struct FoldDesc {
     const float* ws; float* dw; float* dbias; const int32_t* kmap;
@@ -431,3 +449,39 @@ struct isa_slab_arena {
 // the floats left; ISA_ENOMEM when less than the minimum slab budget is left (never a silent fallback).
 int defer_ws(isa_slab_arena* a, float** ws, long* ws_floats);
 bool defer_push(isa_slab_arena* a, FoldDesc d, long used_floats);   // true: recorded, the caller skips its own reduce launch
+// Where a launch of `want` workgroups in x writes its slabs (*ws: the arena's cursor when there is an arena) and how many
+// of them fit: slab_grid (slab_plan.hpp) on what defer_ws leaves.  Nothing is launched or taken from the arena here.
+static inline int slab_plan(isa_slab_arena* sa, float** ws, long ws_floats, long want, long set_floats, int G, long* gx) {
+    if (int rc = defer_ws(sa, ws, &ws_floats)) return rc;
+    return slab_grid(want, set_floats, ws_floats, G, sa != nullptr, gx);
+}
+// second stage, deferred when the slabs lie in the arena, else launched at once.  MFMA-fragment slabs of one tile group
+// with `taps` slab sets per workgroup (conv_fused_bwd.hip, conv3x3_tiled.hip); depthwise tile slabs [gx][ncb][10*cb]
+int wgrad_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int tn, int tk, int N, int cin, int taps,
+                             isa_slab_arena* sa, hipStream_t s);
+int dw_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int ncb, int cb, int C, int csrc, isa_slab_arena* sa,
+                          hipStream_t s);
+
+// ---- argument checks of the fused conv + BatchNorm backward entry points (dwconv.hip, conv_fused_bwd.hip) -------------
+// BN(y), whose backward the kernel applies: complete
+static inline bool bn_bwd_ok(const isa_bn_bwd* b) {
+    return b && b->scale && b->shift && b->mean && b->invstd && b->red && b->count > 0;
+}
+// BN(x), whose backward sums the kernel produces: absent, or the triple it needs
+static inline bool xbn_ok(const isa_bn_bwd* b) { return !b || (b->mean && b->invstd && b->out_red); }
+// the residual gradient added to dx: g's images, pixels and dtype, c channels
+static inline bool addend_ok(const isa_tensor* a, const isa_tensor* g, int c) {
+    return tensor_ok(a, 8) && a->dtype == g->dtype && a->c == c && a->n == g->n && a->h == g->h && a->w == g->w;
+}
+// how the kernel sees x: 0 a plain tensor, 1 a lazy BatchNorm + ReLU6 output whose backward sums it produces, 2 anything else
+static inline int fused_xmode(const ProDev& xp, const isa_bn_bwd* xbn) {
+    if (pro_trivial(xp) && !xbn) return 0;
+    return (xbn && xp.act == ISA_ACT_RELU6) ? 1 : 2;
+}
+// the BatchNorm operands of FusedParams / PwParams (same field names), after the checks above
+template <typename P> static inline void set_bn_bwd(P& p, const isa_bn_bwd* ybn, const ProDev& xp, const isa_bn_bwd* xbn) {
+    p.ysc = ybn->scale; p.ysh = ybn->shift; p.ymu = ybn->mean; p.yis = ybn->invstd; p.yred = ybn->red;
+    p.ycnt_inv = 1.f / ybn->count; p.yact = ybn->act; p.ydgamma = ybn->dgamma; p.ydbeta = ybn->dbeta;
+    p.xsc = xp.scale; p.xsh = xp.shift; p.xact = xp.act;
+    p.xmu = xbn ? xbn->mean : nullptr; p.xis = xbn ? xbn->invstd : nullptr; p.xred = xbn ? xbn->out_red : nullptr;
+}

@@ -7,9 +7,6 @@
 #include "common.hpp"
 #include "tr_lds.hpp"
 
-int wgrad_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int tn, int tk, int N, int cin, int taps,
-                             isa_slab_arena* sa, hipStream_t s);
-
 namespace {
 
 constexpr int TH = 8, TW = 32, HALO = (TH + 2) * (TW + 2);
@@ -263,14 +260,12 @@ int conv3x3_wgrad_tiled_launch(const isa_tensor* x, const isa_tensor* dy, float*
                                isa_slab_arena* sa, hipStream_t s) {
     C3WParams p{};
     p.x = (const bf16_t*)x->data; p.dy = (const bf16_t*)dy->data; p.n = x->n; p.h = x->h; p.w = x->w;
-    if (int rc = defer_ws(sa, &ws, &ws_floats)) return rc;
-    p.cin = x->c; p.ldx = x->ld; p.N = dy->c; p.ldd = dy->ld; p.ws = ws;
+    p.cin = x->c; p.ldx = x->ld; p.N = dy->c; p.ldd = dy->ld;
     p.tiles_x = (p.w + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
     p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;
-    long gx = p.ntiles < 256 ? p.ntiles : 256;
-    const long cap = ws_floats / (9L * (1024 + 32));
-    if (cap < 1) return sa ? ISA_ENOMEM : ISA_EINVAL;
-    if (gx > cap) gx = cap;
+    long gx;                                       // one workgroup per CU; nine tap slabs each; no statistic groups
+    if (int rc = slab_plan(sa, &ws, ws_floats, p.ntiles < 256 ? p.ntiles : 256, 9L * (1024 + 32), 1, &gx)) return rc;
+    p.ws = ws;
     const size_t tiles = (size_t)HALO * WS_ + (size_t)TH * TW * WS_, redb = (9 * 1024 + 32) * 4;
     const size_t lds = tiles > redb ? tiles : redb;
     hipLaunchKernelGGL(conv3x3_wgrad_tiled_kernel, dim3((unsigned)gx), dim3(256), lds, s, p);

@@ -18,9 +18,6 @@
 #include "common.hpp"
 #include "tr_lds.hpp"
 
-int wgrad_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int tn, int tk, int N, int cin, int taps,
-                             isa_slab_arena* sa, hipStream_t s);
-
 namespace {
 
 struct PwParams {
@@ -485,14 +482,9 @@ int launch_inst(PwParams& p, const float* bias, float* dbias, long ws_floats, is
     constexpr size_t wkeep = (REC && TN * TK == 4) ? (size_t)TK * 32 * (TN * 32 + 8) * 2 : 0;     // WLDS: W stays behind the constants
     constexpr size_t lds = slab + wkeep > redb ? slab + wkeep : redb;
     const long nchunks = (p.M + 31) / 32;
-    const long slabf = (long)TN * TK * 1024 + TN * 32;
-    long gx = (nchunks + 3) / 4 * p.G;
-    if (gx > 256 * 2) gx = 256 * 2;                                  // 2 resident workgroups per CU; fewer slabs to reduce
-    if (int rc = defer_ws(sa, &p.ws, &ws_floats)) return rc;
-    const long ws_cap = ws_floats / slabf;
-    if (ws_cap < p.G) return sa ? ISA_ENOMEM : ISA_EINVAL;
-    if (gx > ws_cap) gx = ws_cap;
-    gx = group_grid(gx, p.G);
+    long want = (nchunks + 3) / 4 * p.G, gx;
+    if (want > 256 * 2) want = 256 * 2;                              // 2 resident workgroups per CU; fewer slabs to reduce
+    if (int rc = slab_plan(sa, &p.ws, ws_floats, want, (long)TN * TK * 1024 + TN * 32, p.G, &gx)) return rc;
     if (int rc = fin_standalone(xfin, p.K, xfin_groups, s)) return rc;      // every check has passed
     constexpr int XM = XMODE | (BIAS ? PW_BIAS : 0);
     PwParams q = p;
@@ -505,14 +497,15 @@ int launch_inst(PwParams& p, const float* bias, float* dbias, long ws_floats, is
 
 template <int TN, int TK, bool BIAS>
 int launch_tile(PwParams& p, const float* bias, float* dbias, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
-    const bool y6 = p.yact == ISA_ACT_RELU6, y0 = p.yact == ISA_ACT_NONE;
-#define PW_X(YA, RC) (xmode == 0 ? launch_inst<TN, TK, YA, 0, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s) \
-                    : xmode == 1 ? launch_inst<TN, TK, YA, 1, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s) \
-                                 : launch_inst<TN, TK, YA, 2, RC, BIAS>(p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s))
-    if (y6) return p.y ? PW_X(ISA_ACT_RELU6, false) : PW_X(ISA_ACT_RELU6, true);
-    if (y0) return p.y ? PW_X(ISA_ACT_NONE, false) : PW_X(ISA_ACT_NONE, true);
-    return PW_X(ACT_RT, false);                                   // a null y was refused by the entry point
-#undef PW_X
+    // REC (y == NULL, recomputed): only the two compile-time activations have that form; the entry point refused the rest
+    return by_int<ISA_ACT_RELU6, ISA_ACT_NONE, ACT_RT>(p.yact, [&](auto ya) { return by_int<0, 1, 2>(xmode, [&](auto xm) {
+        auto go = [&](auto rec) {
+            return launch_inst<TN, TK, decltype(ya)::value, decltype(xm)::value, decltype(rec)::value, BIAS>(
+                p, bias, dbias, ws_floats, sa, xfin, xfin_groups, s);
+        };
+        if constexpr (decltype(ya)::value == ACT_RT) return go(std::false_type{});
+        else return by_flag(!p.y, go);
+    }); });
 }
 
 }  // namespace
@@ -531,7 +524,7 @@ extern "C" int isa_conv1x1_bias_bn_backward(const isa_tensor* g, const isa_tenso
     if (!tensor_ok(g, 8) || (y && !tensor_ok(y, 8)) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
     if (!fin_valid(xpro)) return ISA_EINVAL;      // a pending finalize (no in-kernel form here) runs after the last check
     if (g->dtype != ISA_BF16 || (y && y->dtype != ISA_BF16) || x->dtype != ISA_BF16 || dx->dtype != ISA_BF16) return ISA_EINVAL;
-    if (!ybn || !ybn->scale || !ybn->shift || !ybn->mean || !ybn->invstd || !ybn->red || !(ybn->count > 0)) return ISA_EINVAL;
+    if (!bn_bwd_ok(ybn) || !xbn_ok(xbn)) return ISA_EINVAL;
     if (!w || !dw || (!ws && !defer)) return ISA_EINVAL;
     // y == NULL: recomputed in the kernel, which has that form for the two compile-time activations only
     if (!y && ybn->act != ISA_ACT_RELU6 && ybn->act != ISA_ACT_NONE) return ISA_EINVAL;
@@ -543,34 +536,23 @@ extern "C" int isa_conv1x1_bias_bn_backward(const isa_tensor* g, const isa_tenso
         if (t && (t->n != g->n || t->h != g->h || t->w != g->w)) return ISA_EINVAL;
     const ProDev xp = make_pro(xpro);
     if (xp.bscale) return ISA_EINVAL;
-    if (xbn && (!xbn->mean || !xbn->invstd || !xbn->out_red)) return ISA_EINVAL;
+    if (addend && !addend_ok(addend, g, K)) return ISA_EINVAL;
     PwParams p{};
     p.g = (const bf16_t*)g->data; p.y = y ? (const bf16_t*)y->data : nullptr; p.x = (const bf16_t*)x->data; p.dx = (bf16_t*)dx->data;
     p.w = w; p.dw = dw; p.N = N; p.K = K; p.ldg = g->ld; p.ldy = y ? y->ld : 0; p.ldx = x->ld; p.lddx = dx->ld;
-    p.G = tensor_groups(g);                                       // BN(y) constants and sums are per statistic group
-    if (g->n % p.G) return ISA_EINVAL;
+    p.G = stat_groups(g, true);                                   // BN(y) constants and sums are per statistic group
+    if (!p.G) return ISA_EINVAL;
     p.M = (long)(g->n / p.G) * g->h * g->w;
-    p.ysc = ybn->scale; p.ysh = ybn->shift; p.ymu = ybn->mean; p.yis = ybn->invstd; p.yred = ybn->red;
-    p.ycnt_inv = 1.f / ybn->count; p.yact = ybn->act; p.ydgamma = ybn->dgamma; p.ydbeta = ybn->dbeta;
-    p.xsc = xp.scale; p.xsh = xp.shift; p.xact = xp.act;
-    p.xmu = xbn ? xbn->mean : nullptr; p.xis = xbn ? xbn->invstd : nullptr; p.xred = xbn ? xbn->out_red : nullptr;
+    set_bn_bwd(p, ybn, xp, xbn);
     p.accumulate = accumulate; p.ws = ws;
-    if (addend) {
-        if (!tensor_ok(addend, 8) || addend->dtype != ISA_BF16 || addend->c != K || addend->n != g->n || addend->h != g->h ||
-            addend->w != g->w) return ISA_EINVAL;
-        p.addend = (const bf16_t*)addend->data; p.lda = addend->ld;
-    }
-    int xmode = 0;
-    if (!pro_trivial(xp) || xbn) xmode = (xbn && xp.act == ISA_ACT_RELU6) ? 1 : 2;
+    if (addend) { p.addend = (const bf16_t*)addend->data; p.lda = addend->ld; }
+    const int xmode = fused_xmode(xp, xbn);
     hipStream_t s = as_stream(stream);
     const int tn = (N + 31) / 32, tk = (K + 31) / 32;
-#define PW_T(TN_, TK_) (bias ? launch_tile<TN_, TK_, true>(p, bias, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), s) \
-                             : launch_tile<TN_, TK_, false>(p, bias, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), s))
-    if (tn == 1 && tk == 1) return PW_T(1, 1);
-    if (tn == 1 && tk == 2) return PW_T(1, 2);
-    if (tn == 2 && tk == 1) return PW_T(2, 1);
-    return PW_T(2, 2);
-#undef PW_T
+    return by_flag(bias != nullptr, [&](auto b) { return by_int<1, 2>(tn, [&](auto n) { return by_int<1, 2>(tk, [&](auto k) {
+        return launch_tile<decltype(n)::value, decltype(k)::value, decltype(b)::value>(p, bias, dbias, xmode, ws_floats, defer, xpro,
+                                                                                        tensor_groups(x), s);
+    }); }); });
 }
 
 extern "C" int isa_conv1x1_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,

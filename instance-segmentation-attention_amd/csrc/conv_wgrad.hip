@@ -317,10 +317,33 @@ __global__ __launch_bounds__(256) void wgrad_fold_kernel(FoldChunk ch) {
     }
 }
 
+// the immediate fold of depthwise tile slabs: grid = (channel blocks, d.rsplit)
+__global__ __launch_bounds__(256) void dw_reduce_kernel(FoldDesc d) {
+    fold_depthwise(d.ws, d.gx, d.gy, d.tk, d.N, d.ksrc, d.dw, d.dbias, blockIdx.x, blockIdx.y, d.rsplit);
+}
+
 constexpr long DEFER_MIN_FLOATS = 16L << 20;       // an arena with less than this left refuses the call (ISA_ENOMEM)
+
+// The two kinds of fold, each described in one place (rsplit, first_block and blocks belong to whoever runs the fold)
+static FoldDesc fragment_fold(const WgParams& p, int gx, int gy, int tn, int tk) {
+    FoldDesc d{};
+    d.ws = p.ws; d.dw = p.dw; d.dbias = p.dbias; d.kmap = p.kmap;
+    d.kind = 0; d.gx = gx; d.gy = gy; d.taps = p.taps; d.groups_k = p.groups_k; d.tn = tn; d.tk = tk;
+    d.N = p.N; d.cin = p.cin; d.ksrc = p.ksrc; d.out_mode = p.out_mode;
+    return d;
+}
+static FoldDesc depthwise_fold(float* ws, float* dw, float* dbias, int gx, int ncb, int cb, int C, int csrc) {
+    FoldDesc d{};
+    d.ws = ws; d.dw = dw; d.dbias = dbias;
+    d.kind = 1; d.gx = gx; d.gy = ncb; d.taps = 9; d.groups_k = 1; d.tk = cb;      // tk: the channel block's width
+    d.N = C; d.ksrc = csrc;
+    return d;
+}
 
 static int launch_reduce(const WgParams& p, int gx, int gy, int tn, int tk, hipStream_t s) {
     const int slabf = tn * tk * 1024 + tn * 32;
+    const FoldDesc d = fragment_fold(p, gx, gy, tn, tk);
+    if (defer_push(p.sa, d, (long)gx * gy * p.taps * slabf)) return ISA_OK;
     // enough splits for >= ~512 workgroups (a 512-slab reduce of one tile group ran as 144), at most 64 adders per
     // address and never more splits than slabs
     const long base_blocks = (long)cdiv(slabf, 256) * gy * p.taps;
@@ -328,11 +351,7 @@ static int launch_reduce(const WgParams& p, int gx, int gy, int tn, int tk, hipS
     if (rsplit > 64) rsplit = 64;
     if (rsplit > gx) rsplit = gx;
     if (rsplit < 1) rsplit = 1;
-    if (p.sa && p.sa->from_arena) {
-        FoldDesc d{p.ws, p.dw, p.dbias, p.kmap, 0, gx, gy, p.taps, p.groups_k, tn, tk, p.N, p.cin, p.ksrc, p.out_mode, 0, 0, 0};
-        if (defer_push(p.sa, d, (long)gx * gy * p.taps * slabf)) return ISA_OK;
-    }
-    WgReduce q{p.ws, p.dw, p.dbias, p.kmap, gx, gy, p.taps, p.groups_k, tn, tk, p.N, p.cin, p.ksrc, p.out_mode, rsplit};
+    WgReduce q{d.ws, d.dw, d.dbias, d.kmap, d.gx, d.gy, d.taps, d.groups_k, d.tn, d.tk, d.N, d.cin, d.ksrc, d.out_mode, rsplit};
     dim3 grid(cdiv(slabf, 256), gy, p.taps * rsplit);
     hipLaunchKernelGGL(wgrad_reduce_kernel, grid, dim3(256), 0, s, q);
     return launch_status();
@@ -557,6 +576,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgParams p) {
     PHASE_FLUSH(phase_buf);
 }
 
+// The region and the grid of the two launchers below: split-M over `nchunks` wave-chunks, four per workgroup, at most
+// two resident workgroups per CU over the (gy, taps) grid; one slab of `slabf` floats per workgroup
+static int wg_plan(WgParams& p, long nchunks, long slabf, int gy, long* gx) {
+    long cap = (256L * 2) / ((long)gy * p.taps);
+    if (cap < 1) cap = 1;
+    const long want = (nchunks + 3) / 4 * p.G;
+    return slab_plan(p.sa, &p.ws, p.ws_floats, want < cap ? want : cap, slabf * gy * p.taps, p.G, gx);
+}
+
 template <int TN, int TK>
 int launch_wg_bf16(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
     constexpr int SN = TrStride<TN * 32>::bytes, SK = TrStride<TK * 32>::bytes;
@@ -564,26 +592,17 @@ int launch_wg_bf16(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s)
     const size_t redb = ((size_t)fold_part_floats<TN, TK>() + 4 * TN * 32) * 4;     // four parked partials + dy column sums
     const size_t lds = slab > redb ? slab : redb;
     const int gy = groups_n * p.groups_k;
-    const long nchunks = (p.M + 31) / 32;
-    const long slabf = (long)TN * TK * 1024 + TN * 32;
-    long want = (nchunks + 3) / 4 * p.G;
-    long cap = (256L * 2) / ((long)gy * p.taps);
-    if (int rc = defer_ws(p.sa, &p.ws, &p.ws_floats)) return rc;
-    const long ws_cap = p.ws_floats / (slabf * gy * p.taps);
-    if (ws_cap < p.G) return p.sa ? ISA_ENOMEM : ISA_EINVAL;   // workspace too small for even one slab set per group
-    if (cap > ws_cap) cap = ws_cap;
-    if (cap < 1) cap = 1;
-    const int gx = (int)group_grid(want < cap ? want : cap, p.G);
-    dim3 grid(gx, gy, p.taps);
+    long gx;
+    if (int rc = wg_plan(p, (p.M + 31) / 32, (long)TN * TK * 1024 + TN * 32, gy, &gx)) return rc;
+    dim3 grid((unsigned)gx, gy, p.taps);
     if (int rc = fin_standalone(fin, p.cin, p.G, s)) return rc;        // every check has passed
     if (p.pro.act == ISA_ACT_RELU6) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_RELU6>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_LEAKY && TN == 1 && TK == 1) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_LEAKY>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_NONE) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ISA_ACT_NONE>), grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TN, TK, ACT_RT>), grid, dim3(256), lds, s, p);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
-    return launch_reduce(p, gx, gy, TN, TK, s);
+    return launch_reduce(p, (int)gx, gy, TN, TK, s);
 }
-
 
 template <typename T, int TN, int TK>
 int launch_wg(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
@@ -592,22 +611,27 @@ int launch_wg(WgParams& p, int groups_n, const isa_pro* fin, hipStream_t s) {
     const size_t redb = ((size_t)TN * TK * 16 * 64 + TN * 32) * 4;
     const size_t lds = slab > redb ? slab : redb;
     const int gy = groups_n * p.groups_k;
-    const long slabf = (long)TN * TK * 1024 + TN * 32;
-    long want = (p.nchunks + 3) / 4 * p.G;
-    long cap = (256L * 2) / ((long)gy * p.taps);
-    if (int rc = defer_ws(p.sa, &p.ws, &p.ws_floats)) return rc;
-    const long ws_cap = p.ws_floats / (slabf * gy * p.taps);
-    if (ws_cap < p.G) return p.sa ? ISA_ENOMEM : ISA_EINVAL;
-    if (cap > ws_cap) cap = ws_cap;
-    if (cap < 1) cap = 1;
-    const int gx = (int)group_grid(want < cap ? want : cap, p.G);
-    dim3 grid(gx, gy, p.taps);
+    long gx;
+    if (int rc = wg_plan(p, p.nchunks, (long)TN * TK * 1024 + TN * 32, gy, &gx)) return rc;
+    dim3 grid((unsigned)gx, gy, p.taps);
     if (int rc = fin_standalone(fin, p.cin, p.G, s)) return rc;        // every check has passed
     if (p.pro.act == ISA_ACT_RELU6) hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ISA_ACT_RELU6>), grid, dim3(256), lds, s, p);
     else if (p.pro.act == ISA_ACT_NONE) hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ISA_ACT_NONE>), grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL((conv_wgrad_kernel<T, TN, TK, ACT_RT>), grid, dim3(256), lds, s, p);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
-    return launch_reduce(p, gx, gy, TN, TK, s);
+    return launch_reduce(p, (int)gx, gy, TN, TK, s);
+}
+
+// the (tn, tk) accumulator tiles per wave that have kernels: f(integral_constant tn, integral_constant tk)
+template <typename F> int by_tile(int tn, int tk, F&& f) {
+    using one = std::integral_constant<int, 1>; using two = std::integral_constant<int, 2>; using four = std::integral_constant<int, 4>;
+    if (tn == 1 && tk == 1) return f(one{}, one{});
+    if (tn == 1 && tk == 2) return f(one{}, two{});
+    if (tn == 2 && tk == 1) return f(two{}, one{});
+    if (tn == 2 && tk == 2) return f(two{}, two{});
+    if (tn == 1 && tk == 4) return f(one{}, four{});
+    if (tn == 4 && tk == 1) return f(four{}, one{});
+    return ISA_EINVAL;
 }
 
 template <typename T>
@@ -619,22 +643,12 @@ int dispatch_wg(WgParams& p, const isa_pro* fin, hipStream_t s) {
     else { tn = 2; tk = 2; }
     const int groups_n = (nt + tn - 1) / tn;
     p.groups_k = (kt + tk - 1) / tk;
-    if constexpr (sizeof(T) == 2) {
-        if (tn == 1 && tk == 1) return launch_wg_bf16<1, 1>(p, groups_n, fin, s);
-        if (tn == 1 && tk == 2) return launch_wg_bf16<1, 2>(p, groups_n, fin, s);
-        if (tn == 2 && tk == 1) return launch_wg_bf16<2, 1>(p, groups_n, fin, s);
-        if (tn == 2 && tk == 2) return launch_wg_bf16<2, 2>(p, groups_n, fin, s);
-        if (tn == 1 && tk == 4) return launch_wg_bf16<1, 4>(p, groups_n, fin, s);
-        if (tn == 4 && tk == 1) return launch_wg_bf16<4, 1>(p, groups_n, fin, s);
-        return ISA_EINVAL;
-    }
-    if (tn == 1 && tk == 1) return launch_wg<T, 1, 1>(p, groups_n, fin, s);
-    if (tn == 1 && tk == 2) return launch_wg<T, 1, 2>(p, groups_n, fin, s);
-    if (tn == 2 && tk == 1) return launch_wg<T, 2, 1>(p, groups_n, fin, s);
-    if (tn == 2 && tk == 2) return launch_wg<T, 2, 2>(p, groups_n, fin, s);
-    if (tn == 1 && tk == 4) return launch_wg<T, 1, 4>(p, groups_n, fin, s);
-    if (tn == 4 && tk == 1) return launch_wg<T, 4, 1>(p, groups_n, fin, s);
-    return ISA_EINVAL;
+    return by_tile(tn, tk, [&](auto a, auto b) {
+        constexpr int TN = decltype(a)::value, TK = decltype(b)::value;
+        if constexpr (sizeof(T) == 2) return launch_wg_bf16<TN, TK>(p, groups_n, fin, s);
+        // no `else`: bf16 storage keeps its instantiations of the fp32-MFMA kernel, as before (never launched)
+        return launch_wg<T, TN, TK>(p, groups_n, fin, s);
+    });
 }
 
 }  // namespace
@@ -663,18 +677,14 @@ extern "C" int isa_conv_wgrad(const isa_tensor* x, const isa_pro* pro, const isa
         if (dy->h != x->h || dy->w != x->w || dy->n != x->n) return ISA_EINVAL;
         p.taps = in_mode == ISA_IN_3X3 ? 9 : 1; p.N = dy->c;
     }
-    p.G = 1;
-    const int G = tensor_groups(x);
-    if (G > 1 && (p.pro.scale || p.pro.shift)) {            // only the per-channel prologue constants differ by group
-        if (in_mode != ISA_IN_1X1 || out_mode != ISA_OUT_PLAIN || x->n % G) return ISA_EINVAL;
-        p.G = G; p.M /= G;
-    }
+    p.G = stat_groups(x, p.pro.scale || p.pro.shift);       // only the per-channel prologue constants differ by group
+    if (!p.G || (p.G > 1 && (in_mode != ISA_IN_1X1 || out_mode != ISA_OUT_PLAIN))) return ISA_EINVAL;
+    p.M /= p.G;
     p.nchunks = (p.M + PM - 1) / PM;
     if (in_mode == ISA_IN_3X3 && out_mode == ISA_OUT_PLAIN && x->dtype == ISA_BF16 && pro_trivial(p.pro) && !kmap &&
         x->c <= 32 && dy->c <= 32 && p.ksrc == x->c)
         return conv3x3_wgrad_tiled_launch(x, dy, dw, dbias, ws, ws_floats, defer, as_stream(stream));
-    if (x->dtype == ISA_BF16) return dispatch_wg<bf16_t>(p, pro, as_stream(stream));
-    return dispatch_wg<float>(p, pro, as_stream(stream));
+    return by_dtype(x->dtype, [&](auto t) { return dispatch_wg<decltype(t)>(p, pro, as_stream(stream)); });
 }
 
 // second-stage reduction for other translation units that write conv_wgrad-format slabs (conv_fused_bwd.hip,
@@ -686,6 +696,16 @@ int wgrad_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int tn,
     p.ws = ws; p.dw = dw; p.dbias = dbias; p.kmap = nullptr; p.taps = taps; p.groups_k = 1; p.N = N; p.cin = cin;
     p.ksrc = cin; p.out_mode = ISA_OUT_PLAIN;
     return launch_reduce(p, gx, 1, tn, tk, s);
+}
+
+// its depthwise sibling (dwconv.hip): gx tile slabs of ncb channel blocks, cb channels wide; csrc rows of dW exist
+int dw_slab_reduce_launch(float* ws, float* dw, float* dbias, int gx, int ncb, int cb, int C, int csrc, isa_slab_arena* sa,
+                          hipStream_t s) {
+    FoldDesc d = depthwise_fold(ws, dw, dbias, gx, ncb, cb, C, csrc);
+    if (defer_push(sa, d, (long)gx * ncb * 10 * cb)) return ISA_OK;
+    d.rsplit = 16;
+    hipLaunchKernelGGL(dw_reduce_kernel, dim3(ncb, d.rsplit), dim3(256), 0, s, d);
+    return launch_status();
 }
 
 // ---- deferred folds ---------------------------------------------------------------------------------

@@ -595,22 +595,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = tid; i < 10 * CB; i += 256) slab[i] = red[i];
 }
 
-constexpr int DW2_RSPLIT = 16;
-// dw[c][t] += sum_b slab[b][cb][t*CB+cc]; dbias[c] += slab[...][9*CB+cc]
-__global__ __launch_bounds__(256) void dw2_wgrad_reduce_kernel(const float* ws, int nblk, int ncb, int C, int csrc, float* dw, float* dbias) {
-    const int cb = blockIdx.x, split = blockIdx.y;
-    const int per = (nblk + DW2_RSPLIT - 1) / DW2_RSPLIT;
-    const int b0 = split * per, b1 = min(nblk, b0 + per);
-    if (b0 >= b1) return;
-    for (int i = threadIdx.x; i < 10 * CB; i += 256) {
-        float s = 0.f;
-#pragma unroll 8
-        for (int b = b0; b < b1; ++b) s += ws[((long)b * ncb + cb) * 10 * CB + i];
-        const int tp = i / CB, c = cb * CB + (i - tp * CB);
-        if (c >= csrc || c >= C) continue;
-        if (tp < 9) atomicAdd(dw + c * 9 + tp, s);
-        else if (dbias) atomicAdd(dbias + c, s);
-    }
+// the tile grid of a launch (p.n: images per statistic group) and the workgroups in x a persistent kernel wants for it:
+// `resident` over the chip, shared among the ncb channel blocks, never more than there are tiles
+template <typename P> void set_tiles(P& p) {
+    p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
+    p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;
+}
+template <typename P> long want_grid(const P& p, long resident, int ncb) {
+    const long gx = resident / ncb < 1 ? 1 : resident / ncb;
+    return gx > p.ntiles * p.G ? p.ntiles * p.G : gx;
 }
 
 template <typename T, bool HAS_PRO, int ACT, bool ACC = false>
@@ -630,15 +623,11 @@ int launch_fwd2_inst(Dw2Params& p, dim3 grid, hipStream_t s) {
 // The data-gradient entry point (no prologue) is the only caller that may accumulate into the old output
 template <typename T>
 int launch_fwd2(Dw2Params& p, bool has_pro, hipStream_t s) {
-    p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
-    p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;            // p.n: images per statistic group
+    set_tiles(p);
     if (p.ntiles * p.G >= (1L << 31)) return ISA_EINVAL;
     const int ncb = (p.c + CB - 1) / CB;
     // persistent: bf16 = one 512-thread double-buffered workgroup per CU, f32 = three 256-thread ones
-    long gx = (256L * (sizeof(T) == 2 ? 1 : 3)) / ncb;
-    if (gx < 1) gx = 1;
-    if (gx > p.ntiles * p.G) gx = p.ntiles * p.G;
-    gx = group_grid(gx, p.G);
+    const long gx = group_grid(want_grid(p, 256L * (sizeof(T) == 2 ? 1 : 3), ncb), p.G);
     dim3 grid((unsigned)gx, ncb);
     if (p.accumulate) return has_pro ? ISA_EINVAL : launch_fwd2_inst<T, false, ISA_ACT_NONE, true>(p, grid, s);
     if (has_pro && p.pro.act == ISA_ACT_RELU6) return launch_fwd2_inst<T, true, ISA_ACT_RELU6>(p, grid, s);
@@ -648,17 +637,10 @@ int launch_fwd2(Dw2Params& p, bool has_pro, hipStream_t s) {
 
 template <typename T>
 int launch_wg2(Dw2Params& p, bool has_pro, long ws_floats, isa_slab_arena* sa, const isa_pro* fin, hipStream_t s) {
-    p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
-    p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;
+    set_tiles(p);
     const int ncb = (p.c + CB - 1) / CB;
-    long gx = (256L * 2) / ncb;          // 2 resident workgroups per CU
-    if (gx < 1) gx = 1;
-    if (gx > p.ntiles * p.G) gx = p.ntiles * p.G;
-    if (int rc = defer_ws(sa, &p.ws, &ws_floats)) return rc;
-    const long ws_cap = ws_floats / (10L * CB * ncb);
-    if (ws_cap < p.G) return sa ? ISA_ENOMEM : ISA_EINVAL;
-    if (gx > ws_cap) gx = ws_cap;
-    gx = group_grid(gx, p.G);
+    long gx;                             // 2 resident workgroups per CU
+    if (int rc = slab_plan(sa, &p.ws, ws_floats, want_grid(p, 256L * 2, ncb), 10L * CB * ncb, p.G, &gx)) return rc;
     dim3 grid((unsigned)gx, ncb);
     const size_t lds = ((size_t)HALO * PS + 10 * CB) * 4;
     if (int rc = fin_standalone(fin, p.c, p.G, s)) return rc;            // every check has passed
@@ -666,12 +648,8 @@ int launch_wg2(Dw2Params& p, bool has_pro, long ws_floats, isa_slab_arena* sa, c
     else if (has_pro) hipLaunchKernelGGL((dw2_wgrad_kernel<T, true, ACT_RT>), grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL((dw2_wgrad_kernel<T, false, ISA_ACT_NONE>), grid, dim3(256), lds, s, p);
     if (launch_status() != ISA_OK) return ISA_ELAUNCH;
-    if (defer_push(sa, FoldDesc{p.ws, (float*)p.y, (float*)p.bias, nullptr, 1, (int)gx, ncb, 9, 1, 0, CB, p.c, 0, p.csrc, 0, 0, 0, 0},
-                   gx * ncb * 10L * CB)) return ISA_OK;
-    hipLaunchKernelGGL(dw2_wgrad_reduce_kernel, dim3(ncb, DW2_RSPLIT), dim3(256), 0, s, p.ws, (int)gx, ncb, p.c, p.csrc, (float*)p.y, (float*)p.bias);
-    return launch_status();
+    return dw_slab_reduce_launch(p.ws, (float*)p.y, (float*)p.bias, (int)gx, ncb, CB, p.c, p.csrc, sa, s);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // Fused backward of  x --dw3x3--> y --BN(train)+act--> ...   (InvertedResidual / InvertedV1Residual middle):
@@ -1198,38 +1176,23 @@ int launch_fused_inst(FusedParams& p, dim3 grid, hipStream_t s) {
         configured = true;
     }
     hipLaunchKernelGGL(kern, grid, dim3(DB ? 512 : 256), lds, s, p);
-    return ISA_OK;
+    return launch_status();
 }
 
 template <typename T>
 int launch_fused(FusedParams& p, float* dbias, int xmode, long ws_floats, isa_slab_arena* sa, const isa_pro* xfin, int xfin_groups, hipStream_t s) {
-    p.tiles_x = (p.w_ + TW - 1) / TW; p.tiles_y = (p.h + TH - 1) / TH;
-    p.ntiles = (long)p.n * p.tiles_x * p.tiles_y;              // p.n: images per statistic group
+    set_tiles(p);
     const int ncb = (p.c + CB - 1) / CB;
-    const int per_cu = 1;                                        // LDS: 156 KB (bf16, double-buffered) / 100 KB (f32)
-    long gx = (256L * per_cu) / ncb;
-    if (gx < 1) gx = 1;
-    if (gx > p.ntiles * p.G) gx = p.ntiles * p.G;
-    if (int rc = defer_ws(sa, &p.ws, &ws_floats)) return rc;
-    const long ws_cap = ws_floats / (10L * CB * ncb);
-    if (ws_cap < p.G) return sa ? ISA_ENOMEM : ISA_EINVAL;
-    if (gx > ws_cap) gx = ws_cap;
-    gx = group_grid(gx, p.G);
+    long gx;                             // 1 resident workgroup per CU.  LDS: 156 KB (bf16, double-buffered) / 100 KB (f32)
+    if (int rc = slab_plan(sa, &p.ws, ws_floats, want_grid(p, 256L, ncb), 10L * CB * ncb, p.G, &gx)) return rc;
     dim3 grid((unsigned)gx, ncb);
-    int rc = fin_standalone(xfin, p.c, xfin_groups, s);                 // every check has passed
+    if (int rc = fin_standalone(xfin, p.c, xfin_groups, s)) return rc;         // every check has passed
+    const int rc = by_flag(dbias != nullptr, [&](auto b) { return by_int<ISA_ACT_RELU6, ACT_RT>(p.yact, [&](auto ya) {
+        return by_int<0, 1, 2>(xmode, [&](auto xm) {
+            return launch_fused_inst<T, decltype(ya)::value, decltype(xm)::value, decltype(b)::value>(p, grid, s);
+        }); }); });
     if (rc != ISA_OK) return rc;
-    const bool y6 = p.yact == ISA_ACT_RELU6;
-#define DW_X(XM) (dbias ? (y6 ? launch_fused_inst<T, ISA_ACT_RELU6, XM, true>(p, grid, s) : launch_fused_inst<T, ACT_RT, XM, true>(p, grid, s)) \
-                        : (y6 ? launch_fused_inst<T, ISA_ACT_RELU6, XM, false>(p, grid, s) : launch_fused_inst<T, ACT_RT, XM, false>(p, grid, s)))
-    if (xmode == 0) rc = DW_X(0);
-    else if (xmode == 1) rc = DW_X(1);
-    else rc = DW_X(2);
-#undef DW_X
-    if (rc != ISA_OK) return rc;
-    if (defer_push(sa, FoldDesc{p.ws, p.dw, dbias, nullptr, 1, (int)gx, ncb, 9, 1, 0, CB, p.c, 0, p.csrc, 0, 0, 0, 0},
-                   gx * ncb * 10L * CB)) return ISA_OK;
-    hipLaunchKernelGGL(dw2_wgrad_reduce_kernel, dim3(ncb, DW2_RSPLIT), dim3(256), 0, s, p.ws, (int)gx, ncb, p.c, p.csrc, p.dw, dbias);
-    return launch_status();
+    return dw_slab_reduce_launch(p.ws, p.dw, dbias, (int)gx, ncb, CB, p.c, p.csrc, sa, s);
 }
 
 // forward, and the data gradient as the forward of dy
@@ -1242,18 +1205,14 @@ int dw_forward(const isa_tensor* x, const isa_pro* pro, const void* w, const flo
     p.n = x->n; p.h = x->h; p.w_ = x->w; p.c = x->c; p.ldx = x->ld; p.ldy = y->ld; p.wld = ((x->c + 7) / 8) * 8;
     p.pro = make_pro(pro); p.stats = stats; p.accumulate = accumulate;
     const bool has_pro = !pro_trivial(p.pro);
-    p.G = 1;
-    const int G = tensor_groups(x);
-    if (G > 1 && (stats || p.pro.scale || p.pro.shift)) {
-        if (x->n % G || tensor_groups(y) != G) return ISA_EINVAL;
-        p.G = G; p.n = x->n / G;
-    }
+    p.G = stat_groups(x, stats || p.pro.scale || p.pro.shift);
+    if (!p.G || (p.G > 1 && tensor_groups(y) != p.G)) return ISA_EINVAL;
+    p.n = x->n / p.G;
     if (pro && pro->fin) {
         if (!fin_valid(pro)) return ISA_EINVAL;
         p.fin = make_fin(pro);
     }
-    if (x->dtype == ISA_BF16) return launch_fwd2<bf16_t>(p, has_pro, as_stream(stream));
-    return launch_fwd2<float>(p, has_pro, as_stream(stream));
+    return by_dtype(x->dtype, [&](auto t) { return launch_fwd2<decltype(t)>(p, has_pro, as_stream(stream)); });
 }
 
 }  // namespace
@@ -1281,14 +1240,10 @@ extern "C" int isa_dwconv3x3_wgrad(const isa_tensor* x, const isa_pro* pro, cons
     p.n = x->n; p.h = x->h; p.w_ = x->w; p.c = x->c; p.ldx = x->ld; p.ldd = dy->ld;
     p.pro = make_pro(pro); p.ws = ws; p.csrc = (csrc > 0 && csrc < x->c) ? csrc : x->c;
     const bool has_pro = !pro_trivial(p.pro);
-    p.G = 1;
-    const int G = tensor_groups(x);
-    if (G > 1 && (p.pro.scale || p.pro.shift)) {
-        if (x->n % G) return ISA_EINVAL;
-        p.G = G; p.n = x->n / G;
-    }
-    if (x->dtype == ISA_BF16) return launch_wg2<bf16_t>(p, has_pro, ws_floats, defer, pro, as_stream(stream));
-    return launch_wg2<float>(p, has_pro, ws_floats, defer, pro, as_stream(stream));
+    p.G = stat_groups(x, p.pro.scale || p.pro.shift);
+    if (!p.G) return ISA_EINVAL;
+    p.n = x->n / p.G;
+    return by_dtype(x->dtype, [&](auto t) { return launch_wg2<decltype(t)>(p, has_pro, ws_floats, defer, pro, as_stream(stream)); });
 }
 
 // Fused BN-apply + depthwise dgrad/wgrad + next BN-reduce; see dw_bn_bwd_kernel.  dbias (optional): the conv's bias gradient
@@ -1300,7 +1255,7 @@ extern "C" int isa_dwconv3x3_bias_bn_backward(const isa_tensor* g, const isa_ten
                                               float* dbias) {
     if (!tensor_ok(g, 8) || !tensor_ok(y, 8) || !tensor_ok(x, 8) || !tensor_ok(dx, 8)) return ISA_EINVAL;
     if (!fin_valid(xpro)) return ISA_EINVAL;      // a pending finalize (no in-kernel form here) runs after the last check
-    if (!ybn || !ybn->scale || !ybn->shift || !ybn->mean || !ybn->invstd || !ybn->red || !(ybn->count > 0)) return ISA_EINVAL;
+    if (!bn_bwd_ok(ybn) || !xbn_ok(xbn)) return ISA_EINVAL;
     if (!w_flipped || !dw || (!ws && !defer)) return ISA_EINVAL;
     if (x->c % 8 != 0) return ISA_EINVAL;
     const isa_tensor* ts[3] = {y, x, dx};
@@ -1308,30 +1263,22 @@ extern "C" int isa_dwconv3x3_bias_bn_backward(const isa_tensor* g, const isa_ten
         if (t->n != g->n || t->h != g->h || t->w != g->w || t->c != g->c || t->dtype != g->dtype) return ISA_EINVAL;
     const ProDev xp = make_pro(xpro);
     if (xp.bscale) return ISA_EINVAL;                             // per-image scales are not folded here
-    if (xbn && (!xbn->mean || !xbn->invstd || !xbn->out_red)) return ISA_EINVAL;
+    // an addend only next to a plain-tensor x
+    if (addend && (!addend_ok(addend, g, g->c) || !pro_trivial(xp) || xbn)) return ISA_EINVAL;
     FusedParams p{};
     p.g = g->data; p.y = y->data; p.x = x->data; p.w = w_flipped; p.dx = dx->data;
     p.n = g->n; p.h = g->h; p.w_ = g->w; p.c = g->c; p.ldg = g->ld; p.ldy = y->ld; p.ldx = x->ld; p.lddx = dx->ld;
     p.wld = ((g->c + 7) / 8) * 8;
-    p.ysc = ybn->scale; p.ysh = ybn->shift; p.ymu = ybn->mean; p.yis = ybn->invstd; p.yred = ybn->red;
-    p.ycnt_inv = 1.f / ybn->count; p.yact = ybn->act; p.ydgamma = ybn->dgamma; p.ydbeta = ybn->dbeta;
-    p.xsc = xp.scale; p.xsh = xp.shift; p.xact = xp.act;
-    p.xmu = xbn ? xbn->mean : nullptr; p.xis = xbn ? xbn->invstd : nullptr; p.xred = xbn ? xbn->out_red : nullptr;
+    set_bn_bwd(p, ybn, xp, xbn);
     p.accumulate = accumulate; p.ws = ws; p.dw = dw;
-    if (addend) {
-        if (!tensor_ok(addend, 8) || addend->dtype != g->dtype || addend->c != g->c || addend->n != g->n || addend->h != g->h ||
-            addend->w != g->w) return ISA_EINVAL;
-        p.addend = addend->data; p.lda = addend->ld;
-        if (!pro_trivial(make_pro(xpro)) || xbn) return ISA_EINVAL;      // only for a plain-tensor x
-    }
+    if (addend) { p.addend = addend->data; p.lda = addend->ld; }
     p.csrc = (csrc > 0 && csrc < g->c) ? csrc : g->c;
-    p.G = tensor_groups(g);                                          // BN(y) constants and sums are per statistic group
-    if (g->n % p.G) return ISA_EINVAL;
+    p.G = stat_groups(g, true);                                      // BN(y) constants and sums are per statistic group
+    if (!p.G) return ISA_EINVAL;
     p.n = g->n / p.G;
-    int xmode = 0;
-    if (!pro_trivial(xp) || xbn) xmode = (xbn && xp.act == ISA_ACT_RELU6) ? 1 : 2;
-    if (g->dtype == ISA_BF16) return launch_fused<bf16_t>(p, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
-    return launch_fused<float>(p, dbias, xmode, ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
+    return by_dtype(g->dtype, [&](auto t) {
+        return launch_fused<decltype(t)>(p, dbias, fused_xmode(xp, xbn), ws_floats, defer, xpro, tensor_groups(x), as_stream(stream));
+    });
 }
 
 extern "C" int isa_dwconv3x3_bn_backward(const isa_tensor* g, const isa_tensor* y, const isa_bn_bwd* ybn,

@@ -481,7 +481,8 @@ def test_dwconv_fwd_walk(case):
 
 # ------------------------------------------------------------------------------------------------ 4. depthwise weight gradient
 DW_WG = [
-    # dtype, G, k, act: launch_wg2: gx = min(512 / ncb, tiles * G, ws_floats / (10 * 32 * ncb)), group_grid.  c = 64
+    # dtype, G, k, act.  dw2_wgrad_kernel wants min(512 / ncb, tiles * G) workgroups and slab_grid (slab_plan.hpp) caps them
+    # at ws_floats / (10 * 32 * ncb), rounded to a multiple of G.  c = 64
     # (ncb = 2), 3 images of 45x100 per group -> 4 x 6 x 3 = 72 tiles per group.  k = 1: one workgroup, 72 tiles;
     # k = 3: 24; k = 8: 9; k = 9: 8; uncapped: 72 * G workgroups of one tile
     (BF, 1, 1, "relu6"), (BF, 1, 3, "leaky"), (BF, 1, 8, "none"), (BF, 1, 9, "relu6"), (BF, 1, None, "relu6"),
@@ -526,6 +527,37 @@ def test_dwconv_wgrad_walk(dtype, G, k, form):
     tag = "dwwgrad %s G%d k=%s %s" % ("bf16" if dtype == BF else "f32", G, k, form)
     check(tag + " dW", dw, wv.grad, FP32_BOUND)
     check(tag + " db", db, dy.double().sum((0, 2, 3)), FP32_BOUND)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 3, "arena"])
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+def test_dwconv_wgrad_fold_channel_tail(dtype, k):
+    """The second stage (dw_slab_reduce_launch in conv_wgrad.hip: launched at once from a caller workspace, recorded
+    in an arena) where the channel block is not full and dW has fewer rows than x has channels: c = 24 in one 32-wide
+    block, csrc = 21.  One image of 9 x 33 pixels is 2 x 2 tiles; k = 1: one workgroup walks them, k = 3: three slabs to
+    fold.  dW and db are 21 rows followed by guard values that must survive.  FP32_BOUND holds with the margin of the
+    c = 64 cases: worst 1.9e-7 (bf16 dW), the same with the fold kernel this launcher replaced."""
+    L, Act, Engine, ParamStore, Pro = _gpu()
+    lib = L.lib()
+    c, csrc, h, w, guard = 24, 21, 9, 33, 12345.0
+    x = inp(rand(1, c, h, w, seed=44, scale=2.0), dtype)
+    dy = inp(rand(1, c, h, w, seed=45), dtype)
+    xa, da = to_act(Act, x, dtype), to_act(Act, dy, dtype)
+    dw = torch.zeros(csrc * 9 + 64, device="cuda")
+    db = torch.zeros(csrc + 64, device="cuda")
+    dw[csrc * 9:] = guard
+    db[csrc:] = guard
+    set_floats = 10 * CB * ((c + CB - 1) // CB)
+    run_ws_call(L, lambda ws, wsf, sa: lib.isa_dwconv3x3_wgrad(xa.d(), None, da.d(), L.ptr(dw), L.ptr(db), csrc, ws, wsf, sa,
+                                                              L.stream_ptr()),
+                k, set_floats, "isa_dwconv3x3_wgrad")
+    wv = torch.zeros(c, 1, 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x.double(), wv, padding=1, groups=c).backward(dy.double())
+    tag = "dwwgrad tail %s k=%s" % ("bf16" if dtype == BF else "f32", k)
+    check(tag + " dW", dw[:csrc * 9].view(csrc, 1, 3, 3), wv.grad[:csrc], FP32_BOUND)
+    check(tag + " db", db[:csrc], dy.double().sum((0, 2, 3))[:csrc], FP32_BOUND)
+    assert bool((dw[csrc * 9:] == guard).all()) and bool((db[csrc:] == guard).all()), "a row past csrc was written"
 
 
 # ------------------------------------------------------------------------------------------------ 5. fused BN backward
@@ -586,9 +618,9 @@ def xred_ref(L, gx, x, sc, sh, act, mean, invstd, G):
 
 
 FUSED = [
-    # xmode, epi, G, k[, (images per group, h, w)].  launch_fused: gx = min(256 / ncb, tiles * G,
-    # ws_floats / (10 * 32 * ncb)), group_grid; c = 64 (ncb = 2).  Default shape: 3 images of 45x100 per group -> 72
-    # tiles per group (ragged in x and y).  The XCD walk (see DW_FWD) exists only in the bf16 instantiation; the fp32
+    # xmode, epi, G, k[, (images per group, h, w)].  dw_bn_bwd_kernel wants min(256 / ncb, tiles * G) workgroups, slab_grid
+    # caps them at ws_floats / (10 * 32 * ncb), rounded to a multiple of G; c = 64 (ncb = 2).
+    # Default shape: 3 images of 45x100 per group -> 72 tiles per group (ragged in x and y).  The XCD walk (see DW_FWD) exists only in the bf16 instantiation; the fp32
     # one strides from bx.  G = 1: k = 1 -> one workgroup walks 72 tiles; k = 3 -> 24 each; k = 8 -> 9 each (bf16: XCD
     # walk, chunk 9); k = 9 -> 8 each, no XCD walk; uncapped 72 workgroups, one tile each (bf16: XCD walk).
     # G = 2, k = 16 -> 8 per group, 9 tiles each (bf16: XCD walk per group); G = 2, k = 6 -> 3 per group, 24 tiles each;
@@ -675,9 +707,9 @@ def test_dwconv_bn_backward_walk(dtype, xmode, epi, G, k, shape):
 
 
 PW = [
-    # N, K, xmode, epi, G, k.  pw_bn_bwd_kernel (conv_fused_bwd.hip launch_inst): gx = min((chunks + 3) / 4 * G, 512,
-    # ws_floats / slab), group_grid; 2 images of 37x70 per group = 5180 pixels = 162 chunks of 32: k = 1 -> 40-41
-    # chunks per wave; k = 3 -> 13-14; k = 8 -> 5; k = 9 -> 4-5; uncapped 41 * G workgroups (one chunk per wave)
+    # N, K, xmode, epi, G, k.  pw_bn_bwd_kernel (conv_fused_bwd.hip) wants min((chunks + 3) / 4 * G, 512) workgroups, slab_grid
+    # caps them at ws_floats / slab, rounded to a multiple of G.
+    # 2 images of 37x70 per group = 5180 pixels = 162 chunks of 32: k = 1 -> 40-41 chunks per wave; k = 3 -> 13-14; k = 8 -> 5; k = 9 -> 4-5; uncapped 41 * G workgroups (one chunk per wave)
     (32, 32, 0, False, 1, 1), (32, 32, 1, True, 1, 3), (64, 32, 2, False, 1, 8), (32, 64, 1, False, 1, 9),
     (64, 64, 0, True, 1, None), (64, 64, 1, False, 1, "arena"), (32, 64, 2, True, 1, 1),
     (64, 32, 1, False, 2, 8), (32, 32, 0, True, 2, 6), (64, 64, 2, False, 3, 9), (32, 64, 1, True, 3, None),
