@@ -766,6 +766,58 @@ int isa_props_select(const int64_t* acc, int32_t n, int32_t nl, int32_t h, int32
                      int32_t clear_border, int32_t order, int32_t max_objects, uint8_t* table, int32_t* count,
                      int32_t* dropped, void* stream);
 int isa_relabel_u8(const uint8_t* labels, const uint8_t* table, int32_t n, int64_t L, uint8_t* out, void* stream);
+/* ---- tracing instance outlines: polygons, holes, Euler number -----------------------------------------------------------
+ * Both entries check every argument before they launch or write anything (ISA_EINVAL, then ISA_ENOMEM, then ISA_EALIGN),
+ * are asynchronous on `stream`, allocate nothing and never read anything back: the launch count depends on the shape alone
+ * (trace: 2 R + 9 with R = ceil(log4(4 h w)), the pointer-jumping rounds, taken from the edge bound and never from the data;
+ * topology: 1), so a captured hipGraph replays them.  Only integers decide anything and every scattered write goes to a
+ * slot one thread owns: two runs are bit-identical, whatever order workgroups ran in.  n <= 65535.
+ * Definitions.  Pixel (row y, column x) is the unit square with corners (x, y) and (x+1, y+1); y points down.  For a pixel
+ *   of label v != 0 every side whose 4-neighbour holds another value, or lies outside the image, is one directed unit EDGE
+ *   of label v with the pixel on its right: top (x,y)->(x+1,y), direction E = 0; right (x+1,y)->(x+1,y+1), S = 1; bottom
+ *   (x+1,y+1)->(x,y+1), W = 2; left (x,y+1)->(x,y), N = 3.  One pixel alone is the cycle E, S, W, N, clockwise on the
+ *   screen.  The edges of v number the crack perimeter of isa_label_props.  An edge's KEY is
+ *   (y0 * (w + 1) + x0) * 4 + direction, (x0, y0) its start point.
+ *   Successor: an edge of label v and direction d ends at P; of the two pixels ahead of P let R say whether the one on the
+ *   right holds v and L whether the one on the left does.  Connectivity 8: turn left (d - 1) if L, else straight if R,
+ *   else right (d + 1).  Connectivity 4: turn right if not R, else left if L, else straight.  Every edge has exactly one
+ *   successor and one predecessor of its own label; the edges fall into disjoint cycles, and a cycle is a CONTOUR.
+ *   A CORNER EDGE is an edge whose predecessor has another direction.  The vertices of a contour are the start points of
+ *   its corner edges in cycle order, the first one that of the corner edge with the smallest key, the contour's START KEY.
+ *   Twice-area = sum(x_i * y_{i+1} - x_{i+1} * y_i) over the vertices: positive for an outer contour, negative for a hole;
+ *   over the contours of a label it sums to twice the label's pixel count.  The outer contours of v are its connected
+ *   components under the connectivity, its holes the enclosed components of "not v" under the dual one; Euler number =
+ *   outer - holes.
+ * isa_contour_trace: labels uint8 [n,h,w] (4-byte aligned), w % 4 == 0, h and w <= ISA_CONTOUR_MAX_SIDE; connectivity 4
+ *   or 8; cmax >= 1, vmax >= 1.
+ *   table int64 [n][cmax][8] (8-byte aligned), the contours of an image in ascending order of start key:
+ *     0 label   1 offset of the first vertex in the image's verts   2 vertex count   3 edge count (crack length)
+ *     4 signed twice-area   5 start key   6 row-major index of the pixel that owns the start edge   7 always 0
+ *   verts int16 [n][vmax][2] (4-byte aligned): (x, y), the vertices of contour 0 first, then those of contour 1, ...
+ *   counts int32 [n][4] (4-byte aligned): contours found, vertices found (both whatever the capacities),
+ *     contours beyond cmax = max(0, [0] - cmax), vertices beyond vmax = max(0, [1] - vmax).
+ *   Overflow: the first cmax contours get their rows, offsets counted over ALL vertices before them; the vertices of a
+ *   contour are written only when it has a row and offset + count <= vmax, so what is written is a prefix.  Rows and
+ *   vertices past that keep what the caller left there; nothing is written outside the buffers.
+ *   scratch: ISA_CONTOUR_SCRATCH_BYTES(n,h,w) bytes, 16-byte aligned, need not be cleared: per image 48 bytes for each of
+ *   the ISA_CONTOUR_EDGES = 4 h w possible edges (two 16-byte jumping records, key, successor, corner flag, start
+ *   edge), 4 per lattice point (index of its first edge) and the block sums of the two scans.
+ * isa_contour_topology: topo int32 [n][nl][3] (4-byte aligned; 1 <= nl <= 256), set by the entry itself: outer contours
+ *   (= components), holes and Euler number of label v, from the min(counts[i][0], cmax) rows the table holds (contours
+ *   beyond cmax are not in it: the caller sees that from counts); rows of a label >= nl are skipped, label 0 is all 0. */
+#define ISA_CONTOUR_MAX_SIDE 4096
+#define ISA_CONTOUR_BLOCK 1024
+#define ISA_CONTOUR_EDGES(h, w) ((int64_t)4 * (h) * (w))
+#define ISA_CONTOUR_POINTS(h, w) ((((int64_t)(h) + 1) * ((int64_t)(w) + 1) + 3) / 4 * 4)
+#define ISA_CONTOUR_SCRATCH_BYTES(n, h, w)                                                                     \
+    ((int64_t)(n) * (ISA_CONTOUR_EDGES(h, w) * 48 + ISA_CONTOUR_POINTS(h, w) * 4 +                             \
+                     (ISA_CONTOUR_POINTS(h, w) / ISA_CONTOUR_BLOCK + 1) * 16 +                                 \
+                     (ISA_CONTOUR_EDGES(h, w) / ISA_CONTOUR_BLOCK + 1) * 16 + 16))
+int isa_contour_trace(const uint8_t* labels, int32_t n, int32_t h, int32_t w, int32_t connectivity, int32_t cmax,
+                      int32_t vmax, int64_t* table, int16_t* verts, int32_t* counts, void* scratch, int64_t scratch_bytes,
+                      void* stream);
+int isa_contour_topology(const int64_t* table, const int32_t* counts, int32_t n, int32_t cmax, int32_t nl, int32_t* topo,
+                         void* stream);
 /* ---- exact Euclidean distance transform to the two nearest instances; border weights and instance fill -----------------
  * Every entry checks all its arguments before it launches or writes anything (ISA_EINVAL / ISA_EALIGN / ISA_ENOMEM), is
  * asynchronous on `stream`, allocates nothing and never reads anything back: the launch count depends on the shape alone,

@@ -45,7 +45,16 @@ def cc_select_scratch_bytes(n, h, w):
 
 PROPS_ACC, PROPS_OUT, PROPS_MAX_SIDE = 16, 24, 32768      # ISA_PROPS_ACC, ISA_PROPS_OUT, ISA_PROPS_MAX_SIDE
 ORDER_LABEL, ORDER_AREA, ORDER_RASTER = 0, 1, 2
-EDT_MAX_SIDE, EDT_COL_LANES, EDT_ROW_LANES = 4096, 64, 256     # ISA_EDT_MAX_SIDE, ISA_EDT_COL_LANES, ISA_EDT_ROW_LANES
+CONTOUR_MAX_SIDE, CONTOUR_BLOCK, CONTOUR_COLS = 4096, 1024, 8     # ISA_CONTOUR_MAX_SIDE, ISA_CONTOUR_BLOCK, table columns
+
+
+def contour_scratch_bytes(n, h, w):
+    """ISA_CONTOUR_SCRATCH_BYTES: 48 bytes per possible edge (4 h w), 4 per lattice point and the block sums of the scans."""
+    edges, points = 4 * h * w, ((h + 1) * (w + 1) + 3) // 4 * 4
+    return n * (edges * 48 + points * 4 + (points // CONTOUR_BLOCK + 1) * 16 + (edges // CONTOUR_BLOCK + 1) * 16 + 16)
+
+
+EDT_MAX_SIDE, EDT_COL_LANES, EDT_ROW_LANES = 4096, 64, 256    # ISA_EDT_MAX_SIDE, ISA_EDT_COL_LANES, ISA_EDT_ROW_LANES
 
 
 def edt_scratch_bytes(n, h, w):
@@ -278,6 +287,9 @@ SIGNATURES = {
     "isa_instance_props": [VP, I32, I32, I32, I32, I32, VP, VP],
     "isa_props_select": [VP, I32, I32, I32, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP],
     "isa_relabel_u8": [VP, VP, I32, I64, VP, VP],
+    # tracing instance outlines (ReSeg.contours, instance_topology, polygons)
+    "isa_contour_trace": [VP, I32, I32, I32, I32, I32, I32, VP, VP, VP, VP, I64, VP],
+    "isa_contour_topology": [VP, VP, I32, I32, I32, VP, VP],
     # distance transform to the two nearest instances (ReSeg.distance_transform, border_weights, fill_instances)
     "isa_edt2_u8": [VP, I32, I32, I32, VP, VP, VP, VP, I64, VP],
     "isa_border_weights": [VP, VP, VP, VP, I32, I64, VP, VP],

@@ -386,6 +386,16 @@ class Model(object):
         rows = [props[b, 1:1 + int(counts[b])] for b in range(props.shape[0])]
         return fg_prob.cpu(), labels.cpu(), counts, rows
 
+    def predict_polygons(self, images, **predict_kwargs):
+        """predict_instances(images, **predict_kwargs) and the outlines of what it found: (fg_prob, labels, n_objects,
+        polygons), polygons a list per image of {'label', 'outer': int16 [k,2], 'holes': [int16 [k,2], ...]} in
+        model-resolution pixel-corner coordinates (ReSeg.polygons, traced on the device under the clean-up's connectivity,
+        8 by default)."""
+        m = self.model
+        fg_prob, labels, n_objects = self.__predict_instances(images, **predict_kwargs)
+        polys = m.polygons(labels, connectivity=predict_kwargs.get('connectivity', 8))
+        return fg_prob.cpu(), labels.cpu(), n_objects.cpu(), polys
+
     def predict_components(self, images, *, min_area=1, connectivity=8, max_objects=None):
         """The count-the-blobs baseline, for any model (no instance head is run): the connected components of the predicted
         class map (class 0 = background; pixels of different classes never join) with at least min_area pixels, numbered in

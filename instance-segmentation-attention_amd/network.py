@@ -624,6 +624,30 @@ class Network:
         E.lib.isa_relabel_u8(labels, table, n, labels.numel() // n, out, E.st())
         return out
 
+    def contour_trace(self, labels: torch.Tensor, connectivity, cmax, vmax):
+        """(table int64 [n,cmax,8], verts int16 [n,vmax,2], counts int32 [n,4]) of a uint8 label map [n,h,w]
+        (isa_contour_trace): every contour in ascending order of start key, its corner points, and what was found against
+        what fitted.  New tensors; rows and vertices past the counts are uninitialised."""
+        E = self.E
+        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
+        n, h, w = labels.shape
+        table = torch.empty((n, int(cmax), L.CONTOUR_COLS), dtype=torch.int64, device=labels.device)
+        verts = torch.empty((n, int(vmax), 2), dtype=torch.int16, device=labels.device)
+        counts = torch.empty((n, 4), dtype=torch.int32, device=labels.device)
+        scratch = torch.empty((L.contour_scratch_bytes(n, h, w),), dtype=torch.uint8, device=labels.device)
+        E.lib.isa_contour_trace(labels, n, h, w, int(connectivity), int(cmax), int(vmax), table, verts, counts, scratch,
+                                scratch.numel(), E.st())
+        return table, verts, counts
+
+    def contour_topology(self, table: torch.Tensor, counts: torch.Tensor, n_labels=256) -> torch.Tensor:
+        """int32 [n,n_labels,3] from contour_trace's table and counts (isa_contour_topology): outer contours, holes and
+        Euler number per label.  A new tensor."""
+        E = self.E
+        n, cmax = table.shape[0], table.shape[1]
+        topo = torch.empty((n, int(n_labels), 3), dtype=torch.int32, device=table.device)
+        E.lib.isa_contour_topology(table, counts, n, cmax, int(n_labels), topo, E.st())
+        return topo
+
     # ------------------------------------------------------------------ boundary
     def to_nhwc(self, x: torch.Tensor, c_pad=None) -> Act:
         """NCHW fp32 (reference layout) -> NHWC activation view."""

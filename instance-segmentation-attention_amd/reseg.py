@@ -630,6 +630,114 @@ class ReSeg(nn.Module):
                                                           clear_border, orders[order], int(max_objects))
             return self.net.relabel(t, table), count, dropped
 
+    # ------------------------------------------------------------------ outlines: polygons, holes, Euler number
+    def _contour_map(self, labels, connectivity):
+        t = labels.to(self.store.device).contiguous()
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise TypeError("expects a uint8 label map [B,H,W], got %s %s" % (t.dtype, tuple(t.shape)))
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+        n, h, w = t.shape
+        if w % 4 or max(h, w) > L.CONTOUR_MAX_SIDE or not 1 <= n <= 65535 or h < 1:
+            raise ValueError("labels [B,H,W]: W a multiple of 4, H and W at most %d, 1 <= B <= 65535; got %s"
+                             % (L.CONTOUR_MAX_SIDE, tuple(t.shape)))
+        return t
+
+    @staticmethod
+    def contour_capacities(h, w):
+        """The default (max_contours, max_vertices) of contours() for an H x W map: max(256, H W / 16) contours and eight
+        vertices each - 4096 and 32768 at 256 x 256, where a map of leaves has some hundred contours and a few thousand
+        vertices.  The worst cases are H W contours (isolated pixels) and 4 H W vertices."""
+        cmax = max(256, h * w // 16)
+        return cmax, 8 * cmax
+
+    def contours(self, labels, *, connectivity=8, max_contours=None, max_vertices=None, check=True):
+        """The outlines of every instance of a uint8 label map [B,H,W], on the device: (table int64 [B,max_contours,8],
+        verts int16 [B,max_vertices,2], counts int32 [B,4]).  A contour is a closed chain of pixel edges with the label on
+        its right - an outer boundary (clockwise on the screen, positive area) or a hole (negative area) - and a row of
+        table: label, offset of its first vertex in verts[b], vertex count, edge count (crack length), signed twice-area,
+        start key, index of the pixel that owns the start edge, 0; rows in ascending order of start key.  verts holds the
+        corner points (x, y) of contour 0, then of contour 1, ..: collinear points are dropped, pixel (y, x) is the square
+        (x, y) .. (x+1, y+1).  connectivity 8 joins pixels of one label across a corner into one contour, 4 does not.
+        counts[b]: contours found, vertices found, contours beyond max_contours, vertices beyond max_vertices; rows and
+        vertices past what was found (or what fitted: the first max_contours rows, and whole contours while they fit into
+        max_vertices) are uninitialised.  The capacities default to contour_capacities(H, W).  check=True reads counts (the
+        call's only synchronisation) and raises ValueError on overflow; check=False reads nothing and leaves counts in
+        self.last_contour_counts.  isa_contour_trace; DESIGN.md section 21."""
+        with torch.no_grad():
+            t = self._contour_map(labels, connectivity)
+            cmax, vmax = self.contour_capacities(t.shape[1], t.shape[2])
+            cmax = cmax if max_contours is None else int(max_contours)
+            vmax = vmax if max_vertices is None else int(max_vertices)
+            if cmax < 1 or vmax < 1:
+                raise ValueError("max_contours and max_vertices must be positive, got %r, %r" % (max_contours, max_vertices))
+            table, verts, counts = self.net.contour_trace(t, connectivity, cmax, vmax)
+            self.last_contour_counts = counts
+            if check:
+                c = counts.cpu()
+                if int(c[:, 2:].sum()):
+                    raise ValueError("contours: images %s hold up to %d contours and %d vertices, more than max_contours = %d "
+                                     "or max_vertices = %d" % (torch.nonzero(c[:, 2:].sum(1)).view(-1).tolist(),
+                                                               int(c[:, 0].max()), int(c[:, 1].max()), cmax, vmax))
+            return table, verts, counts
+
+    def _contours_that_fit(self, t, connectivity, want_vertices):
+        """contours() of the device map t at the default capacities and, where those overflow, once more at what was found;
+        returns (table, verts, counts, counts on the host).  One read of counts per trace."""
+        table, verts, counts = self.contours(t, connectivity=connectivity, check=False,
+                                             max_vertices=None if want_vertices else 1)
+        c = counts.cpu()
+        over = c[:, 2].sum() + (c[:, 3].sum() if want_vertices else 0)
+        if int(over):
+            table, verts, counts = self.contours(t, connectivity=connectivity, check=False, max_contours=int(c[:, 0].max()),
+                                                 max_vertices=max(1, int(c[:, 1].max())) if want_vertices else 1)
+            c = counts.cpu()
+        return table, verts, counts, c
+
+    def instance_topology(self, labels, *, connectivity=8, n_labels=256):
+        """int32 [B, n_labels, 3] on the device: per label of a uint8 map [B,H,W] the number of its connected components
+        under `connectivity` (its outer contours), of its holes (enclosed components of everything else under the dual
+        connectivity) and the Euler number, components - holes.  Label 0 and absent labels are 0.  The contour table is
+        traced at the default capacity and, after one read of the counts, again at the size found if it did not fit.
+        isa_contour_trace + isa_contour_topology."""
+        if not 1 <= int(n_labels) <= 256:
+            raise ValueError("n_labels must be in 1..256, got %r" % (n_labels,))
+        with torch.no_grad():
+            t = self._contour_map(labels, connectivity)
+            table, _, counts, _ = self._contours_that_fit(t, connectivity, False)
+            return self.net.contour_topology(table, counts, int(n_labels))
+
+    def polygons(self, labels, *, connectivity=8):
+        """The instances of a uint8 label map [B,H,W] as polygons on the host: per image a list with one entry
+        {'label': int, 'outer': int16 ndarray [k,2], 'holes': [int16 ndarray [k,2], ...]} per outer contour, in table
+        order; points are (x, y) corners of pixels (see contours()), the outer ring clockwise on the screen, holes
+        counter-clockwise.  A hole goes to the outer contour of its own connected component (components() of the same map,
+        read at the pixel that owns each contour's start edge).  Only the tables, the vertices in use and one component id
+        per contour come down."""
+        with torch.no_grad():
+            t = self._contour_map(labels, connectivity)
+            table, verts, _, counts = self._contours_that_fit(t, connectivity, True)
+            comp, _ = self.components(t, connectivity=connectivity)
+            n = t.shape[0]
+            rows = int(counts[:, 0].max())
+            ids = torch.gather(comp.view(n, -1), 1, table[:, :rows, 6].clamp(0, comp[0].numel() - 1)).cpu().numpy()
+            table_h = table[:, :rows].cpu().numpy()
+            verts_h = verts[:, :max(1, int(counts[:, 1].max()))].cpu().numpy()
+        out = []
+        for b in range(n):
+            polys, by_comp = [], {}
+            k = int(counts[b, 0])
+            rings = [verts_h[b, int(r[1]):int(r[1] + r[2])].copy() for r in table_h[b, :k]]
+            for r, ring, cid in zip(table_h[b, :k], rings, ids[b, :k]):
+                if r[4] > 0:
+                    polys.append({'label': int(r[0]), 'outer': ring, 'holes': []})
+                    by_comp[int(cid)] = polys[-1]
+            for r, ring, cid in zip(table_h[b, :k], rings, ids[b, :k]):
+                if r[4] < 0:
+                    by_comp[int(cid)]['holes'].append(ring)
+            out.append(polys)
+        return out
+
     # ------------------------------------------------------------------ distance transform, border weights, instance fill
     def _edt_map(self, labels):
         t = labels.to(self.store.device).contiguous()

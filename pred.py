@@ -27,24 +27,26 @@ from isa_amd.model import Model  # noqa: E402
 from pred_list import (H, W, add_cleanup_arguments, add_embedding_arguments, add_fill_arguments,  # noqa: E402
                        add_measure_arguments, check_cleanup_arguments, check_embedding_arguments, check_fill_arguments,
                        check_measure_arguments, clean_and_fill, cleanup_arguments, fill_arguments, nearest_upsample,
-                       select_and_measure, select_arguments, write_classes, write_instances, write_properties)
+                       select_and_measure, select_arguments, write_classes, write_instances, write_polygons,
+                       write_properties)
 
 
 def predict_file(model, image, out_dir, name, instances=False, max_objects=32, clean=None, components=None,
-                 instances_from='attention', bandwidth=None, fill=None, select=None, properties=False):
+                 instances_from='attention', bandwidth=None, fill=None, select=None, properties=False, polygons=None):
     """image: uint8 RGB [h0,w0,3].  Returns the path of the written mask.  clean: ReSeg.clean_instances' keywords for the
     instance map; components: ReSeg.split_components' keywords - the instance files come from the class map's components;
     instances_from='embedding': the instances are mean-shift clusters of the embedding (ReSeg.segment_embedding); fill:
     ReSeg.fill_instances' keywords - unlabelled foreground goes to the nearest instance after the clean-up; select:
     ReSeg.select_instances' keywords - the instances are then filtered and renumbered by their measurements; properties:
-    also write <name>-instances.csv and <name>-ins_mask_model.png (pred_list.write_properties)."""
+    also write <name>-instances.csv and <name>-ins_mask_model.png (pred_list.write_properties); polygons: ReSeg.polygons'
+    keywords - also write <name>-polygons.json (pred_list.write_polygons)."""
     from PIL import Image
     from isa_amd.data import resize_bilinear
     x = resize_bilinear(torch.from_numpy(image[None]), (H, W))  # uint8 [1,H,W,3] on the device, bit-identical to PIL's
                                                                # BILINEAR resize (prediction.py:37); ImageEx follows there
     net = model.model
     net.eval()
-    labels = classes = props = None
+    labels = classes = props = polys = None
     with torch.no_grad():
         if net.n_classes > 2:
             net(False, x)
@@ -66,6 +68,8 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32, c
                 labels, counts, _ = net.split_components(net.class_map(), **components)
         if labels is not None:
             labels, counts, props = select_and_measure(net, labels, counts, x, select, properties)
+            if polygons is not None:
+                polys = net.polygons(labels, **polygons)
     fg = sem_arg[0, 0].cpu().numpy() > 0.5
     full = nearest_upsample(fg, image.shape[0], image.shape[1])            # prediction.py:47-50
     fg_seg_pred_norm = (full * 255).astype(np.float32)                     # pred.py:117
@@ -79,6 +83,8 @@ def predict_file(model, image, out_dir, name, instances=False, max_objects=32, c
     if props is not None:
         write_properties(out_dir, name, labels[0].cpu().numpy(), props[0].cpu().numpy(), int(counts[0]), image.shape[0],
                          image.shape[1])
+    if polys is not None:
+        write_polygons(out_dir, name, labels[0].cpu().numpy(), polys[0], image.shape[0], image.shape[1])
     return path
 
 
@@ -126,7 +132,8 @@ def main():
     components = {'connectivity': opt.connectivity, 'min_area': opt.min_area, 'max_objects': opt.max_objects} \
         if opt.components else None
     path = predict_file(model, image, opt.output, name, opt.instances, opt.max_objects, cleanup_arguments(opt), components,
-                        opt.instances_from, opt.bandwidth, fill_arguments(opt), select_arguments(opt), opt.properties)
+                        opt.instances_from, opt.bandwidth, fill_arguments(opt), select_arguments(opt), opt.properties,
+                        {'connectivity': opt.connectivity} if opt.polygons else None)
     print('wrote', path)
 
 

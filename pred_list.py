@@ -29,6 +29,9 @@ nearest instance (ReSeg.fill_instances, on the device); `--fill-max-dist D` only
 measures what is left on the device (ReSeg.instance_properties) and writes <name>-instances.csv - one row per instance in
 the columns reseg.PROPS_COLUMNS, taken at model resolution, followed by model_w, model_h, orig_w, orig_h so that a caller
 can rescale - and <name>-ins_mask_model.png, the label map at model resolution that the rows describe.
+`--polygons` traces the outlines of what is left on the device (ReSeg.polygons, under `--connectivity`) and writes
+<name>-polygons.json: model_w, model_h, orig_w, orig_h and one {label, outer, holes} entry per connected piece, rings of
+[x, y] pixel corners at model resolution; <name>-ins_mask_model.png is written with it.
 `--synthetic N` runs N random images instead of a list (no files needed)."""
 import argparse
 import os
@@ -190,6 +193,9 @@ def add_measure_arguments(parser):
     parser.add_argument('--properties', action='store_true', help='with --instances or --components: measure every instance '
                         'on the device (ReSeg.instance_properties) and write <name>-instances.csv, one row per instance, '
                         'and <name>-ins_mask_model.png, the label map at model resolution that the rows describe')
+    parser.add_argument('--polygons', action='store_true', help='with --instances or --components: trace every instance on '
+                        'the device (ReSeg.polygons) and write <name>-polygons.json, outer rings and holes as [x, y] pixel '
+                        'corners at model resolution, and <name>-ins_mask_model.png')
     parser.add_argument('--order', choices=['label', 'area', 'raster'], default=None, help='with --instances or '
                         '--components: renumber the instances by old label, largest first, or by first pixel')
     parser.add_argument('--clear-border', action='store_true', help='with --instances or --components: drop the instances '
@@ -201,6 +207,8 @@ def add_measure_arguments(parser):
 def check_measure_arguments(parser, opt):
     if (opt.properties or opt.order or opt.clear_border or opt.max_area is not None) and not (opt.instances or opt.components):
         parser.error('--properties, --order, --clear-border and --max-area need --instances or --components')
+    if opt.polygons and not (opt.instances or opt.components):
+        parser.error('--polygons needs --instances or --components')
     if opt.max_area is not None and opt.max_area < 1:
         parser.error('--max-area must be positive')
 
@@ -234,6 +242,20 @@ def write_properties(d, name, labels, props, n_objects, out_h, out_w):
         f.write(','.join(PROPS_COLUMNS + ('model_w', 'model_h', 'orig_w', 'orig_h')) + '\n')
         for k in range(1, int(n_objects) + 1):
             f.write(','.join([repr(float(v)) for v in props[k]] + sizes) + '\n')
+    Image.fromarray(labels).save(os.path.join(d, name + '-ins_mask_model.png'))
+
+
+def write_polygons(d, name, labels, polys, out_h, out_w):
+    """<name>-polygons.json: the sizes, as in the properties CSV, and ReSeg.polygons' entries of one image with the rings as
+    lists of [x, y] at model resolution; <name>-ins_mask_model.png: the uint8 label map [h,w] they outline."""
+    import json
+    from PIL import Image
+    h, w = labels.shape
+    doc = {'model_w': w, 'model_h': h, 'orig_w': int(out_w), 'orig_h': int(out_h),
+           'polygons': [{'label': p['label'], 'outer': p['outer'].tolist(), 'holes': [r.tolist() for r in p['holes']]}
+                        for p in polys]}
+    with open(os.path.join(d, name + '-polygons.json'), 'w') as f:
+        json.dump(doc, f)
     Image.fromarray(labels).save(os.path.join(d, name + '-ins_mask_model.png'))
 
 
@@ -276,7 +298,7 @@ def main():
         imgs = [ld() for ld in loaders[s:s + opt.batch]]
         # resize on the device (isa_resize_bilinear_u8, bit-identical to PIL's BILINEAR): one launch per source size
         x = torch.cat([resize_bilinear(torch.from_numpy(im[None]), (H, W)) for im in imgs])   # uint8 [B,H,W,3]; ImageEx follows
-        labels = counts = classes = props = None
+        labels = counts = classes = props = polys = None
         select = select_arguments(opt)
         if opt.n_classes > 2:
             with torch.no_grad():
@@ -287,6 +309,7 @@ def main():
                 labels, counts, _ = net.split_components(classes, connectivity=opt.connectivity, min_area=opt.min_area,
                                                          max_objects=opt.max_objects)
                 labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
+                polys = net.polygons(labels, connectivity=opt.connectivity) if opt.polygons else None
                 labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
             classes = classes.cpu().numpy()
         elif opt.instances:
@@ -294,6 +317,7 @@ def main():
             # at model resolution, before the nearest up-sampling
             labels, counts = clean_and_fill(net, labels, counts, cleanup_arguments(opt), fill_arguments(opt))
             labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
+            polys = net.polygons(labels, connectivity=opt.connectivity) if opt.polygons else None
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         elif opt.components:
             with torch.no_grad():
@@ -301,6 +325,7 @@ def main():
                 labels, counts, _ = net.split_components(net.class_map(), connectivity=opt.connectivity,
                                                          min_area=opt.min_area, max_objects=opt.max_objects)
                 labels, counts, props = select_and_measure(net, labels, counts, x, select, opt.properties)
+                polys = net.polygons(labels, connectivity=opt.connectivity) if opt.polygons else None
             labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
         else:
             _, sem_arg = net.infer_graphed(x) if len(imgs) == opt.batch else net(False, x)
@@ -317,6 +342,8 @@ def main():
                 write_instances(d, name, labels[i], counts[i], im.shape[0], im.shape[1])
             if props is not None:
                 write_properties(d, name, labels[i], props[i], counts[i], im.shape[0], im.shape[1])
+            if polys is not None:
+                write_polygons(d, name, labels[i], polys[i], im.shape[0], im.shape[1])
             if classes is not None:
                 write_classes(d, name, classes[i], im.shape[0], im.shape[1])
             done += 1
