@@ -8,31 +8,11 @@
 // traffic of the feature tensors they are derived from, so precision is free there and the
 // softmax / argmax paths stay bit-stable across storage modes.
 // Row-wide reductions (L = h*w = 65 536 at 256^2) use one 1024-thread workgroup per row:
-// wave shuffles, then a 16-entry LDS exchange — the row (256 KB) lives in L2 across the passes.
+// wave shuffles, then a 16-entry LDS exchange (block_sum / block_max, wave.hpp) — the row (256 KB) lives in L2 across the
+// passes.
 #include "common.hpp"
 
 namespace {
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float r = 0.f;
-    for (int i = 0; i < nw; ++i) r += sh[i];
-    return r;
-}
-__device__ __forceinline__ float block_max(float v, float* sh) {
-    v = wave_max(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float r = -INFINITY;
-    for (int i = 0; i < nw; ++i) r = fmaxf(r, sh[i]);
-    return r;
-}
 
 // ---- a7 step 1: dot[p] = m[p]*<w, x[p,:]> + bias ; chansum[b,c] += m[p]*x[p,c] -----------------
 template <typename T>

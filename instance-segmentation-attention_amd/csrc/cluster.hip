@@ -53,21 +53,6 @@ static inline Scratch carve(void* p, long n, long chunks) {
 }
 
 __device__ __forceinline__ int clamp_nb(int v) { return v < 0 ? 0 : (v > KI ? KI : v); }
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {      // a + b == b + a: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // 8 channels [8g, 8g+8) of a pixel row; channels >= c and groups past the last read as 0
 template <typename T>
@@ -130,8 +115,8 @@ __global__ __launch_bounds__(NT) void cluster_init_kernel(const uint8_t* __restr
         labels[(long)b * L + p] = 0;
         if (fg[(long)b * L + p]) { ++cnt; if ((int)p < mn) mn = (int)p; }
     }
-    cnt = wave_sum_i(cnt);
-    mn = wave_min_i(mn);
+    cnt = wave_sum(cnt);
+    mn = wave_min(mn);
     if (lane == 0) { red[wave][0] = cnt; red[wave][1] = mn; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -292,13 +277,13 @@ __global__ __launch_bounds__(NT) void cluster_ms_kernel(View x, const uint8_t* _
             }
         }
     }
-    cnt = wave_sum_i(cnt);
-    mn = wave_min_i(mn);
+    cnt = wave_sum(cnt);
+    mn = wave_min(mn);
     if (lane == 0) { redi[wave][0] = cnt; redi[wave][1] = mn; }
     if (KIND == MS_SHIFT) {
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
-            const float v = wave_sum_f(acc[j]);
+            const float v = wave_sum(acc[j]);
             if (lane == 0) redf[wave][j] = v;
         }
     }
@@ -492,7 +477,7 @@ __global__ __launch_bounds__(NT) void cluster_lloyd_kernel(View x, const uint8_t
         __syncthreads();
         onehot_mma(xs[wave], labs[wave], lane, acc);
     }
-    mv = wave_sum_i(mv);
+    mv = wave_sum(mv);
     if (lane == 0) redm[wave] = mv;
     __syncthreads();
     const long o = ((long)(i & 1) * B + b) * nch + chunk;

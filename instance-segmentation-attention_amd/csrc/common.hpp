@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "../../include/isa_kernels.h"
 #include "slab_plan.hpp"
+#include "wave.hpp"       // wave and workgroup reductions and scans
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -37,6 +38,11 @@ static inline bool tensor_ok(const isa_tensor* t, int align_elems) {
 }
 
 static inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+// do the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte?
+static inline bool ranges_overlap(const void* a, uintptr_t abytes, const void* b, uintptr_t bbytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bbytes && y < x + abytes;
+}
 static inline bool same_shape(const isa_tensor* a, const isa_tensor* b) {
     return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c && a->dtype == b->dtype;
 }
@@ -328,18 +334,6 @@ __device__ __forceinline__ bool bn_fin_inline(const FinDev& f, int c, int groups
     // the writer is the LAST workgroup in x: in the persistent tile loops it has the fewest tiles, its extra work hides there
     return bn_fin_inline<NTHREADS>(f, c, groups, gsel, tab, tab_ld, tid, 0, c,
                                    blockIdx.x == gridDim.x - 1 && blockIdx.y == 0 && blockIdx.z == 0);
-}
-
-// ---- wave reductions ------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's GLOBAL stores (vmcnt(0)

@@ -40,12 +40,6 @@ static_assert(CC_TAB_CHUNK + ISA_ROW_CHUNKS <= CC_TAB_WORDS && ISA_CC_TAB_BYTES 
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- union-find in LDS (tile) ----------------------------------------------------------------------------------------
 // lab[i] <= i for every i at all times (it starts at i or at the start of i's run, and only atomicMin writes it).
 __device__ __forceinline__ int lds_read(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(const int* paren
         }
         *reinterpret_cast<i32x4*>(comp + (long)b * hw + p) = out;
     }
-    roots = wave_sum_i(roots);
+    roots = wave_sum(roots);
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(n_comp + b, roots);
 }
 
@@ -268,25 +262,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_area_kernel(const int* comp, Cc
     if (run_len) atomicAdd(ar + run_c - 1, run_len);
 }
 
-// exclusive prefix of v over the workgroup in thread order; total: the workgroup's sum.  sh: CC_THREADS / 64 ints.
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();                                             // sh may still be read from the last call
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < CC_THREADS / 64; ++k) { const int t = sh[k]; if (k < wave) off += t; total += t; }
-    return off + inc - v;
-}
-
 // A root pixel holds comp == its own index + 1.  PASS 0: the qualifying roots of the chunk are counted into tab (and, in
 // LARGEST mode, every root offers its (area, inverted root) key to its value's winner word).  PASS 1 (SPLIT, after the fold
 // has turned the chunk counts into their exclusive scan): the root at raster rank r among the image's qualifying roots gets
@@ -333,7 +308,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_roots_kernel(const uint8_t* map
             mine += cnt;
         } else {
             int total;
-            int r = before + block_excl_scan(cnt, sh, total);
+            int r = before + block_excl_scan<CC_THREADS>(cnt, sh, total);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (!root[j]) continue;
@@ -346,7 +321,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_roots_kernel(const uint8_t* map
     }
     if constexpr (PASS == 0) {
         int total;
-        block_excl_scan(mine, sh, total);
+        block_excl_scan<CC_THREADS>(mine, sh, total);
         if (threadIdx.x == 0) tab[CC_TAB_CHUNK + s] = total;
     }
 }
@@ -358,12 +333,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_split_fold_kernel(int* tabs, in
     for (int b = wave; b < n; b += CC_THREADS / 64) {            // wave-uniform
         int* ch = tabs + (long)b * CC_TAB_WORDS + CC_TAB_CHUNK;
         const int v = lane < S ? ch[lane] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        const int inc = wave_incl_scan(v);
         if (lane < S) ch[lane] = inc - v;
         const int total = __shfl(inc, 63, 64);
         if (lane == 0) {
@@ -384,7 +354,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_largest_fold_kernel(int* tabs, 
     const int area = (int)(key >> 32), root = 0x7fffffff - (int)(uint32_t)key;
     const int survives = v > 0 && area >= min_area;              // min_area >= 1 here: a value without pixels has key 0
     int survivors;
-    const int rank = block_excl_scan(survives, sh, survivors);
+    const int rank = block_excl_scan<CC_THREADS>(survives, sh, survivors);
     const int lab = survives && rank < max_objects ? rank + 1 : 0;
     tab[CC_TAB_ROOT + v] = lab ? root + 1 : 0;
     tab[CC_TAB_LAB + v] = lab;
@@ -435,7 +405,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_write_kernel(const uint8_t* map
     }
 }
 
-bool cc_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 bool cc_shape_ok(int n, int h, int w) {
     return n > 0 && n <= 65535 && h > 0 && w > 0 && w % 4 == 0 && (int64_t)h * w < (1L << 30);
 }
@@ -446,7 +415,7 @@ extern "C" int isa_cc_label(const uint8_t* map, int32_t n, int32_t h, int32_t w,
                             int32_t* n_comp, void* scratch, int64_t scratch_bytes, void* stream) {
     if (!map || !comp || !n_comp || !scratch || !cc_shape_ok(n, h, w) || (connectivity != 4 && connectivity != 8))
         return ISA_EINVAL;
-    if (!cc_aligned(map, 4) || !cc_aligned(comp, 16) || !cc_aligned(n_comp, 4) || !cc_aligned(scratch, 16)) return ISA_EALIGN;
+    if (!aligned(map, 4) || !aligned(comp, 16) || !aligned(n_comp, 4) || !aligned(scratch, 16)) return ISA_EALIGN;
     if (scratch_bytes < ISA_CC_LABEL_SCRATCH_BYTES(n, h, w)) return ISA_ENOMEM;
     const long hw = (long)h * w;
     int* parent = reinterpret_cast<int*>(scratch);
@@ -475,11 +444,9 @@ extern "C" int isa_cc_select(const uint8_t* map, const int32_t* comp, int32_t n,
         (mode != ISA_CC_SPLIT && mode != ISA_CC_LARGEST) || max_objects < 1 || max_objects > 255)
         return ISA_EINVAL;
     const long hw = (long)h * w;
-    const uintptr_t m0 = reinterpret_cast<uintptr_t>(map), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t bytes = (uintptr_t)n * hw;
-    if (o0 < m0 + bytes && m0 < o0 + bytes) return ISA_EINVAL;   // out may not alias map
-    if (!cc_aligned(map, 4) || !cc_aligned(comp, 16) || !cc_aligned(out, 4) || !cc_aligned(count, 4) ||
-        !cc_aligned(dropped, 4) || !cc_aligned(scratch, 16))
+    if (ranges_overlap(out, (uintptr_t)n * hw, map, (uintptr_t)n * hw)) return ISA_EINVAL;   // out may not alias map
+    if (!aligned(map, 4) || !aligned(comp, 16) || !aligned(out, 4) || !aligned(count, 4) ||
+        !aligned(dropped, 4) || !aligned(scratch, 16))
         return ISA_EALIGN;
     if (scratch_bytes < ISA_CC_SELECT_SCRATCH_BYTES(n, h, w)) return ISA_ENOMEM;
     if (min_area < 1) min_area = 1;

@@ -75,33 +75,6 @@ __device__ __forceinline__ int edge_mask(const Quad& q) {
            (q.b > 0 && q.b != q.a ? 8 : 0);
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-// exclusive scan of v over the CT_THREADS threads of the workgroup; *total: their sum.  sh: CT_THREADS / 64 ints; ends with a
-// barrier, so sh may be used again at once
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(v, lane);
-    if (lane == 63) sh[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < CT_THREADS / 64; ++k) {
-        const int t = sh[k];
-        if (k < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
 // the edge masks of the thread's CT_ITEMS lattice points of block blockIdx.x; returns their edge count
 __device__ __forceinline__ int point_masks(const uint8_t* m, const CtGeom& g, int (&mask)[CT_ITEMS]) {
     const int p0 = blockIdx.x * CT_BLOCK + threadIdx.x * CT_ITEMS;
@@ -121,7 +94,7 @@ __global__ __launch_bounds__(CT_THREADS) void count_kernel(const uint8_t* labels
     const int img = blockIdx.y;
     int mask[CT_ITEMS], total;
     const int cnt = point_masks(labels + (long)img * g.h * g.w, g, mask);
-    block_excl_scan(cnt, sh, &total);
+    block_excl_scan<CT_THREADS>(cnt, sh, total);
     if (threadIdx.x == 0) b.bsum[(long)img * g.bstride + blockIdx.x] = total;
 }
 
@@ -129,17 +102,8 @@ __global__ __launch_bounds__(CT_THREADS) void count_kernel(const uint8_t* labels
 __global__ __launch_bounds__(CT_THREADS) void scan_blocks_kernel(CtGeom g, CtBuf b) {
     __shared__ int sh[CT_THREADS / 64];
     const int img = blockIdx.x;
-    int32_t* s = b.bsum + (long)img * g.bstride;
-    int carry = 0;
-    for (int k0 = 0; k0 < g.nbp; k0 += CT_THREADS) {
-        const int k = k0 + threadIdx.x;
-        const int v = k < g.nbp ? s[k] : 0;
-        int total;
-        const int ex = block_excl_scan(v, sh, &total);
-        if (k < g.nbp) s[k] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) b.ecount[img * 4] = carry;
+    const int edges = block_scan_walk<CT_THREADS>(b.bsum + (long)img * g.bstride, g.nbp, 1, sh);
+    if (threadIdx.x == 0) b.ecount[img * 4] = edges;
 }
 
 __global__ __launch_bounds__(CT_THREADS) void emit_kernel(const uint8_t* labels, CtGeom g, CtBuf b) {
@@ -147,7 +111,7 @@ __global__ __launch_bounds__(CT_THREADS) void emit_kernel(const uint8_t* labels,
     const int img = blockIdx.y;
     int mask[CT_ITEMS], total;
     const int cnt = point_masks(labels + (long)img * g.h * g.w, g, mask);
-    int at = b.bsum[(long)img * g.bstride + blockIdx.x] + block_excl_scan(cnt, sh, &total);
+    int at = b.bsum[(long)img * g.bstride + blockIdx.x] + block_excl_scan<CT_THREADS>(cnt, sh, total);
     const int p0 = blockIdx.x * CT_BLOCK + threadIdx.x * CT_ITEMS;
     int32_t* base = b.base + (long)img * g.pstride;
     uint32_t* key = b.key + (long)img * g.emax;
@@ -267,8 +231,8 @@ __global__ __launch_bounds__(CT_THREADS) void final_count_kernel(CtGeom g, CtBuf
     start_items(g, b, sums, img, E, is, nv);
 #pragma unroll
     for (int i = 0; i < CT_ITEMS; ++i) { c += is[i]; v += nv[i]; }
-    block_excl_scan(c, sh, &tc);
-    block_excl_scan(v, sh, &tv);
+    block_excl_scan<CT_THREADS>(c, sh, tc);
+    block_excl_scan<CT_THREADS>(v, sh, tv);
     if (threadIdx.x == 0) {
         b.fsum[(long)img * g.fstride + 2 * blockIdx.x] = tc;
         b.fsum[(long)img * g.fstride + 2 * blockIdx.x + 1] = tv;
@@ -279,17 +243,8 @@ __global__ __launch_bounds__(CT_THREADS) void final_scan_kernel(CtGeom g, CtBuf 
     __shared__ int sh[CT_THREADS / 64];
     const int img = blockIdx.x, E = b.ecount[img * 4];
     const int nb = (E + CT_BLOCK - 1) / CT_BLOCK;
-    int32_t* s = b.fsum + (long)img * g.fstride;
-    int cc = 0, cv = 0;
-    for (int k0 = 0; k0 < nb; k0 += CT_THREADS) {
-        const int k = k0 + threadIdx.x;
-        const int c = k < nb ? s[2 * k] : 0, v = k < nb ? s[2 * k + 1] : 0;
-        int tc, tv;
-        const int ec = block_excl_scan(c, sh, &tc), ev = block_excl_scan(v, sh, &tv);
-        if (k < nb) { s[2 * k] = cc + ec; s[2 * k + 1] = cv + ev; }
-        cc += tc;
-        cv += tv;
-    }
+    int32_t* s = b.fsum + (long)img * g.fstride;                         // (contours, vertices) per block, interleaved
+    const int cc = block_scan_walk<CT_THREADS>(s, nb, 2, sh), cv = block_scan_walk<CT_THREADS>(s + 1, nb, 2, sh);
     if (threadIdx.x == 0) {
         int32_t* o = counts + img * 4;
         o[0] = cc; o[1] = cv; o[2] = max(0, cc - g.cmax); o[3] = max(0, cv - g.vmax);
@@ -306,8 +261,8 @@ __global__ __launch_bounds__(CT_THREADS) void final_write_kernel(const uint8_t* 
     start_items(g, b, sums, img, E, is, nv);
 #pragma unroll
     for (int i = 0; i < CT_ITEMS; ++i) { c += is[i]; v += nv[i]; }
-    int row = b.fsum[(long)img * g.fstride + 2 * blockIdx.x] + block_excl_scan(c, sh, &tc);
-    int off = b.fsum[(long)img * g.fstride + 2 * blockIdx.x + 1] + block_excl_scan(v, sh, &tv);
+    int row = b.fsum[(long)img * g.fstride + 2 * blockIdx.x] + block_excl_scan<CT_THREADS>(c, sh, tc);
+    int off = b.fsum[(long)img * g.fstride + 2 * blockIdx.x + 1] + block_excl_scan<CT_THREADS>(v, sh, tv);
     const long eo = (long)img * g.emax;
     const int e0 = blockIdx.x * CT_BLOCK + threadIdx.x * CT_ITEMS;
 #pragma unroll

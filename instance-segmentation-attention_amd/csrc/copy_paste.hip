@@ -271,11 +271,6 @@ __global__ __launch_bounds__(CP_THREADS) void cp_compact_kernel(CpArgs a) {
     }
 }
 
-bool cp_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool cp_overlap(const void* a, uintptr_t abytes, const void* b, uintptr_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
 
 template <bool VEC> void cp_launch(const CpArgs& a, hipStream_t st) {
     const long hw = (long)a.h * a.w;
@@ -308,13 +303,13 @@ extern "C" int isa_copy_paste_u8(const uint8_t* rgb, const uint8_t* sem, const u
                                                               {n_out, (uintptr_t)n * 4}, {plan, (uintptr_t)n * 16}, {scratch, counters}};
     for (const auto& o : out)
         for (const auto& i : in)
-            if (cp_overlap(o.p, o.bytes, i.p, i.bytes)) return ISA_EINVAL;
+            if (ranges_overlap(o.p, o.bytes, i.p, i.bytes)) return ISA_EINVAL;
     for (int i = 0; i < 6; ++i)
         for (int j = i + 1; j < 6; ++j)
-            if (cp_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return ISA_EINVAL;
+            if (ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return ISA_EINVAL;
     const bool vec = k % 16 == 0;
-    if (!cp_aligned(n_objects, 4) || !cp_aligned(xform, 4) || !cp_aligned(select, 4) || !cp_aligned(n_out, 4) || !cp_aligned(plan, 4) ||
-        !cp_aligned(scratch, 4) || (vec && (!cp_aligned(planes, 16) || !cp_aligned(planes_out, 16))))
+    if (!aligned(n_objects, 4) || !aligned(xform, 4) || !aligned(select, 4) || !aligned(n_out, 4) || !aligned(plan, 4) ||
+        !aligned(scratch, 4) || (vec && (!aligned(planes, 16) || !aligned(planes_out, 16))))
         return ISA_EALIGN;
     if (scratch_bytes < ISA_COPY_PASTE_SCRATCH_BYTES(n, k)) return ISA_ENOMEM;
     hipStream_t st = as_stream(stream);

@@ -37,11 +37,6 @@ static inline Geo geometry(long L) {
     return Geo{ch, ((L + ch - 1) / ch + TP - 1) / TP * TP};
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // sum over the 4 lanes of a pixel (its channel groups): every lane of the quad ends with the same bits
 __device__ __forceinline__ float quad_sum(float v) {
     v += __shfl_xor(v, 1, 64);
@@ -249,24 +244,13 @@ __global__ __launch_bounds__(NT) void disc_hinge_kernel(View x, const uint8_t* _
         __syncthreads();
         onehot_mma(xs[wave], labs[wave], lane, acc);
     }
-    hs = wave_sum_d(hs);
-    qs = wave_sum_d(qs);
+    hs = wave_sum(hs);
+    qs = wave_sum(qs);
     if (lane == 0) { dred[wave][0] = hs; dred[wave][1] = qs; }
     __syncthreads();
     const long o = (long)b * nch + chunk;
     if (threadIdx.x < 2) partial[o * 2 + threadIdx.x] = ((dred[0][threadIdx.x] + dred[1][threadIdx.x]) + dred[2][threadIdx.x]) + dred[3][threadIdx.x];
     fold_acc(acc, &xs[0][0][0], hslab + o * SLAB);
-}
-
-// sum over the 1024 threads, fixed order; the result reaches every thread.  sh: 16 doubles.
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < 16; ++w) t += sh[w];
-    return t;
 }
 
 // grid B, 1024 threads: thread (i, j).  img [B][8] = {var_b, dist_b, reg_b, qreg sum, np_b, F_b, foreground, 0}
@@ -304,7 +288,7 @@ __global__ __launch_bounds__(1024) void disc_image_kernel(const float* __restric
     const float tt = pair ? fmaxf(2.f * dd - dist, 0.f) : 0.f;
     T[i][j] = NORM == 2 ? (dist > 0.f ? tt / dist : 0.f) : tt;
     const double pairs = np >= 2 ? (double)np * (double)(np - 1) : 1.0;
-    const double dist_b = block_sum_d((double)tt * (double)tt, sh) / pairs;       // (its barriers publish T)
+    const double dist_b = block_sum((double)tt * (double)tt, sh) / pairs;       // (its barriers publish T)
     // element (i, c = j)
     float gd = 0.f;
 #pragma unroll 8
@@ -314,7 +298,7 @@ __global__ __launch_bounds__(1024) void disc_image_kernel(const float* __restric
     }
     const float invB = 1.f / (float)B;
     const float rn = NORM == 2 ? sqrtf(row32_sum(muv * muv)) : row32_sum(fabsf(muv));
-    const double reg_b = block_sum_d(present && j == 0 ? (double)rn : 0.0, sh) / (np > 0 ? (double)np : 1.0);
+    const double reg_b = block_sum(present && j == 0 ? (double)rn : 0.0, sh) / (np > 0 ? (double)np : 1.0);
     float g = 0.f;
     if (present) {
         if (F > 0) g -= 2.f * alpha * invB / (float)F * S;
@@ -350,7 +334,7 @@ __global__ __launch_bounds__(64) void disc_total_kernel(const double* __restrict
 #pragma unroll
         for (int q = 0; q < 7; ++q) a[q] += img[(long)b * 8 + q];
 #pragma unroll
-    for (int q = 0; q < 7; ++q) a[q] = wave_sum_d(a[q]);
+    for (int q = 0; q < 7; ++q) a[q] = wave_sum(a[q]);
     if (threadIdx.x == 0) {
         const double var = a[0] / B, dist = a[1] / B, reg = a[2] / B, num = a[6];
         const double qreg = num > 0.0 ? a[3] / num : 0.0;

@@ -34,11 +34,6 @@ constexpr int DT_THREADS = 256;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // the last labelled pixel met by a sweep (a) and the last one met whose label is not a's (b); label 0 = none yet
 struct Sweep {
@@ -211,15 +206,10 @@ __global__ __launch_bounds__(DT_THREADS) void fill_labels_kernel(const uint8_t* 
         }
         *reinterpret_cast<uint32_t*>(out + off + p) = o;
     }
-    cnt = wave_sum_i(cnt);
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(filled + blockIdx.y, cnt);
 }
 
-bool dt_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool dt_overlap(const void* a, const void* b, uintptr_t bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bytes && b0 < a0 + bytes;
-}
 
 }  // namespace
 
@@ -228,8 +218,8 @@ extern "C" int isa_edt2_u8(const uint8_t* labels, int32_t n, int32_t h, int32_t 
     if (!labels || !scratch || n <= 0 || n > 65535 || h <= 0 || w <= 0 || h > ISA_EDT_MAX_SIDE || w > ISA_EDT_MAX_SIDE ||
         w % 4 != 0)
         return ISA_EINVAL;
-    if (!dt_aligned(labels, 4) || !dt_aligned(d1sq, 16) || !dt_aligned(d2sq, 16) || !dt_aligned(nearest, 4) ||
-        !dt_aligned(scratch, 16))
+    if (!aligned(labels, 4) || !aligned(d1sq, 16) || !aligned(d2sq, 16) || !aligned(nearest, 4) ||
+        !aligned(scratch, 16))
         return ISA_EALIGN;
     if (scratch_bytes < ISA_EDT_SCRATCH_BYTES(n, h, w)) return ISA_ENOMEM;
     uint2* ent = reinterpret_cast<uint2*>(scratch);
@@ -243,7 +233,7 @@ extern "C" int isa_edt2_u8(const uint8_t* labels, int32_t n, int32_t h, int32_t 
 extern "C" int isa_border_weights(const uint8_t* labels, const int32_t* d1sq, const int32_t* d2sq, const float* cfg, int32_t n,
                                   int64_t hw, float* out, void* stream) {
     if (!labels || !d1sq || !d2sq || !cfg || !out || n <= 0 || hw <= 0 || hw % 4 != 0 || hw >= (1L << 30)) return ISA_EINVAL;
-    if (!dt_aligned(labels, 4) || !dt_aligned(d1sq, 16) || !dt_aligned(d2sq, 16) || !dt_aligned(cfg, 4) || !dt_aligned(out, 16))
+    if (!aligned(labels, 4) || !aligned(d1sq, 16) || !aligned(d2sq, 16) || !aligned(cfg, 4) || !aligned(out, 16))
         return ISA_EALIGN;
     const long total = (long)n * hw;
     hipLaunchKernelGGL(border_weights_kernel, dim3(grid_cap(cdiv(total, DT_THREADS * 4))), dim3(DT_THREADS), 0,
@@ -256,9 +246,9 @@ extern "C" int isa_fill_labels(const uint8_t* labels, const uint8_t* fg, const u
     if (!labels || !fg || !nearest || !d1sq || !out || !filled || n <= 0 || n > 65535 || hw <= 0 || hw % 4 != 0 ||
         hw >= (1L << 30))
         return ISA_EINVAL;
-    if (dt_overlap(out, labels, (uintptr_t)n * hw)) return ISA_EINVAL;          // out may not alias labels
-    if (!dt_aligned(labels, 4) || !dt_aligned(fg, 4) || !dt_aligned(nearest, 4) || !dt_aligned(d1sq, 16) || !dt_aligned(out, 4) ||
-        !dt_aligned(filled, 4))
+    if (ranges_overlap(out, (uintptr_t)n * hw, labels, (uintptr_t)n * hw)) return ISA_EINVAL;   // out may not alias labels
+    if (!aligned(labels, 4) || !aligned(fg, 4) || !aligned(nearest, 4) || !aligned(d1sq, 16) || !aligned(out, 4) ||
+        !aligned(filled, 4))
         return ISA_EALIGN;
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(fill_clear_kernel, dim3(cdiv(n, DT_THREADS)), dim3(DT_THREADS), 0, st, filled, (int)n);

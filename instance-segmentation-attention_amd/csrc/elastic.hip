@@ -235,11 +235,6 @@ void warp_launch(const uint8_t* src, const float2* disp, long total, int h, int 
                            total, h, w, c, dst);
 }
 
-bool el_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-bool el_overlap(const void* a, uintptr_t abytes, const void* b, uintptr_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
 bool el_shape_ok(int32_t n, int32_t h, int32_t w) {
     return n >= 1 && n <= 65535 && h >= 1 && h <= ISA_WARP_MAX_SIDE && w >= 1 && w <= ISA_WARP_MAX_SIDE;
 }
@@ -253,9 +248,10 @@ extern "C" int isa_elastic_field(const float* noise, const float* alpha_dev, int
         radius > ISA_ELASTIC_MAX_RADIUS)
         return ISA_EINVAL;
     const uintptr_t bytes = (uintptr_t)ISA_ELASTIC_SCRATCH_BYTES(n, h, w);      // of noise, disp and the scratch alike
-    if (el_overlap(disp, bytes, noise, bytes) || el_overlap(scratch, bytes, noise, bytes) || el_overlap(scratch, bytes, disp, bytes))
+    if (ranges_overlap(disp, bytes, noise, bytes) || ranges_overlap(scratch, bytes, noise, bytes) ||
+        ranges_overlap(scratch, bytes, disp, bytes))
         return ISA_EINVAL;
-    if (!el_aligned(noise, 8) || !el_aligned(disp, 8) || !el_aligned(alpha_dev, 4) || !el_aligned(scratch, 16)) return ISA_EALIGN;
+    if (!aligned(noise, 8) || !aligned(disp, 8) || !aligned(alpha_dev, 4) || !aligned(scratch, 16)) return ISA_EALIGN;
     if (scratch_bytes < ISA_ELASTIC_SCRATCH_BYTES(n, h, w)) return ISA_ENOMEM;
     ElTaps taps = {};
     if (radius == 0) taps.v[0] = 1.f;                                           // disp = alpha * noise, whatever the one tap says
@@ -276,9 +272,9 @@ extern "C" int isa_warp_u8(const uint8_t* src, const float* disp, int32_t n, int
         (mode != ISA_WARP_NEAREST && mode != ISA_WARP_BILINEAR))
         return ISA_EINVAL;
     const long total = (long)n * h * w;
-    if (el_overlap(dst, (uintptr_t)total * c, src, (uintptr_t)total * c)) return ISA_EINVAL;
-    if (el_overlap(dst, (uintptr_t)total * c, disp, (uintptr_t)total * 8)) return ISA_EINVAL;
-    if (!el_aligned(disp, 8) || !el_aligned(src, 4) || !el_aligned(dst, 4)) return ISA_EALIGN;
+    if (ranges_overlap(dst, (uintptr_t)total * c, src, (uintptr_t)total * c)) return ISA_EINVAL;
+    if (ranges_overlap(dst, (uintptr_t)total * c, disp, (uintptr_t)total * 8)) return ISA_EINVAL;
+    if (!aligned(disp, 8) || !aligned(src, 4) || !aligned(dst, 4)) return ISA_EALIGN;
     const float2* d = reinterpret_cast<const float2*>(disp);
     if (mode == ISA_WARP_NEAREST) warp_launch<ISA_WARP_NEAREST>(src, d, total, h, w, c, dst, as_stream(stream));
     else warp_launch<ISA_WARP_BILINEAR>(src, d, total, h, w, c, dst, as_stream(stream));

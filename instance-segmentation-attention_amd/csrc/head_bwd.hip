@@ -8,17 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float r = 0.f;
-    for (int i = 0; i < nw; ++i) r += sh[i];
-    return r;
-}
-
 // ---------------------------------------------------------------------------------------------
 // loss assembly (one workgroup): per-level coefficients for the prediction gradients, REINFORCE
 // advantage, EMA baseline, and the four reported scalars.  attenet2.py:239-290.

@@ -52,16 +52,6 @@ __device__ __forceinline__ void softmax_row(const float (&l)[KT], float (&p)[KT]
     for (int c = 0; c < KT; ++c) p[c] *= inv;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // classes [c0, c0 + nc): keys / vals [nc][B][L], G [nc * (per_image ? B : 1)] (zeroed by the caller).  Grid (x, B).
 template <typename T, int KT>
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(NT) void lovasz_tilecount_kernel(const uint32_t* __
         const long i = (long)tile * TILE + j * NT + threadIdx.x;
         if (i < seglen) n += v[i] >> 31;
     }
-    n = wave_sum_i(n);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) cnt[blockIdx.x] = (uint32_t)(sh[0] + sh[1] + sh[2] + sh[3]);
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(NT) void lovasz_apply_kernel(const uint32_t* __rest
         }
         run += (long)__popcll(m);
     }
-    acc = wave_sum_d(acc);
+    acc = wave_sum(acc);
     if (lane == 0) wsum[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(1024) void lovasz_assemble_kernel(const double* __r
     for (int seg = wave; seg < nseg; seg += 16) {          // one wave per segment: lanes stride the tiles, fixed fold
         double a = 0.0;
         for (int t = lane; t < ntiles; t += 64) a += partial[(long)seg * ntiles + t];
-        a = wave_sum_d(a);
+        a = wave_sum(a);
         if (lane == 0) segloss[seg] = a;
     }
     __syncthreads();                                       // one workgroup: its own global writes are visible after this
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(1024) void lovasz_assemble_kernel(const double* __r
         for (int c = 0; c < K; ++c) scale[c * nimg + s] = (c >= c0 && (!present || G[c * nimg + s] > 0)) ? sc : 0.f;
         tot += kept ? sum / (double)kept : 0.0;
     }
-    tot = wave_sum_d(tot);
+    tot = wave_sum(tot);
     if (lane == 0) red[wave] = tot;
     __syncthreads();
     if (threadIdx.x == 0) {

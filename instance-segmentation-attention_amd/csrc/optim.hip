@@ -125,7 +125,6 @@ __global__ void adam_prepare_kernel(int* step, float* aux, double b1, double b2,
     aux[3] = (float)sqrt(bc2);
 }
 
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 inline bool finite_f(double v) { return isfinite(v); }
 // what every entry shares: lr, weight decay, clip and the averaging scale
 inline bool common_ok(float lr, float wd, const float* sqnorm, float max_norm, float gscale) {
@@ -148,7 +147,8 @@ extern "C" int isa_adam(float* p, const float* g, float* exp_avg, float* exp_avg
     if (!p || !g || !exp_avg || !exp_avg_sq || !step || !aux || n <= 0) return ISA_EINVAL;
     if (!common_ok(lr, wd, sqnorm, max_norm, gscale) || !finite_f(eps) || eps < 0.f) return ISA_EINVAL;
     if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return ISA_EINVAL;
-    if (!aligned16(p) || !aligned16(g) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) || !aligned16(aux)) return ISA_EALIGN;
+    if (!aligned(p, 16) || !aligned(g, 16) || !aligned(exp_avg, 16) || !aligned(exp_avg_sq, 16) || !aligned(aux, 16))
+        return ISA_EALIGN;
     hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, as_stream(stream), step, aux, beta1, beta2, sqnorm,
                        max_norm, gscale);
     const AdamOp op{aux, lr_dev, lr, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd};
@@ -160,7 +160,7 @@ extern "C" int isa_rmsprop(float* p, const float* g, float* square_avg, int64_t 
     if (!p || !g || !square_avg || n <= 0) return ISA_EINVAL;
     if (!common_ok(lr, wd, sqnorm, max_norm, gscale) || !finite_f(eps) || eps < 0.f) return ISA_EINVAL;
     if (!(alpha >= 0.0 && alpha <= 1.0)) return ISA_EINVAL;
-    if (!aligned16(p) || !aligned16(g) || !aligned16(square_avg)) return ISA_EALIGN;
+    if (!aligned(p, 16) || !aligned(g, 16) || !aligned(square_avg, 16)) return ISA_EALIGN;
     const RmspropOp op{sqnorm, lr_dev, lr, (float)alpha, (float)(1.0 - alpha), eps, wd, max_norm, gscale};
     return launch(p, g, square_avg, nullptr, n, op, stream);
 }
@@ -170,7 +170,7 @@ extern "C" int isa_sgd(float* p, const float* g, float* momentum_buffer, int64_t
     if (!p || !g || !momentum_buffer || n <= 0) return ISA_EINVAL;
     if (!common_ok(lr, wd, sqnorm, max_norm, gscale)) return ISA_EINVAL;
     if (!(momentum >= 0.0) || !finite_f(momentum)) return ISA_EINVAL;
-    if (!aligned16(p) || !aligned16(g) || !aligned16(momentum_buffer)) return ISA_EALIGN;
+    if (!aligned(p, 16) || !aligned(g, 16) || !aligned(momentum_buffer, 16)) return ISA_EALIGN;
     const SgdOp op{sqnorm, lr_dev, lr, (float)momentum, wd, max_norm, gscale};
     return launch(p, g, momentum_buffer, nullptr, n, op, stream);
 }

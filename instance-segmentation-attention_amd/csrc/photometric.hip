@@ -183,8 +183,7 @@ __global__ __launch_bounds__(256) void photo_luma_sum_kernel(const uint8_t* src,
         jitter<1>(r, g, bl, c, c.contrast_at);
         acc += (unsigned)luma(r[0], g[0], bl[0]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(sums + b, part[0] + part[1] + part[2] + part[3]);
@@ -261,7 +260,7 @@ extern "C" int isa_photometric_u8(const uint8_t* src, uint8_t* dst, int32_t n, i
                                   int32_t has_contrast, int64_t* sums_ws, void* stream) {
     if (!src || !dst || !progs_dev || n <= 0 || n > 65535 || h <= 0 || w <= 0) return ISA_EINVAL;
     if (has_contrast && !sums_ws) return ISA_EINVAL;
-    if (has_contrast && (reinterpret_cast<uintptr_t>(sums_ws) % 8)) return ISA_EALIGN;
+    if (has_contrast && !aligned(sums_ws, 8)) return ISA_EALIGN;
     hipStream_t s = as_stream(stream);
     const long npix = (long)h * w;
     const int per_image = 2048 / n > 0 ? 2048 / n : 1;     // about 2048 workgroups in all, grid-stride beyond

@@ -211,8 +211,7 @@ __global__ __launch_bounds__(PR_THREADS) void props_kernel(const uint8_t* labels
         }
         flush<C>(r, tab, w);                                             // the lane's next trip is not its neighbour
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n_oob += __shfl_xor(n_oob, o, 64);
+    n_oob = wave_sum(n_oob);
     if (lane == 0 && n_oob) atomicAdd(oob + img, n_oob);
     __syncthreads();
     // thread v adds row v (label 0 is never accumulated: its row stays empty)
@@ -400,9 +399,9 @@ extern "C" int isa_props_select(const int64_t* acc, int32_t n, int32_t nl, int32
 
 extern "C" int isa_relabel_u8(const uint8_t* labels, const uint8_t* table, int32_t n, int64_t L, uint8_t* out, void* stream) {
     if (!labels || !table || !out || n <= 0 || n > 65535 || L <= 0 || L % 4 || L >= (1ll << 31)) return ISA_EINVAL;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(out);
     const uintptr_t bytes = (uintptr_t)n * (uintptr_t)L;
-    if (a != b && a < b + bytes && b < a + bytes) return ISA_EINVAL;     // the same map or two apart, nothing between
+    // the same map or two apart, nothing between
+    if (labels != out && ranges_overlap(labels, bytes, out, bytes)) return ISA_EINVAL;
     if (!aligned(labels, 4) || !aligned(out, 4)) return ISA_EALIGN;
     const bool wide = L % 16 == 0 && aligned(labels, 16) && aligned(out, 16);
     const long per_block = (long)PR_THREADS * (wide ? 16 : 4);

@@ -187,7 +187,7 @@ extern "C" int isa_resize_lanczos_ws_bytes(int32_t n, int32_t h0, int32_t w0, in
 extern "C" int isa_resize_lanczos_u8(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t c, uint8_t* dst,
                                      int32_t h, int32_t w, void* ws, int64_t ws_bytes, void* stream) {
     if (!src || !dst || src == dst || !ws || !lanczos_sizes_ok(n, h0, w0, c, h, w)) return ISA_EINVAL;
-    if (reinterpret_cast<uintptr_t>(ws) % 4) return ISA_EALIGN;
+    if (!aligned(ws, 4)) return ISA_EALIGN;
     int64_t need = 0;
     isa_resize_lanczos_ws_bytes(n, h0, w0, c, h, w, &need);
     if (ws_bytes < need) return ISA_ENOMEM;

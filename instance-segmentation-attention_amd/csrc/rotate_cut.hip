@@ -86,8 +86,7 @@ __global__ __launch_bounds__(64) void cover_rows_kernel(const uint8_t* planes, i
         single[row * w + x] = (uint8_t)one;
         cnt += one;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    cnt = wave_sum(cnt);
     if (threadIdx.x == 0) row_counts[row] = cnt;
 }
 

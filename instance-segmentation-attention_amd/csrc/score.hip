@@ -34,13 +34,6 @@ bool sc_geom(int64_t L, int W, ScGeom* g) {
     *g = ScGeom{(long)L, (int)S, chunk};
     return true;
 }
-bool sc_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- isa_labels_from_planes -----------------------------------------------------------------------------------------
 // one thread per pixel; PIXEL_MAJOR: planes [n, hw, k] (the k values of a pixel are contiguous), else [n, k, hw]
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(SC_THREADS) void pair_hist_kernel(const uint8_t* a,
         }
     }
     if (run_len) atomicAdd(&bins[run_key], run_len);
-    n_oob = wave_sum_i(n_oob);
+    n_oob = wave_sum(n_oob);
     if (lane == 0 && n_oob) atomicAdd(oob + img, n_oob);
     __syncthreads();
     int32_t* out = hist + (long)img * nbins;
@@ -163,8 +156,7 @@ __device__ __forceinline__ void best_dice(const int32_t* h, int np, int nq, int 
             const int v = A_ROWS ? h[p * nb + q] : h[q * nb + p];
             m = fmax(m, 2.0 * (double)v / ((double)size_p[p] + (double)size_q[q]));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+        m = wave_max(m);
         if (lane == 0) best[p] = m;
     }
 }
@@ -221,7 +213,7 @@ extern "C" int isa_labels_from_planes(const void* planes, int32_t form, int32_t 
     if (!planes || !labels || form < ISA_PLANES_U8_NHWK || form > ISA_PLANES_F32_NKHW || n <= 0 || n > 65535 || k < 1 ||
         k > 255 || hw <= 0 || hw > 0x7fffffffL - SC_THREADS)
         return ISA_EINVAL;
-    if (!sc_aligned(planes, form == ISA_PLANES_I64_NKHW ? 8 : form == ISA_PLANES_F32_NKHW ? 4 : 1)) return ISA_EALIGN;
+    if (!aligned(planes, form == ISA_PLANES_I64_NKHW ? 8 : form == ISA_PLANES_F32_NKHW ? 4 : 1)) return ISA_EALIGN;
     const dim3 grid(cdiv(hw, SC_THREADS), n), block(SC_THREADS);
     hipStream_t st = as_stream(stream);
     if (form == ISA_PLANES_U8_NHWK)
@@ -241,8 +233,8 @@ extern "C" int isa_label_pair_hist(const uint8_t* a, const uint8_t* b, int32_t n
     if (!a || !b || !hist || !oob || n <= 0 || n > 65535 || !ids_ok(na, nb) || L <= 0 || L % 4 ||
         (mode != ISA_HIST_AGGREGATE && mode != ISA_HIST_NAIVE))
         return ISA_EINVAL;
-    if (!sc_aligned(a, 4) || !sc_aligned(b, 4) || !sc_aligned(hist, 4) || !sc_aligned(oob, 4)) return ISA_EALIGN;
-    const bool wide = L % 16 == 0 && sc_aligned(a, 16) && sc_aligned(b, 16);
+    if (!aligned(a, 4) || !aligned(b, 4) || !aligned(hist, 4) || !aligned(oob, 4)) return ISA_EALIGN;
+    const bool wide = L % 16 == 0 && aligned(a, 16) && aligned(b, 16);
     ScGeom g;
     if (!sc_geom(L, wide ? 4 : 1, &g)) return ISA_EINVAL;
     hipStream_t st = as_stream(stream);
@@ -260,7 +252,7 @@ extern "C" int isa_label_pair_hist(const uint8_t* a, const uint8_t* b, int32_t n
 extern "C" int isa_instance_scores(const int32_t* hist, int32_t n, int32_t na, int32_t nb, const int32_t* n_a,
                                    const int32_t* n_b, double* out, void* stream) {
     if (!hist || !out || n <= 0 || n > 65535 || !ids_ok(na, nb)) return ISA_EINVAL;
-    if (!sc_aligned(hist, 4) || !sc_aligned(out, 8) || !sc_aligned(n_a, 4) || !sc_aligned(n_b, 4)) return ISA_EALIGN;
+    if (!aligned(hist, 4) || !aligned(out, 8) || !aligned(n_a, 4) || !aligned(n_b, 4)) return ISA_EALIGN;
     hipLaunchKernelGGL(scores_kernel, dim3(n), dim3(SC_THREADS), 0, as_stream(stream), hist, na, nb, n_a, n_b, out);
     return launch_status();
 }

@@ -40,35 +40,11 @@ __global__ __launch_bounds__(NT) void segsort_hist_kernel(const uint32_t* __rest
     table[((long)seg * 256 + threadIdx.x) * ntiles + tile] = h[threadIdx.x];
 }
 
-// exclusive scan of n entries per segment, in place; one workgroup per segment, 1024 entries a trip with a running total.
-// For short tables: the chunk sums below, and the tile counts of lovasz.hip.
+// exclusive scan of n entries per segment, in place; one workgroup per segment walks it 1024 entries a trip
+// (block_scan_walk, wave.hpp).  For short tables: the chunk sums below, and the tile counts of lovasz.hip.
 __global__ __launch_bounds__(SCAN_NT) void seg_scan_kernel(uint32_t* table, long n) {
     __shared__ uint32_t wtot[SCAN_NT / 64];
-    uint32_t* t = table + (long)blockIdx.x * n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (long base = 0; base < n; base += SCAN_NT) {
-        const long i = base + threadIdx.x;
-        const uint32_t v = i < n ? t[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < SCAN_NT / 64; ++w) {
-            const uint32_t x = wtot[w];
-            before += w < wave ? x : 0u;
-            all += x;
-        }
-        if (i < n) t[i] = carry + before + incl - v;
-        carry += all;
-        __syncthreads();                                   // wtot is rewritten by the next trip
-    }
+    block_scan_walk<SCAN_NT>(table + (long)blockIdx.x * n, n, 1, wtot);
 }
 
 // The digit table of a long segment is scanned by many workgroups in three launches: the sum of every chunk of
@@ -85,8 +61,7 @@ __global__ __launch_bounds__(NT) void seg_chunksum_kernel(const uint32_t* __rest
         const long i = (long)chunk * SCAN_CHUNK + j * NT + threadIdx.x;
         if (i < n) sum += t[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) csum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
@@ -98,24 +73,14 @@ __global__ __launch_bounds__(NT) void seg_chunkscan_kernel(uint32_t* table, long
     __shared__ uint32_t wtot[WAVES];
     const int seg = blockIdx.x / nchunks, chunk = blockIdx.x - seg * nchunks;
     uint32_t* t = table + (long)seg * n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long i0 = (long)chunk * SCAN_CHUNK + (long)threadIdx.x * ITEMS;
-    uint32_t v[ITEMS], sum = 0;
+    uint32_t v[ITEMS], sum = 0, all;
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         v[k] = i0 + k < n ? t[i0 + k] : 0u;
         sum += v[k];
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    uint32_t run = csum[blockIdx.x] + incl - sum;
-    for (int w = 0; w < wave; ++w) run += wtot[w];
+    uint32_t run = csum[blockIdx.x] + block_excl_scan<NT>(sum, wtot, all);
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         if (i0 + k < n) t[i0 + k] = run;
@@ -183,8 +148,6 @@ __global__ __launch_bounds__(NT) void segsort_scatter_kernel(const uint32_t* __r
     }
 }
 
-bool al4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
-
 }  // namespace
 
 int seg_exclusive_scan_u32(uint32_t* table, int nseg, long n, hipStream_t s) {
@@ -204,7 +167,8 @@ extern "C" int isa_segsort_kv_u32(const uint32_t* keys_in, const uint32_t* vals_
             for (int j = i + 1; j < 7; ++j)
                 if (bufs[i] == bufs[j]) return ISA_EINVAL;
     }
-    if (!al4(keys_in) || !al4(vals_in) || !al4(keys_out) || !al4(vals_out) || !al4(tmp_keys) || !al4(tmp_vals) || !al4(table))
+    if (!aligned(keys_in, 4) || !aligned(vals_in, 4) || !aligned(keys_out, 4) || !aligned(vals_out, 4) || !aligned(tmp_keys, 4) ||
+        !aligned(tmp_vals, 4) || !aligned(table, 4))
         return ISA_EALIGN;
     if (table_elems < ISA_SEGSORT_TABLE_ELEMS(nseg, seglen)) return ISA_ENOMEM;
     const int ntiles = (int)((seglen + TILE - 1) / TILE);

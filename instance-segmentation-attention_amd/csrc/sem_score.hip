@@ -73,11 +73,6 @@ template <int CTRL> __device__ __forceinline__ void sm_fold(float& best, int& bi
     if (sm_better(ov, oc, best, bi)) { best = ov; bi = oc; }
 }
 
-__device__ __forceinline__ int sm_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <typename T, int P>
 __global__ __launch_bounds__(SM_THREADS) void sem_confusion_kernel(const T* logits, long ld, int K, const uint8_t* labels,
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(SM_THREADS) void sem_confusion_kernel(const T* logi
     }
     if (!lab_row) return;
     if (run_len) atomicAdd(&bins[run_key], run_len);
-    n_oob = sm_wave_sum(n_oob);
+    n_oob = wave_sum(n_oob);
     if (lane == 0 && n_oob) atomicAdd(oob + img, n_oob);
     __syncthreads();
     unsigned long long* out = conf + (long)img * nbins;

@@ -9,8 +9,10 @@ capacities are exactly what each batch needs unless a test says otherwise.
 
 Shapes.  The scans work on blocks of 1024 lattice points ((h+1) * (w+1) of them) and of 1024 edges, the jumping rounds on
 all edges: 4 x 4 and 8 x 12 (one block, 25 and 117 points), 64 x 64 (5 blocks of points, up to 16 of edges) with n = 1, 3, 16,
-72 x 136 (10 blocks of points, the last one ragged, up to 39 of edges), 256 x 256 with n = 2.  There is one load path; the
-map is still traced once from a pointer 4 bytes off a 16-byte boundary."""
+72 x 136 (10 blocks of points, the last one ragged, up to 39 of edges), 256 x 256 with n = 2 (65 blocks of points, at most
+256 of edges: one trip of the per-image scans of the block sums, 256 blocks a trip), and 520 x 520 (266 blocks of points:
+a second trip; with four edges a pixel 1057 blocks of edges: five trips) against answers written by hand.  There is one
+load path; the map is still traced once from a pointer 4 bytes off a 16-byte boundary."""
 import json
 import os
 import subprocess
@@ -197,6 +199,86 @@ def test_256x256_two_images():
     maps = np.stack([blobs(256, 256, 5, k=12, noise=0.05), spiral(256, 256)])
     f4, f8 = check(maps, "256x256")
     assert f8[1][0]["edges"] > 1 << 15 and len(f8[0]) > 500
+
+
+# ---- past one trip of the one-workgroup scans --------------------------------------------------------------------------------
+# The per-image scans of the block sums take 256 blocks a trip.  520 x 520 has 521^2 lattice points = 266 point blocks, so the
+# point-block scan takes a second trip; the edge-block scan takes one per 256 * 1024 edges the map really has.
+def hand_rows(items, w):
+    """[(table row, its four vertices)] in ascending key order, written out by hand: items are ("outer", label, x0, y0, a, b)
+    for a rectangle a wide and b high with top-left corner (x0, y0), and ("hole", ...) for such a hole in that label.  An
+    outer contour starts with the E edge at its top-left corner and runs clockwise (y points down): 4 vertices, crack
+    length 2 (a + b), twice-area +2 a b, owner pixel (x0, y0).  A hole starts with the S edge at its top-left corner,
+    owned by the pixel left of it, and runs the other way: twice-area -2 a b."""
+    out = []
+    for kind, v, x0, y0, a, b in items:
+        pt = y0 * (w + 1) + x0
+        if kind == "outer":
+            row = [v, 0, 4, 2 * (a + b), 2 * a * b, pt * 4 + C.E, y0 * w + x0, 0]
+            vs = [(x0, y0), (x0 + a, y0), (x0 + a, y0 + b), (x0, y0 + b)]
+        else:
+            row = [v, 0, 4, 2 * (a + b), -2 * a * b, pt * 4 + C.S, y0 * w + x0 - 1, 0]
+            vs = [(x0, y0), (x0, y0 + b), (x0 + a, y0 + b), (x0 + a, y0)]
+        out.append((row, vs))
+    out.sort(key=lambda rv: rv[0][5])
+    for i, (row, _) in enumerate(out):
+        row[1] = 4 * i
+    return out
+
+
+def test_520x520_rectangles_second_trip_of_the_block_scan():
+    """Five rectangles of distinct labels on 520 x 520: one at the origin, one that touches the far corner (its points lie
+    in the blocks of the scan's second trip), one with a rectangular hole and one inside that hole.  Answers by hand, the
+    restatement as well, both connectivities (nothing touches diagonally: they agree), and a repeat that is bit-identical."""
+    h = w = 520
+    m = np.zeros((h, w), np.uint8)
+    items = [("outer", 1, 0, 0, 8, 4), ("outer", 2, 300, 48, 16, 20), ("outer", 3, 100, 200, 40, 30),
+             ("hole", 3, 110, 210, 10, 6), ("outer", 4, 112, 212, 4, 2), ("outer", 5, w - 12, h - 8, 12, 8)]
+    for kind, v, x0, y0, a, b in items:
+        m[y0:y0 + b, x0:x0 + a] = v if kind == "outer" else 0
+    assert m[h - 1, w - 1] == 5 and m[210, 110] == 0 and m[212, 112] == 4
+    assert (h + 1) * (w + 1) > 256 * 1024 and 4 * h * w > 256 * 1024
+    rows = hand_rows(items, w)
+    wt = np.array([[r for r, _ in rows]], np.int64)
+    wv = np.array([[p for _, vs in rows for p in vs]], np.int16)
+    wc = np.array([[6, 24, 0, 0]], np.int32)
+    wtopo = np.zeros((1, 256, 3), np.int32)
+    wtopo[0, [1, 2, 4, 5]] = (1, 0, 1)
+    wtopo[0, 3] = (1, 1, 0)                                       # Euler number 0: one component, one hole
+    maps = m[None]
+    for conn in (4, 8):
+        tag = "rectangles 520x520, connectivity %d" % conn
+        got = dev_trace(maps, conn, 6, 24)
+        for g, want, part in zip(got, (wt, wv, wc, wtopo), ("table", "verts", "counts", "topo")):
+            same(g, want, "%s: %s by hand" % (tag, part))
+        rt, rv, rc = want_trace(maps, conn, 6, 24)
+        for g, want, part in zip(got, (rt, rv, rc, C.topology(rt, rc, 256)), ("table", "verts", "counts", "topo")):
+            same(g, want, "%s: %s" % (tag, part))
+        again = dev_trace(maps, conn, 6, 24)
+        assert all(np.array_equal(a, b) for a, b in zip(got, again)), tag + ": the repeat differs"
+
+
+def test_520x520_four_edges_a_pixel_five_trips_of_the_edge_block_scan():
+    """(x + 2 y) % 3 + 1: every pixel differs from its four neighbours, so under 4-connectivity every pixel is a contour of
+    its own and the map has all 4 h w = 1 081 600 edges the bound allows: 1057 edge blocks, five trips of the scan that gives
+    every contour its row and vertex offset.  Answers by hand (test_patterns holds the same pattern against the restatement
+    at small sizes): row r is pixel r in raster order, a unit square from its top-left corner."""
+    h = w = 520
+    yy, xx = np.mgrid[:h, :w]
+    m = ((xx + 2 * yy) % 3 + 1).astype(np.uint8)
+    px = np.arange(h * w, dtype=np.int64)
+    y, x = px // w, px % w
+    wt = np.stack([m.reshape(-1).astype(np.int64), 4 * px, np.full_like(px, 4), np.full_like(px, 4), np.full_like(px, 2),
+                   (y * (w + 1) + x) * 4, px, np.zeros_like(px)], axis=1)[None]
+    wv = np.stack([np.stack([x, x + 1, x + 1, x], axis=1), np.stack([y, y, y + 1, y + 1], axis=1)], axis=2)
+    wv = wv.reshape(1, 4 * h * w, 2).astype(np.int16)
+    wc = np.array([[h * w, 4 * h * w, 0, 0]], np.int32)
+    assert 4 * h * w > 4 * 256 * 1024
+    got = dev_trace(m[None], 4, h * w, 4 * h * w, nl=4)
+    wtopo = np.zeros((1, 4, 3), np.int32)
+    wtopo[0, 1:, 0] = wtopo[0, 1:, 2] = np.bincount(m.reshape(-1), minlength=4)[1:]
+    for g, want, part in zip(got, (wt, wv, wc, wtopo), ("table", "verts", "counts", "topo")):
+        same(g, want, "four edges a pixel 520x520: " + part)
 
 
 # ---- overflow -----------------------------------------------------------------------------------------------------------
