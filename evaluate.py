@@ -69,7 +69,7 @@ def device_scores(map_a, map_b, n_a=None, n_b=None):
     the GPU: [best Dice a->b, best Dice b->a, SBD, objects in a, objects in b, |n_a - n_b|, foreground Dice, 0]."""
     import torch
     import isa_amd  # noqa: F401
-    from isa_amd import lib as L
+    from isa_amd.labelmaps import LabelOps
     a, b = np.asarray(map_a).reshape(-1), np.asarray(map_b).reshape(-1)
     if a.shape != b.shape:
         raise ValueError("label maps differ in size: %s vs %s" % (np.shape(map_a), np.shape(map_b)))
@@ -78,17 +78,13 @@ def device_scores(map_a, map_b, n_a=None, n_b=None):
         raise ValueError("label ids 0..%d and 0..%d: --device counts at most 256 ids a map and 16384 id pairs "
                          "(isa_label_pair_hist)" % (na - 1, nb - 1))
     pad = -a.size % 4                    # the kernel reads 4 pixels per load; (0, 0) pixels change none of the scores
-    dev = lambda m: torch.from_numpy(np.concatenate([m.astype(np.uint8), np.zeros(pad, np.uint8)])).cuda()
+    dev = lambda m: torch.from_numpy(np.concatenate([m.astype(np.uint8), np.zeros(pad, np.uint8)])[None]).cuda()
     cnt = lambda v: None if v is None else torch.tensor([int(v)], dtype=torch.int32, device="cuda")
-    ta, tb, ca, cb = dev(a), dev(b), cnt(n_a), cnt(n_b)
-    hist = torch.empty(na * nb, dtype=torch.int32, device="cuda")
-    oob = torch.empty(1, dtype=torch.int32, device="cuda")
-    out = torch.empty(8, dtype=torch.float64, device="cuda")
-    lib, st = L.checked(), L.stream_ptr()
-    lib.isa_label_pair_hist(ta, tb, 1, ta.numel(), na, nb, hist, oob, L.HIST_AGGREGATE, st)
-    lib.isa_instance_scores(hist, 1, na, nb, ca, cb, out, st)
+    ops = LabelOps()
+    oob = ops.alloc((1,), torch.int32)
+    out = ops.pair_scores(dev(a), dev(b), na, nb, cnt(n_a), cnt(n_b), oob)
     assert int(oob.cpu()[0]) == 0
-    return out.cpu().numpy()
+    return out[0].cpu().numpy()
 
 
 def evaluate_cvppp(pred_dir, data_root, fg_only=False, device=False):

@@ -366,15 +366,15 @@ class InstanceHead:
 
     # ------------------------------------------------------------------ discriminative loss on the embedding
     def disc_loss(self, x_enc: Act, ins: torch.Tensor, n_obj: torch.Tensor) -> torch.Tensor:
-        """The discriminative embedding loss (Network.disc_loss; settings in net.disc) on the instance embedding x_enc
-        against the step's instance planes: the label map once, the four forward launches, and one tape closure that adds
-        the loss's gradient into d(x_enc).  Returns scal [8]."""
+        """The discriminative embedding loss (LabelOps.disc_loss in the step's arena; settings in net.disc) on the instance
+        embedding x_enc against the step's instance planes: the label map once, the four forward launches, and one tape
+        closure that adds the loss's gradient into d(x_enc).  Returns scal [8]."""
         E, net = self.E, self.net
-        n, k, Lp = ins.shape[0], ins.shape[1], x_enc.h * x_enc.w
+        n, k = ins.shape[0], ins.shape[1]
         assert ins.dtype == torch.int64 and 1 <= k <= L.DISC_MAX_K, "instance planes: int64 [n,K,h,w], K <= 32"
-        labels = E.arena.alloc((n, Lp), torch.uint8)
-        E.lib.isa_labels_from_planes(ins, L.PLANES_I64_NKHW, n, k, Lp, labels, E.st())
-        scal, _, grad = net.disc_loss(x_enc, labels, k, n_obj, net.disc.cfg, net.disc.norm)
+        labels, _ = net.maps.labels_from_planes(ins, "instance planes")
+        assert labels.numel() == n * x_enc.h * x_enc.w, "instance planes do not match the embedding"
+        scal, _, grad = net.maps.disc_loss(x_enc, labels.view(n, -1), k, n_obj, net.disc.cfg, net.disc.norm)
         if E.record:
             def bwd_disc():
                 acc = E.grads.claim(x_enc, E)

@@ -12,6 +12,7 @@ import torch
 
 from . import lib as L
 from .engine import Act, Engine, Pro, rup
+from .labelmaps import DISC_FORMS, DiscCriterion, LabelOps  # noqa: F401  (the names are imported from here too)
 
 
 CRITERIA = ("CE", "Dice", "Multi", "Lovasz", "CELovasz")
@@ -104,47 +105,14 @@ class SemCriterion:
         return self.border_on
 
 
-DISC_FORMS = {"reference": (True, (1.0, 0.0, 0.0, 0.005)), "full": (False, (1.0, 1.0, 0.001, 0.0))}
+class _EngineLib:
+    """Engine.lib as it is at call time: tests and tracing scripts put a recorder in its place after construction."""
 
+    def __init__(self, eng):
+        self._eng = eng
 
-class DiscCriterion:
-    """Settings of the discriminative embedding loss (DiscriminativeLoss, losses/discriminative.py:162-213) in ONE device
-    buffer, allocated once and rewritten in place so that a captured hipGraph reads them at replay time.  Layout
-    (include/isa_kernels.h, isa_disc_*): {delta_v, delta_d, norm, unit_means, alpha, beta, gamma, gamma_q, weight, 0, 0, 0}.
-    form 'reference': what discriminative_loss() computes (unit means, var + 0.005 qreg); 'full': var + dist + 0.001 reg on
-    plain means; `weights` = (alpha, beta, gamma, gamma_q) and `unit_means` override the form's.  The loss runs when
-    weight > 0; on / off, the form and the norm belong to a captured step's configuration (key()), the rest does not."""
-
-    def __init__(self, device):
-        self.cfg = torch.zeros(L.DISC_CFG_FLOATS, dtype=torch.float32, device=device)
-        self.set(0.0)
-
-    def set(self, weight, delta_var=0.5, delta_dist=1.5, norm=2, form="reference", weights=None, unit_means=None):
-        if form not in DISC_FORMS:
-            raise ValueError("form must be one of %s, got %r" % (tuple(DISC_FORMS), form))
-        if int(norm) not in (1, 2):
-            raise ValueError("norm must be 1 or 2, got %r" % (norm,))
-        if float(delta_var) < 0 or float(delta_dist) < 0 or float(weight) < 0:
-            raise ValueError("delta_var, delta_dist and the weight must not be negative")
-        unit, w = DISC_FORMS[form]
-        if weights is not None:
-            w = tuple(float(v) for v in weights)
-            if len(w) != 4:
-                raise ValueError("weights: (alpha, beta, gamma, gamma_q)")
-        if unit_means is not None:
-            unit = bool(unit_means)
-        self.weight, self.norm, self.form, self.on = float(weight), int(norm), form, float(weight) > 0
-        self.cfg.copy_(torch.tensor([float(delta_var), float(delta_dist), float(norm), float(unit)] + list(w) +
-                                    [float(weight), 0.0, 0.0, 0.0]))
-
-    def set_weight(self, weight):
-        """In place: a captured step follows it (on / off is part of the step's configuration and stays)."""
-        assert float(weight) > 0 and self.on, "the weight of a running loss; switch it on or off with set()"
-        self.weight = float(weight)
-        self.cfg[8:9].fill_(float(weight))
-
-    def key(self):
-        return (True, self.form, self.norm) if self.on else (False, None, None)
+    def __getattr__(self, name):
+        return getattr(self._eng.lib, name)
 
 
 class Network:
@@ -154,6 +122,9 @@ class Network:
         self.n_classes = n_classes
         self.crit = SemCriterion(n_classes, eng.device)
         self.disc = DiscCriterion(eng.device)
+        # the label-map operators of a step (border map, discriminative loss) answer in the step's arena; Engine.begin
+        # puts another arena in place per configuration, hence the lookup at call time
+        self.maps = LabelOps(eng.device, _EngineLib(eng), alloc=lambda shape, dtype: eng.arena.alloc(shape, dtype))
 
     # ------------------------------------------------------------------ blocks
     def block_v1(self, x: Act, pre: str, out: Act):
@@ -274,75 +245,13 @@ class Network:
             E.tape.append(bwd)
         return sem
 
-    def distance_transform(self, labels: torch.Tensor, want=(True, True, True), alloc=None):
-        """(d1sq int32, d2sq int32, nearest uint8), each [n,h,w] or None where `want` says so, of the uint8 label map
-        [n,h,w] on the device (isa_edt2_u8).  alloc(shape, dtype): where outputs and scratch come from (default: new
-        tensors)."""
-        E = self.E
-        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
-        n, h, w = labels.shape
-        alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=labels.device))
-        d1 = alloc((n, h, w), torch.int32) if want[0] else None
-        d2 = alloc((n, h, w), torch.int32) if want[1] else None
-        near = alloc((n, h, w), torch.uint8) if want[2] else None
-        scratch = alloc((L.edt_scratch_bytes(n, h, w),), torch.uint8)
-        E.lib.isa_edt2_u8(labels, n, h, w, d1, d2, near, scratch, scratch.numel(), E.st())
-        return d1, d2, near
-
-    def border_weights(self, labels: torch.Tensor, cfg: torch.Tensor, alloc=None):
-        """fp32 [n,h,w] border weight map of the uint8 instance label map [n,h,w] (isa_edt2_u8 + isa_border_weights);
-        cfg: device float[2] = {w0, sigma}, read by the kernel at run time."""
-        E = self.E
-        n, h, w = labels.shape
-        alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=labels.device))
-        d1, d2, _ = self.distance_transform(labels, (True, True, False), alloc)
-        out = alloc((n, h, w), torch.float32)
-        E.lib.isa_border_weights(labels, d1, d2, cfg, n, h * w, out, E.st())
-        return out
-
-    def fill_labels(self, labels: torch.Tensor, fg: torch.Tensor, max_dist_sq=-1):
-        """(labels uint8 [n,h,w], filled int32 [n]): every pixel with label 0 and fg != 0 takes the nearest label when
-        that lies within max_dist_sq (< 0: no limit) (isa_edt2_u8 + isa_fill_labels).  New tensors."""
-        E = self.E
-        n, h, w = labels.shape
-        assert fg.dtype == torch.uint8 and fg.shape == labels.shape and fg.is_contiguous(), "fg: contiguous uint8 [n,h,w]"
-        d1, _, near = self.distance_transform(labels, (True, False, True))
-        out = torch.empty_like(labels)
-        filled = torch.empty((n,), dtype=torch.int32, device=labels.device)
-        E.lib.isa_fill_labels(labels, fg, near, d1, int(max_dist_sq), n, h * w, out, filled, E.st())
-        return out, filled
-
-    def labels_from_planes(self, planes: torch.Tensor, what, alloc):
-        """(uint8 label map [n,h,w], k) of k instance planes in any form forward() takes: uint8 [n,h,w,k], int64 or fp32
-        [n,k,h,w]; 0 = background, i + 1 = plane i, the first plane gets an overlap (isa_labels_from_planes).
-        alloc(shape, dtype): where the map comes from; what: the argument's name in the error text."""
-        E = self.E
-        form = {torch.uint8: L.PLANES_U8_NHWK, torch.int64: L.PLANES_I64_NKHW,
-                torch.float32: L.PLANES_F32_NKHW}.get(planes.dtype)
-        if form is None:
-            raise TypeError("%s: uint8 [B,H,W,K], int64 [B,K,H,W] or fp32 [B,K,H,W], got %s" % (what, planes.dtype))
-        n, h, w, k = planes.shape if form == L.PLANES_U8_NHWK else (planes.shape[i] for i in (0, 2, 3, 1))
-        assert planes.is_contiguous(), "%s must be contiguous" % what
-        lab = alloc((n, h, w), torch.uint8)
-        E.lib.isa_labels_from_planes(planes, form, n, k, h * w, lab, E.st())
-        return lab, k
-
-    def labels_from_onehot(self, onehot: torch.Tensor, alloc):
-        """uint8 label map [n,h,w] of a one-hot int64 [n,K,h,w] (isa_labels_from_onehot); alloc(shape, dtype): where from."""
-        E = self.E
-        n, K, h, w = onehot.shape
-        labels = alloc((n, h, w), torch.uint8)
-        E.lib.isa_labels_from_onehot(onehot, n, K, h * w, labels, None, E.st())
-        return labels
-
     def _border_map(self, sem: Act, ins: torch.Tensor):
         """The step's border weight map fp32 [n,h,w] from its instance planes (either form forward() takes), in the arena."""
-        E = self.E
         if ins is None or ins.dim() != 4 or ins.numel() == 0:
             raise ValueError("the border weight is on: the step needs the batch's instance planes")
-        lab, _ = self.labels_from_planes(ins, "instance planes", E.arena.alloc)
+        lab, _ = self.maps.labels_from_planes(ins, "instance planes")
         assert lab.numel() == sem.n * sem.h * sem.w, "instance planes do not match the logits"
-        return self.border_weights(lab.view(sem.n, sem.h, sem.w), self.crit.border, E.arena.alloc)
+        return self.maps.border_map(lab.view(sem.n, sem.h, sem.w), self.crit.border)
 
     def sem_loss(self, sem: Act, sem_onehot: torch.Tensor, labels: torch.Tensor = None, ins: torch.Tensor = None):
         """Trainer-side semantic criterion on the logits (model.py:255-269), per self.crit: CE (weighted) and / or
@@ -366,7 +275,7 @@ class Network:
         K, cfg = sem.c, self.crit.cfg
         if labels is None:
             assert sem_onehot.dtype == torch.int64 and tuple(sem_onehot.shape) == (n, K, sem.h, sem.w)
-            labels = self.labels_from_onehot(sem_onehot, E.arena.alloc)
+            labels = self.maps.labels_from_onehot(sem_onehot)
         assert labels.dtype == torch.uint8 and tuple(labels.shape) == (n, sem.h, sem.w)
         pixw = self._border_map(sem, ins) if self.crit.border_on else None
         if self.crit.lovasz:
@@ -447,58 +356,6 @@ class Network:
             E.tape.append(bwd)
         return scal
 
-    def disc_loss(self, emb: Act, labels: torch.Tensor, k, n_obj: torch.Tensor, cfg: torch.Tensor, norm, alloc=None):
-        """The forward launches of the discriminative embedding loss on `emb` (isa_disc_sums, _means, _hinge, _assemble):
-        labels uint8 [n, h*w] of k planes, n_obj int32 [n], cfg the settings buffer.  Returns (scal [8] = {loss, var, dist,
-        reg, qreg, present instances, their pixels, 0}, mu [n,32,32], grad) where grad(demb: Act, accumulate) launches
-        isa_disc_grad.  alloc(shape, dtype): where the scratch comes from (default: the step's arena)."""
-        E = self.E
-        alloc = alloc or E.arena.alloc
-        n, hw = emb.n, emb.h * emb.w
-        ch = L.disc_chunks(hw)
-        f32, i32 = torch.float32, torch.int32
-        slab, hslab = alloc((n * ch * 1024,), f32), alloc((n * ch * 1024,), f32)
-        cslab = alloc((n * ch * 32,), i32)
-        mu, m, gconst = alloc((n, 32, 32), f32), alloc((n, 32, 32), f32), alloc((n, 32, 32), f32)
-        mnorm, cnt = alloc((n * 32,), f32), alloc((n * L.DISC_CNT_STRIDE,), i32)
-        partial, img = alloc((n * ch * 2,), torch.float64), alloc((n * 8,), torch.float64)
-        coef, scal = alloc((n + 1,), f32), alloc((8,), f32)
-        E.lib.isa_disc_sums(emb.d(), labels, k, slab, cslab, E.st())
-        E.lib.isa_disc_means(slab, cslab, n_obj, cfg, n, hw, mu, m, mnorm, cnt, E.st())
-        E.lib.isa_disc_hinge(emb.d(), labels, k, n_obj, mu, cfg, norm, hslab, partial, E.st())
-        E.lib.isa_disc_assemble(hslab, partial, mu, mnorm, cnt, n_obj, cfg, norm, n, hw, gconst, coef, img, scal, E.st())
-
-        def grad(demb: Act, accumulate):
-            E.lib.isa_disc_grad(emb.d(), labels, k, n_obj, mu, gconst, coef, cfg, norm, demb.d(), int(accumulate), E.st())
-        return scal, mu, grad
-
-    def cluster(self, emb: Act, fg: torch.Tensor, method, *, bandwidth=1.5, shifts=3, max_objects=32, max_rounds=None,
-                min_pixels=1, assign_rest=True, refine=0, n_objects=None, iters=10, init=None):
-        """Clusters the embedding `emb` over the foreground fg (uint8 [n, h*w], non-zero = foreground) per image:
-        isa_cluster_meanshift, or isa_cluster_kmeans from the counts n_objects (int32 [n]) and init (None: farthest-point, or
-        float [n,32,32]).  max_rounds (default max_objects): the mean-shift's round budget, refused balls included.
-        refine > 0 runs that many Lloyd iterations from the mean-shift's centres over the whole foreground.  Returns (labels uint8 [n, h*w], n_objects int32 [n], centres float [n,32,32], sizes int32 [n,32], moved
-        int32 [n]); everything stays on the device and nothing is read back."""
-        E = self.E
-        dev = emb.buf.device
-        n, hw = emb.n, emb.h * emb.w
-        labels = torch.empty((n, hw), dtype=torch.uint8, device=dev)
-        n_out, moved = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
-        centres = torch.empty((n, 32, 32), dtype=torch.float32, device=dev)
-        sizes = torch.empty((n, 32), dtype=torch.int32, device=dev)
-        scratch = torch.empty((L.cluster_scratch_bytes(n, hw),), dtype=torch.uint8, device=dev)
-        outs = (labels, n_out, centres, sizes, moved, scratch, E.st())
-        if method == 'meanshift':
-            rounds = int(max_objects if max_rounds is None else max_rounds)
-            E.lib.isa_cluster_meanshift(emb.d(), fg, float(bandwidth), int(shifts), int(max_objects), rounds,
-                                        int(min_pixels), int(bool(assign_rest)), *outs)
-            if refine > 0:
-                n_in, init = n_out.clone(), centres.clone()
-                E.lib.isa_cluster_kmeans(emb.d(), fg, n_in, init, 32, int(refine), *outs)
-        else:
-            E.lib.isa_cluster_kmeans(emb.d(), fg, n_objects, init, int(max_objects), int(iters), *outs)
-        return labels, n_out, centres, sizes, moved
-
     def onehot_map(self, sem_onehot: torch.Tensor) -> torch.Tensor:
         """int64 one-hot [n,K,h,w] -> fp32 argmax(1) map [n, h*w] (sem_seg_argmax of reseg.py:118, on the device)."""
         E = self.E
@@ -540,113 +397,6 @@ class Network:
         oob = torch.empty((sem.n,), dtype=torch.int32, device=sem.buf.device)
         E.lib.isa_sem_confusion(sem.d(), labels, K, conf, oob, None, E.st())
         return conf, oob
-
-    def sem_scores(self, conf: torch.Tensor) -> torch.Tensor:
-        """double [n, 4+2K] from confusion matrices int64 [n,K,K] (isa_sem_scores): pixel accuracy, mean IoU, mean Dice,
-        classes present, IoU[K], Dice[K]."""
-        E = self.E
-        n, K = conf.shape[0], conf.shape[1]
-        out = torch.empty((n, 4 + 2 * K), dtype=torch.float64, device=conf.device)
-        E.lib.isa_sem_scores(conf, n, K, out, E.st())
-        return out
-
-    def cc_label(self, maps: torch.Tensor, connectivity=8):
-        """(comp int32 [n,h,w], n_comp int32 [n]) of the uint8 map [n,h,w] on the device (isa_cc_label): 0 for background,
-        else 1 + the smallest row-major pixel index of the pixel's component inside its image.  New tensors."""
-        E = self.E
-        assert maps.dtype == torch.uint8 and maps.dim() == 3 and maps.is_contiguous(), "maps: contiguous uint8 [n,h,w]"
-        n, h, w = maps.shape
-        comp = torch.empty((n, h, w), dtype=torch.int32, device=maps.device)
-        n_comp = torch.empty((n,), dtype=torch.int32, device=maps.device)
-        scratch = torch.empty((L.cc_label_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
-        E.lib.isa_cc_label(maps, n, h, w, int(connectivity), comp, n_comp, scratch, scratch.numel(), E.st())
-        return comp, n_comp
-
-    def cc_select(self, maps: torch.Tensor, comp: torch.Tensor, mode, min_area=1, max_objects=255):
-        """(labels uint8 [n,h,w], count int32 [n], dropped int32 [n]) from a uint8 map and its cc_label components
-        (isa_cc_select), mode L.CC_SPLIT or L.CC_LARGEST.  New tensors."""
-        E = self.E
-        assert maps.dtype == torch.uint8 and maps.dim() == 3 and maps.is_contiguous(), "maps: contiguous uint8 [n,h,w]"
-        assert comp.dtype == torch.int32 and comp.shape == maps.shape and comp.is_contiguous()
-        n, h, w = maps.shape
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=maps.device)
-        count = torch.empty((n,), dtype=torch.int32, device=maps.device)
-        dropped = torch.empty((n,), dtype=torch.int32, device=maps.device)
-        scratch = torch.empty((L.cc_select_scratch_bytes(n, h, w),), dtype=torch.uint8, device=maps.device)
-        E.lib.isa_cc_select(maps, comp, n, h, w, int(mode), int(min_area), int(max_objects), out, count, dropped, scratch,
-                            scratch.numel(), E.st())
-        return out, count, dropped
-
-    def label_props(self, labels: torch.Tensor, image: torch.Tensor = None, n_labels=256):
-        """(acc int64 [n,n_labels,16], oob int32 [n]) of a uint8 label map [n,h,w] and an optional uint8 image [n,h,w,c]
-        (isa_label_props): area, box, raw moments, crack perimeter, first pixel and channel sums per label.  New tensors."""
-        E = self.E
-        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
-        n, h, w = labels.shape
-        c = 0
-        if image is not None:
-            assert image.dtype == torch.uint8 and image.dim() == 4 and image.is_contiguous() and \
-                tuple(image.shape[:3]) == (n, h, w), "image: contiguous uint8 [n,h,w,c]"
-            c = image.shape[3]
-        acc = torch.empty((n, n_labels, L.PROPS_ACC), dtype=torch.int64, device=labels.device)
-        oob = torch.empty((n,), dtype=torch.int32, device=labels.device)
-        E.lib.isa_label_props(labels, image, n, h, w, c, int(n_labels), acc, oob, E.st())
-        return acc, oob
-
-    def instance_props(self, acc: torch.Tensor, h, w, c=0) -> torch.Tensor:
-        """double [n,n_labels,24] of label_props' accumulators (isa_instance_props).  A new tensor."""
-        E = self.E
-        n, nl = acc.shape[0], acc.shape[1]
-        out = torch.empty((n, nl, L.PROPS_OUT), dtype=torch.float64, device=acc.device)
-        E.lib.isa_instance_props(acc, n, nl, int(h), int(w), int(c), out, E.st())
-        return out
-
-    def props_select(self, acc: torch.Tensor, h, w, min_area=1, max_area=0, clear_border=False, order=L.ORDER_LABEL,
-                     max_objects=255):
-        """(table uint8 [n,256], count int32 [n], dropped int32 [n]) from label_props' accumulators (isa_props_select):
-        the new label of every old one after filtering by area and border contact and ranking by `order`.  New tensors."""
-        E = self.E
-        n, nl = acc.shape[0], acc.shape[1]
-        table = torch.empty((n, 256), dtype=torch.uint8, device=acc.device)
-        count = torch.empty((n,), dtype=torch.int32, device=acc.device)
-        dropped = torch.empty((n,), dtype=torch.int32, device=acc.device)
-        E.lib.isa_props_select(acc, n, nl, int(h), int(w), int(min_area), int(max_area), int(bool(clear_border)), int(order),
-                               int(max_objects), table, count, dropped, E.st())
-        return table, count, dropped
-
-    def relabel(self, labels: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-        """table[i][labels[i]] of a uint8 map [n,...] (isa_relabel_u8); out may be labels itself.  A new tensor without out."""
-        E = self.E
-        assert labels.dtype == torch.uint8 and labels.is_contiguous() and table.dtype == torch.uint8 and table.is_contiguous()
-        n = labels.shape[0]
-        assert tuple(table.shape) == (n, 256)
-        out = torch.empty_like(labels) if out is None else out
-        E.lib.isa_relabel_u8(labels, table, n, labels.numel() // n, out, E.st())
-        return out
-
-    def contour_trace(self, labels: torch.Tensor, connectivity, cmax, vmax):
-        """(table int64 [n,cmax,8], verts int16 [n,vmax,2], counts int32 [n,4]) of a uint8 label map [n,h,w]
-        (isa_contour_trace): every contour in ascending order of start key, its corner points, and what was found against
-        what fitted.  New tensors; rows and vertices past the counts are uninitialised."""
-        E = self.E
-        assert labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), "labels: contiguous uint8 [n,h,w]"
-        n, h, w = labels.shape
-        table = torch.empty((n, int(cmax), L.CONTOUR_COLS), dtype=torch.int64, device=labels.device)
-        verts = torch.empty((n, int(vmax), 2), dtype=torch.int16, device=labels.device)
-        counts = torch.empty((n, 4), dtype=torch.int32, device=labels.device)
-        scratch = torch.empty((L.contour_scratch_bytes(n, h, w),), dtype=torch.uint8, device=labels.device)
-        E.lib.isa_contour_trace(labels, n, h, w, int(connectivity), int(cmax), int(vmax), table, verts, counts, scratch,
-                                scratch.numel(), E.st())
-        return table, verts, counts
-
-    def contour_topology(self, table: torch.Tensor, counts: torch.Tensor, n_labels=256) -> torch.Tensor:
-        """int32 [n,n_labels,3] from contour_trace's table and counts (isa_contour_topology): outer contours, holes and
-        Euler number per label.  A new tensor."""
-        E = self.E
-        n, cmax = table.shape[0], table.shape[1]
-        topo = torch.empty((n, int(n_labels), 3), dtype=torch.int32, device=table.device)
-        E.lib.isa_contour_topology(table, counts, n, cmax, int(n_labels), topo, E.st())
-        return topo
 
     # ------------------------------------------------------------------ boundary
     def to_nhwc(self, x: torch.Tensor, c_pad=None) -> Act:

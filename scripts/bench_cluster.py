@@ -27,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import isa_amd  # noqa: F401,E402
 from isa_amd.engine import Act  # noqa: E402
+from isa_amd.labelmaps import LabelOps  # noqa: E402
 from isa_amd.reseg import ReSeg  # noqa: E402
 
 K_OBJ, BW, SHIFTS, ITERS = 8, 1.5, 3, 10
@@ -119,8 +120,7 @@ def main():
     B, S, C = opt.batch, opt.size, opt.channels
     lines = ["cluster bench: %s, B=%d, %d x %d, C=%d, %d planted instances an image; median of %d alternating calls after %d "
              "warm-up, one event pair per call" % (torch.cuda.get_device_name(0), B, S, S, C, K_OBJ, opt.calls, opt.warmup)]
-    m = ReSeg(2, use_instance_seg=False, dtype=torch.float32)
-    m.eval()
+    m = LabelOps()
     g = torch.Generator(device="cuda").manual_seed(5)
     truth = torch.randint(0, K_OBJ + 1, (B, S // 8, S // 8), generator=g, device="cuda", dtype=torch.int32)
     truth = truth.repeat_interleave(8, 1).repeat_interleave(8, 2).long().contiguous()

@@ -7,7 +7,7 @@ Maps uint8 [16,256,256], already on the device (where ReSeg.segment leaves them)
            components, the worst case of the union-find).
 Timed, each as the median of --calls calls taken in turn (one call of every variant per round), host clock around a
 device synchronise:
-  label   isa_cc_label alone (Network.cc_label);
+  label   isa_cc_label alone (LabelOps.cc_label);
   clean   ReSeg.clean_instances(keep='largest'): isa_cc_label + isa_cc_select(ISA_CC_LARGEST);
   host    the same clean-up the host way: labels.cpu(), scipy.ndimage.label per value when scipy can be imported (else the
           restatement tests/components_np.py), the largest piece of every value, and the copy back; median of --host-calls.
@@ -104,7 +104,7 @@ def main():
         maps_np = make_maps(kind, B, size, seed=size)
         maps = torch.from_numpy(maps_np).cuda()
         for conn in (4, 8):
-            variants = {"label": lambda: m.net.cc_label(maps, conn),
+            variants = {"label": lambda: m.cc_label(maps, conn),
                         "clean": lambda: m.clean_instances(maps, keep='largest', connectivity=conn)}
             got = [v.cpu().numpy() for v in variants["clean"]()]
             want = cnp.largest(maps_np, cnp.label(maps_np, conn)[0], 1, 255)

@@ -28,10 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")]
 import isa_amd  # noqa: F401,E402
 import contours_np as C  # noqa: E402
-import reseg_ref as R  # noqa: E402
 from bench_props import event_ms, make_maps, timed_ms  # noqa: E402
 from isa_amd import lib as L  # noqa: E402
-from isa_amd.reseg import ReSeg  # noqa: E402
+from isa_amd.labelmaps import LabelOps  # noqa: E402
 
 
 def maps_of(kind, B, size, seed):
@@ -69,9 +68,7 @@ def main():
              "per call, median of %d windows; e2e: ReSeg.contours(check=False), host clock around a device synchronise, median "
              "of %d; host: labels.cpu() + numpy listing of the crack edges only, median of %d"
              % (torch.cuda.get_device_name(0), B, opt.reps, opt.calls, opt.calls, opt.host_calls)]
-    m = ReSeg(2, True, dtype=torch.float32)
-    m.load_state_dict(R.synth_state_dict())
-    m.eval()
+    m = LabelOps()
     for size in opt.sizes:
         for kind in ("leaves", "uniform", "checker"):
             conn = 4 if kind == "checker" else 8

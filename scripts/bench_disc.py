@@ -3,7 +3,7 @@
 
 Inputs already on the device: an embedding NHWC [B,H,W,C = 24] (bf16, then fp32), a uint8 label map [B,H,W] of 8 instances
 an image and the object counts; the 'full' form (var + dist + 0.001 reg on plain means), L2 norm.
-  (a) kernels : Network.disc_loss - sums, means, hinge, assemble - and isa_disc_grad; d emb in the embedding's dtype;
+  (a) kernels : LabelOps.disc_loss - sums, means, hinge, assemble - and isa_disc_grad; d emb in the embedding's dtype;
   (b) torch   : one-hot matmul for the means, gathered means for the pull hinge, pairwise distances for the push hinge,
                 autograd for d emb (fp32 from the stored embedding).  (The reference's own formulation expands
                 [B, L, 32, C]: 3 GB at this size.)
@@ -20,8 +20,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import isa_amd  # noqa: F401,E402
-from isa_amd.engine import Act  # noqa: E402
-from isa_amd.network import DiscCriterion  # noqa: E402
+from isa_amd.engine import Act, Arena  # noqa: E402
+from isa_amd.labelmaps import DiscCriterion, LabelOps  # noqa: E402
 from isa_amd.reseg import ReSeg  # noqa: E402
 from isa_amd.trainer import Trainer  # noqa: E402
 
@@ -85,8 +85,8 @@ def main():
     B, S, C = opt.batch, opt.size, opt.channels
     lines = ["disc bench: %s, B=%d, %d x %d, C=%d, %d instances an image, form 'full', L2; median of %d alternating calls after "
              "%d warm-up, one event pair per call" % (torch.cuda.get_device_name(0), B, S, S, C, K_OBJ, opt.calls, opt.warmup)]
-    m = ReSeg(2, use_instance_seg=False, dtype=torch.float32)
-    E = m.engine
+    arena = Arena(torch.device("cuda", torch.cuda.current_device()))     # as in a training step: the scratch is reused
+    ops = LabelOps(alloc=arena.alloc)
     crit = DiscCriterion("cuda")
     crit.set(1.0, DELTA_V, DELTA_D, 2, "full")
     g = torch.Generator(device="cuda").manual_seed(5)
@@ -101,8 +101,8 @@ def main():
         res = {}
 
         def kernels():
-            E.begin(bn_train=True, record=False, key=("bench-disc", dtype))
-            res["scal"], _, grad = m.net.disc_loss(a, labels.view(B, -1), 32, n_obj, crit.cfg, crit.norm)
+            arena.reset()
+            res["scal"], _, grad = ops.disc_loss(a, labels.view(B, -1), 32, n_obj, crit.cfg, crit.norm)
             grad(da, 0)
 
         def baseline():
@@ -115,7 +115,7 @@ def main():
         lines.append("%-8s (a) kernels %8.3f ms   (b) torch one-hot matmul + autograd %8.3f ms   (b) / (a) %6.2f   loss %.6f vs "
                      "%.6f, d emb rel L2 %.1e; one pass over the embedding = %.1f MB"
                      % (str(dtype)[6:], t_k, t_t, t_t / t_k, got, ref, gerr, passes / 1e6))
-    del m
+    del ops, arena
     torch.cuda.empty_cache()
     if not opt.no_step:
         from isa_amd.data import synth_batch

@@ -33,6 +33,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import isa_amd  # noqa: F401,E402
 import distance_np as dn  # noqa: E402  (the restatement the tests use: the self-check below, as bench_components.py does)
 from isa_amd import lib as L  # noqa: E402
+from isa_amd.labelmaps import LabelOps  # noqa: E402
 from isa_amd.reseg import ReSeg  # noqa: E402
 from isa_amd.trainer import Trainer  # noqa: E402
 
@@ -121,7 +122,7 @@ def main():
              % (torch.cuda.get_device_name(0), B, S, S, opt.calls, opt.warmup, opt.host_calls),
              "edt / weights / fill: the entry points on preallocated buffers (2 / 3 / 4 launches); method: ReSeg.fill_instances, "
              "allocations included"]
-    m = ReSeg(2, use_instance_seg=False, dtype=torch.float32)
+    m = LabelOps()
     for kind in ("blobs8", "holes", "single", "pair"):
         maps_np, fg_np = make_maps(kind, B, S, seed=S)
         maps, fg = torch.from_numpy(maps_np).cuda(), torch.from_numpy(fg_np).cuda()

@@ -28,9 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 import isa_amd  # noqa: F401,E402
 import props_np as P  # noqa: E402
-import reseg_ref as R  # noqa: E402
 from isa_amd import lib as L  # noqa: E402
-from isa_amd.reseg import ReSeg  # noqa: E402
+from isa_amd.labelmaps import LabelOps  # noqa: E402
 from scipy import ndimage  # noqa: E402
 
 
@@ -98,9 +97,7 @@ def main():
              "per call, median of %d windows taken in turn; e2e: host clock around a device synchronise, median of %d; host: "
              "labels.cpu() + scipy.ndimage find_objects / sum_labels / center_of_mass per image, median of %d"
              % (torch.cuda.get_device_name(0), B, opt.reps, opt.calls, opt.calls, opt.host_calls)]
-    m = ReSeg(2, True, dtype=torch.float32)
-    m.load_state_dict(R.synth_state_dict())
-    m.eval()
+    m = LabelOps()
     for size in opt.sizes:
         rgb = torch.randint(0, 256, (B, size, size, 3), dtype=torch.uint8, device="cuda")
         for k in opt.objects:

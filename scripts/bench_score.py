@@ -26,10 +26,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
 import isa_amd  # noqa: F401,E402
-import reseg_ref as R  # noqa: E402
 from evaluate import calc_dice, calc_sbd  # noqa: E402
 from isa_amd import lib as L  # noqa: E402
-from isa_amd.reseg import ReSeg  # noqa: E402
+from isa_amd.labelmaps import LabelOps  # noqa: E402
 
 K = 32
 
@@ -100,9 +99,7 @@ def main():
     B = opt.batch
     lines = ["score bench: %s, B=%d, %d objects; host: median of %d calls (host clock), device: events over %d calls after "
              "%d warm-up" % (torch.cuda.get_device_name(0), B, K, opt.host_calls, opt.calls, opt.warmup)]
-    m = ReSeg(2, True, dtype=torch.float32)
-    m.load_state_dict(R.synth_state_dict())
-    m.eval()
+    m = LabelOps()
     for size in [int(v) for v in opt.sizes.split(",")]:
         hist_us = {}
         for dist in ("background", "uniform"):

@@ -6,9 +6,10 @@ After the line `== streams` the same step in a second form: `stream entry_point`
 call time) and `sync src dst` per stream edge (Engine.sync with src != dst), in host order - two builds that agree here
 also put every launch on the same stream and order the streams by the same edges.
 Modes: train (Trainer.forward_backward), train1 (the same with one object in the first image: one decoder iteration),
+train_terms (train with the border-weighted CE and the discriminative loss on: Trainer(border_weight=10, disc_weight=1)),
 train_eval (train() module called with training=False on a batch whose smallest image has four objects: four
 iterations with batch statistics), eval_head (eval() module with ground truth), eval (no instance head).
-usage: python scripts/launch_trace.py [train|train1|train_eval|eval|eval_head] [bf16|f32] > trace.txt    (diff two of them)
+usage: python scripts/launch_trace.py [train|train1|train_terms|train_eval|eval|eval_head] [bf16|f32] > trace.txt    (diff two of them)
        python scripts/launch_trace.py --counts trace.txt ...                            (launches per entry point)"""
 import collections, itertools, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,10 +37,10 @@ torch.manual_seed(0)
 m = ReSeg(2, mode != "eval", dtype=dtype).cuda()
 x, sem, ins, n = synth_batch(2, 64, 64, seed=2 if mode == "train_eval" else 0)
 x, sem, ins = x.cuda(), sem.cuda(), ins.cuda()
-if mode in ("train", "train1"):
+if mode in ("train", "train1", "train_terms"):
     if mode == "train1":
         n[0] = 1
-    tr = Trainer(m.train())
+    tr = Trainer(m.train(), **(dict(border_weight=10.0, disc_weight=1.0) if mode == "train_terms" else {}))
     step = lambda: tr.forward_backward(x, sem, ins, n)
 elif mode == "eval":
     m.eval()
@@ -74,7 +75,7 @@ def recorded_sync(src, dst, sync=E.sync):
 
 
 E.lib, E.sync = Recorder(E.lib), recorded_sync
-with torch.set_grad_enabled(mode in ("train", "train1")):
+with torch.set_grad_enabled(mode in ("train", "train1", "train_terms")):
     for i in range(3):
         E.profile = i == 2
         step()

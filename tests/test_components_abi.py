@@ -98,9 +98,9 @@ def test_the_new_methods_exist():
     import inspect
     import isa_amd  # noqa: F401
     from isa_amd.model import Model
-    from isa_amd.network import Network
+    from isa_amd.labelmaps import LabelOps
     from isa_amd.reseg import ReSeg
-    for cls, names in ((Network, ("cc_label", "cc_select")), (ReSeg, ("components", "split_components", "clean_instances")),
+    for cls, names in ((LabelOps, ("cc_label", "cc_select")), (ReSeg, ("components", "split_components", "clean_instances")),
                        (Model, ("predict_components",))):
         for name in names:
             assert callable(getattr(cls, name)), (cls, name)

@@ -100,9 +100,9 @@ def test_header_constants_equal_the_binding():
 def test_the_host_interface_has_the_new_names():
     import isa_amd  # noqa: F401
     from isa_amd.model import Model
-    from isa_amd.network import Network
+    from isa_amd.labelmaps import LabelOps
     from isa_amd.reseg import ReSeg
-    for cls, names in ((Network, ("contour_trace", "contour_topology")),
+    for cls, names in ((LabelOps, ("contour_trace", "contour_topology")),
                        (ReSeg, ("contours", "instance_topology", "polygons")), (Model, ("predict_polygons",))):
         for name in names:
             assert callable(getattr(cls, name)), (cls, name)

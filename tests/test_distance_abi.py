@@ -143,10 +143,11 @@ def test_the_new_methods_exist():
     import inspect
     import isa_amd  # noqa: F401
     from isa_amd.model import Model
-    from isa_amd.network import Network, SemCriterion
+    from isa_amd.labelmaps import LabelOps
+    from isa_amd.network import SemCriterion
     from isa_amd.reseg import ReSeg
     from isa_amd.trainer import Trainer
-    for cls, names in ((Network, ("distance_transform", "border_weights", "fill_labels")),
+    for cls, names in ((LabelOps, ("edt2", "border_map", "fill_labels")),
                        (ReSeg, ("distance_transform", "border_weights", "fill_instances")),
                        (SemCriterion, ("set_border", "border_key")), (Trainer, ("set_border",))):
         for name in names:

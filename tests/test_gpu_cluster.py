@@ -375,7 +375,7 @@ def test_predict_instances_default_is_the_attention_path():
         raise AssertionError("the default arguments reached the clustering code")
 
     net.segment = segment
-    new_code = [(net, "segment_embedding"), (net, "cluster_embedding"), (net, "embedding"), (net.net, "cluster")]
+    new_code = [(net, "segment_embedding"), (net, "cluster_embedding"), (net, "embedding"), (net, "cluster")]
     real = [getattr(obj, name) for obj, name in new_code]
     for obj, name in new_code:
         setattr(obj, name, trap)

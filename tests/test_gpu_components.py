@@ -399,8 +399,8 @@ def test_model_defaults_are_untouched_and_the_keywords_clean():
         raise AssertionError("the default arguments reached the component code")
 
     net.segment = segment
-    new_code = [(net, "clean_instances"), (net, "split_components"), (net, "components"), (net.net, "cc_label"),
-                (net.net, "cc_select")]
+    new_code = [(net, "clean_instances"), (net, "split_components"), (net, "components"), (net, "cc_label"),
+                (net, "cc_select")]
     for obj, name in new_code:
         setattr(obj, name, trap)
     prob, labels, count = model.predict_instances(x)

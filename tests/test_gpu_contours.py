@@ -436,8 +436,8 @@ def test_model_defaults_run_nothing_new_and_predict_polygons_outlines_the_labels
     def trap(*a, **k):
         raise AssertionError("the default arguments reached the contour code")
 
-    new_code = [(net, "contours"), (net, "instance_topology"), (net, "polygons"), (net.net, "contour_trace"),
-                (net.net, "contour_topology")]
+    new_code = [(net, "contours"), (net, "instance_topology"), (net, "polygons"), (net, "contour_trace"),
+                (net, "contour_topology")]
     for obj, name in new_code:
         setattr(obj, name, trap)
     _, labels, count = model.predict_instances(x)

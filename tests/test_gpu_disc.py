@@ -187,6 +187,7 @@ def test_three_runs_and_an_unrelated_launch_give_the_same_bits():
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_accumulate_adds_and_zero_overwrites(dtype):
     from isa_amd.engine import Act
+    from isa_amd.labelmaps import LabelOps
     from isa_amd.network import DiscCriterion
     m = model()
     x, labels, n_objects, _ = make_case("3x40x52-c24")
@@ -200,7 +201,8 @@ def test_accumulate_adds_and_zero_overwrites(dtype):
     crit = DiscCriterion("cuda")
     crit.set(1.0, 2.9, 1.5, 2, "full")
     alloc = lambda shape, dt: torch.full(shape, float("nan") if dt.is_floating_point else -1, dtype=dt, device="cuda")
-    scal, mu, grad = m.net.disc_loss(a, lab, 32, n, crit.cfg, crit.norm, alloc)       # every scratch buffer starts poisoned
+    # every scratch buffer starts poisoned
+    scal, mu, grad = LabelOps(lib=m.engine.lib, alloc=alloc).disc_loss(a, lab, 32, n, crit.cfg, crit.norm)
     over = Act(torch.full_like(buf, float("nan")), 0, C)
     grad(over, 0)
     pre = torch.randn(B, H, W, ld, device="cuda").to(dtype)

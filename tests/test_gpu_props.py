@@ -446,8 +446,8 @@ def test_model_defaults_run_nothing_new_and_the_keywords_select():
         raise AssertionError("the default arguments reached the measuring code")
 
     net.segment = segment
-    new_code = [(net, "instance_properties"), (net, "select_instances"), (net.net, "label_props"),
-                (net.net, "instance_props"), (net.net, "props_select"), (net.net, "relabel")]
+    new_code = [(net, "instance_properties"), (net, "select_instances"), (net, "label_props"),
+                (net, "instance_props"), (net, "props_select"), (net, "relabel")]
     for obj, name in new_code:
         setattr(obj, name, trap)
     prob, labels, count = model.predict_instances(x)

@@ -122,9 +122,9 @@ def test_the_host_interface_has_the_new_names():
     import inspect
     import isa_amd  # noqa: F401
     from isa_amd.model import Model
-    from isa_amd.network import Network
+    from isa_amd.labelmaps import LabelOps
     from isa_amd.reseg import ReSeg
-    for cls, names in ((Network, ("label_props", "props_select", "relabel")),
+    for cls, names in ((LabelOps, ("label_props", "props_select", "relabel")),
                        (ReSeg, ("instance_properties", "select_instances")), (Model, ("measure_instances",))):
         for name in names:
             assert callable(getattr(cls, name)), (cls, name)
